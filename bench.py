@@ -12,13 +12,19 @@ samples are independent so the ranks share nothing on the data path (weak
 scaling); RCCL only carries the barrier, the max-over-ranks timing, the
 early-stop flag (abort leg) and the 136-byte pose selections (all_gather).
 
-Besides the headline line (config 2) the JSON carries: `pose` (device pose
+A plain run does only what the headline needs: set up, W warmup steps, K timed
+steps, the outputs of the last timed step with `--dump-outputs DIR`, and one
+JSON line (paths/s of config 2, `ms_per_step`).
+
+With `--full` the run goes on and the JSON also carries: the pipelined and
+single-launch timings, `small_launch`, `ablation`, `pose` (device pose
 recovery + maximal support over the config-2 tracks),
 `early_abort` (config 3 / 4: time-to-first-good-pose), `noisy_pose` (config 5:
-sigma=1px noisy synthcurves, pose success rate vs paths/s), `roofline` and
-`cpu_baseline`.
+sigma=1px noisy synthcurves, pose success rate vs paths/s), `roofline`,
+`solutions` and `cpu_baseline`.  The options that size or disable those legs
+(--no-cpu-baseline, --abort-samples, --noisy-trials, ...) act under `--full`.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--samples S] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--samples S] [--dump-outputs DIR] [--full]
 """
 from __future__ import annotations
 
@@ -92,6 +98,13 @@ def parse():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--samples", type=int, default=100, help="RANSAC samples per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg (pipelined and single-launch timings, small "
+                         "launches, ablation, pose, roofline, early abort, config 5, CPU baselines); the options "
+                         "below that size those legs act only with it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0's shard) as DIR/<name>.npy (float32; a "
+                         "fixed seeded sample of the paths when the whole would exceed 64 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-small-launch", action="store_true",
                     help="skip the 1- and 8-sample launch timings (profiles: keeps the kernel trace to config 2)")
@@ -122,7 +135,33 @@ def parse():
                     help="samples of the 4-thread CPU-HC run (the reference's Num_Of_Cores default)")
     ap.add_argument("--cpu-samples-ref", type=int, default=100,
                     help="samples of the reference-build CPU-HC run (plain operators + OpenBLAS 0.3.23 cgesv)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, r):
+    """Writes the arrays a caller of the timed path receives (a TrackResult of
+    one tracking launch) as out_dir/<name>.npy in float32: tracks (paths, 31, 2),
+    converge, infinity (paths,) and stats (paths, 4).  When they would exceed
+    DUMP_LIMIT_BYTES, a fixed sample of the paths (default_rng(0), ascending) is
+    written instead, with its path numbers as path_index.npy (float64)."""
+    arrays = {"tracks": r.tracks, "converge": r.converge, "infinity": r.infinity, "stats": r.stats}
+    arrays = {k: v.cpu().numpy().astype(np.float32) for k, v in arrays.items()}
+    n = arrays["tracks"].shape[0]
+    per_path = sum(a[0].size * 4 for a in arrays.values()) + 8
+    keep = DUMP_LIMIT_BYTES // per_path
+    os.makedirs(out_dir, exist_ok=True)
+    if n > keep:
+        idx = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        arrays = {k: v[idx] for k, v in arrays.items()}
+        arrays["path_index"] = idx.astype(np.float64)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(v))
 
 
 SCHEMA = 5   # bench-line schema: bumped when a field changes meaning (ADVICE r4: roofline.achieved is dense-priced since 4)
@@ -258,12 +297,13 @@ def main():
     # step i: batch i on stream i % ns with its own buffers and workspace (independent
     # RANSAC batches; a stream reuses its buffers only after its previous launch)
     NS = max(1, args.streams)
-    NP = max(NS, args.pipelined_streams)
+    n_pipe = args.pipelined_streams if args.full else 0
+    NP = max(NS, n_pipe)
     # the serial leg runs on the current stream; the pipelined leg on streams of
     # its own (all non-default: the legacy default stream would order itself
     # against them)
     streams = [stream] + [torch.cuda.Stream(dev) for _ in range(NS - 1)]
-    pstreams = [torch.cuda.Stream(dev) for _ in range(args.pipelined_streams)]
+    pstreams = [torch.cuda.Stream(dev) for _ in range(n_pipe)]
     bufs = [res] + [tr.allocate(S, stats=True) for _ in range(NP - 1)]
     wss = [tr.new_workspace(S) for _ in range(NP)]
 
@@ -308,6 +348,62 @@ def main():
     own = {}
     elapsed = timed(NS, streams)
     el_own = own[NS]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, bufs[(args.steps - 1) % NS])   # the last timed step's buffers
+
+    t_max = elapsed                 # already the max over ranks
+    ms_per_step = t_max / args.steps * 1e3
+    paths = 312 * S * world
+    value = paths / (ms_per_step / 1e3)
+    step_ms = gather_floats([el_own * 1e3 / args.steps], dev, world)   # every rank's own wall time per step
+    bid = _abi.build_id()
+    line = {
+        "metric": "HC paths/sec (312 tracks x RANSAC samples)",
+        "value": round(value, 1),
+        "unit": "paths/s",
+        "n_gpus": world,
+        "world_size": dist_world,
+        "schema": SCHEMA,
+        "full": args.full,
+        "distributed": {
+            "launcher": ("bench.py (torch.distributed.run child it started)" if os.environ.get("HC_BENCH_SPAWNED")
+                         else "external (WORLD_SIZE set)") if world > 1 else "none (one process)",
+            "backend": dist.get_backend() if world > 1 else None,
+            "world_size_reported_by": "torch.distributed.get_world_size()" if world > 1 else None,
+            "devices": ("all ranks on cuda:%d (rehearsal)" % dev_idx) if "HC_BENCH_DEVICE" in os.environ
+                       else "cuda:LOCAL_RANK",
+            "per_rank_step_ms": [round(r_[0], 4) for r_ in step_ms],
+            "note": "step ms = the rank's own timed-loop time per step before the closing barrier; ms_per_step is "
+                    "the max over ranks after it"},
+        "ms_per_step": round(ms_per_step, 4),
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic RANSAC samples from the reference's synthcurves data (Triplet_Edgels_000, srand(0))",
+        "config": {"workload": "trifocal_2op1p_30x30 config 2: 100 RANSAC samples x 312 tracks per GPU, "
+                               "Abort_RANSAC=false",
+                   "samples_per_gpu": S, "tracks_per_sample": 312, "paths_per_step": paths,
+                   "streams": NS,
+                   "step": "reset tracks + one tracking launch; steps serialised on one stream, each a "
+                           "launch -> sync of one RANSAC batch (the reference's timer scope, "
+                           "GPU_HC_Solver.cpp:384,446)" if NS == 1 else
+                           f"reset tracks + one tracking launch, steps rotating over {NS} streams",
+                   "parallelism": f"samples sharded over {world} GPU(s), no data-path collective",
+                   "GPUHC_Max_Steps": tr.settings.max_steps,
+                   "GPUHC_Max_Correction_Steps": tr.settings.max_corrections,
+                   "kernel": _abi.lib().hc_trifocal_version().decode(),
+                   "build_id": bid},
+    }
+    if not args.full:   # the plain run ends here: nothing but the headline's own work
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
     pipe_elapsed = timed(args.pipelined_streams, pstreams) if args.pipelined_streams > 1 else None
 
     # kernel time of one launch alone (serial, HIP events on the launch stream): the
@@ -321,8 +417,8 @@ def main():
     torch.cuda.synchronize(dev)
     tr.workspace_status()   # raises on a device-side failure (table / time-slicing hand-over)
     launch_ms = np.array([a_.elapsed_time(b_) for a_, b_ in ev])
-    # every rank's own kernel time (median of its 5 single launches) and wall time per step
-    rank_ms = gather_floats([float(np.median(launch_ms)), el_own * 1e3 / args.steps], dev, world)
+    # every rank's own kernel time (median of its 5 single launches)
+    rank_ms = gather_floats([float(np.median(launch_ms))], dev, world)
 
     # small launches (1 and 8 samples): the latency-mode tracking kernel the
     # launcher picks when a launch fills at most half of the path slots, against
@@ -386,17 +482,12 @@ def main():
     steps_sum = int(host["stats"]["steps"].astype(np.int64).sum())
     corr_sum = int(host["stats"]["corrections"].astype(np.int64).sum())
     flops = steps_sum * 4 * FLOP_PRED_STAGE + corr_sum * FLOP_CORR_STAGE          # dense-LU convention
-    bid = _abi.build_id()
     lu_frac, lu_frac_src = lu_executed_fraction(bid)
     flops_exec = None if lu_frac is None else \
         flops - (steps_sum * 4 + corr_sum) * LU_UPDATE_DENSE_FLOP * (1.0 - lu_frac)   # LU updates as executed
     from trifocal_pose_estimation_using_improved_gpuhc_amd import count_solutions
     counts = count_solutions(host["tracks"], host["converge"], host["infinity"])
 
-    t_max = elapsed                 # already the max over ranks
-    ms_per_step = t_max / args.steps * 1e3
-    paths = 312 * S * world
-    value = paths / (ms_per_step / 1e3)
     pipelined = None if pipe_elapsed is None else paths * args.steps / pipe_elapsed
 
     # ---- early abort (config 3 at N=1, config 4 at N=8): time-to-first-good-pose.
@@ -539,57 +630,23 @@ def main():
         hbm_s = None if traffic is None else ((traffic_ns or float(np.median(launch_ms)) * 1e6) / 1e9)
         alg_bytes = algorithmic_bytes(S)
         k_ms = [r_[0] for r_ in rank_ms]
-        line = {
-            "metric": "HC paths/sec (312 tracks x RANSAC samples)",
-            "value": round(value, 1),
-            "unit": "paths/s",
-            "n_gpus": world,
-            "world_size": dist_world,
-            "schema": SCHEMA,
-            "distributed": {
-                "launcher": ("bench.py (torch.distributed.run child it started)" if os.environ.get("HC_BENCH_SPAWNED")
-                             else "external (WORLD_SIZE set)") if world > 1 else "none (one process)",
-                "backend": dist.get_backend() if world > 1 else None,
-                "world_size_reported_by": "torch.distributed.get_world_size()" if world > 1 else None,
-                "devices": ("all ranks on cuda:%d (rehearsal)" % dev_idx) if "HC_BENCH_DEVICE" in os.environ
-                           else "cuda:LOCAL_RANK",
-                "per_rank_kernel_ms": [round(v, 4) for v in k_ms],
-                "kernel_ms_min": round(min(k_ms), 4), "kernel_ms_max": round(max(k_ms), 4),
-                "per_rank_step_ms": [round(r_[1], 4) for r_ in rank_ms],
-                "note": "kernel ms = median of each rank's 5 single config-2 launches (HIP events); step ms = "
-                        "the rank's own timed-loop time per step before the closing barrier; ms_per_step is "
-                        "the max over ranks after it"},
-            "ms_per_step": round(ms_per_step, 4),
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic RANSAC samples from the reference's synthcurves data (Triplet_Edgels_000, srand(0))",
-            "config": {"workload": "trifocal_2op1p_30x30 config 2: 100 RANSAC samples x 312 tracks per GPU, "
-                                   "Abort_RANSAC=false",
-                       "samples_per_gpu": S, "tracks_per_sample": 312, "paths_per_step": paths,
-                       "streams": NS,
-                       "step": "reset tracks + one tracking launch; steps serialised on one stream, each a "
-                               "launch -> sync of one RANSAC batch (the reference's timer scope, "
-                               "GPU_HC_Solver.cpp:384,446)" if NS == 1 else
-                               f"reset tracks + one tracking launch, steps rotating over {NS} streams",
-                       "single_launch_paths_per_s": round(paths / (float(np.median(launch_ms)) / 1e3), 1),
-                       "pipelined_paths_per_s": None if pipelined is None else round(pipelined, 1),
-                       "small_launch": dict(small, note="ms per tracking launch of 1 / 8 samples (median of 5, HIP "
-                                                         "events): the latency-mode kernel the launcher picks at "
-                                                         "most half of the path slots, and the throughput kernel "
-                                                         "forced"),
-                       "pipelined_streams": args.pipelined_streams if pipelined is not None else None,
-                       "pipelined_note": "the same K steps with consecutive batches overlapped on "
-                                         f"{args.pipelined_streams} streams (own buffers each): a batch's "
-                                         "tail runs beside the next batch's start; not the headline",
-                       "parallelism": f"samples sharded over {world} GPU(s), no data-path collective",
-                       "GPUHC_Max_Steps": tr.settings.max_steps,
-                       "GPUHC_Max_Correction_Steps": tr.settings.max_corrections,
-                       "kernel": _abi.lib().hc_trifocal_version().decode(),
-                       "build_id": bid},
+        line["distributed"].update({
+            "per_rank_kernel_ms": [round(v, 4) for v in k_ms],
+            "kernel_ms_min": round(min(k_ms), 4), "kernel_ms_max": round(max(k_ms), 4),
+            "note": "kernel ms = median of each rank's 5 single config-2 launches (HIP events); "
+                    + line["distributed"]["note"]})
+        line["config"].update({
+            "single_launch_paths_per_s": round(paths / (float(np.median(launch_ms)) / 1e3), 1),
+            "pipelined_paths_per_s": None if pipelined is None else round(pipelined, 1),
+            "small_launch": dict(small, note="ms per tracking launch of 1 / 8 samples (median of 5, HIP "
+                                              "events): the latency-mode kernel the launcher picks at "
+                                              "most half of the path slots, and the throughput kernel "
+                                              "forced"),
+            "pipelined_streams": args.pipelined_streams if pipelined is not None else None,
+            "pipelined_note": "the same K steps with consecutive batches overlapped on "
+                              f"{args.pipelined_streams} streams (own buffers each): a batch's "
+                              "tail runs beside the next batch's start; not the headline"})
+        line.update({
             "roofline": {"bound": "valu_fp32", "achieved": round(achieved_tf, 3), "peak": FP32_PEAK_TFLOPS,
                          "unit": "TFLOP/s", "frac": round(achieved_tf / FP32_PEAK_TFLOPS, 4),
                          "traffic": traffic,
@@ -636,7 +693,7 @@ def main():
                      "note": "device candidate filter + Cayley pose + reprojection inlier scoring of every "
                              "candidate over all triplet edgels + maximal-support selection "
                              "(Evaluations.cpp:298-504), merged over ranks (RCCL all_gather)"},
-        }
+        })
         tp_ms = float(np.median(launch_ms))
         leg = lambda ms, st: {"kernel_ms": round(ms, 4), "paths_per_s": round(312 * S / (ms / 1e3), 1),  # noqa: E731
                               "stages": st}

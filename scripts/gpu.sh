@@ -6,11 +6,11 @@
 #   tests     pytest -m gpu                          -> gpurun_out/TAG_pytest.log
 #   smoke     __graft_entry__.smoke()
 #   luwork    LU work of the HC_DIAG_LUWORK build    -> TAG_lu_work.json
-#   bench     the default bench line                 -> TAG_bench.json
+#   bench     the full bench line (bench.py --full)  -> TAG_bench.json
 #   profile   kernel trace + PMC passes + summary    -> TAG_pmc_summary.json, TAG_kernel_stats.csv
 #   traffic   kernel trace + FETCH/WRITE passes only -> TAG_pmc_summary.json
 #   datasets  held-out datasets (scripts/datasets.py)-> TAG_datasets.jsonl
-#   n2        bare `bench.py --gpus 2` rehearsal, both ranks on cuda:0 -> TAG_bench_n2_rehearsal.json
+#   n2        bare `bench.py --full --gpus 2` rehearsal, both ranks on cuda:0 -> TAG_bench_n2_rehearsal.json
 #   ab        interleaved A/B of builds: extra args NAME=lib/libX.so ... (package-relative)
 #   ttfp_ab   time to the first pose of builds NAME=lib/libX.so ... (package-relative): the abort-mode
 #             parity tests on each, then 3 interleaved rounds of scripts/ttfp.py (config 3 in both
@@ -41,9 +41,9 @@ for step in ${STEPS//,/ }; do
     tests) run tests 900 python -u -m pytest tests -m gpu -x -v --timeout 200 --timeout-method thread > $O/${T}_pytest.log 2>&1; rc=$?; tail -3 $O/${T}_pytest.log ;;
     smoke) run smoke 300 python -c 'import __graft_entry__ as g; g.smoke()'; rc=$? ;;
     luwork) HC_TRIFOCAL_LIB=$L/libhc_trifocal_luwork.so run luwork 200 python scripts/lu_work.py > $O/${T}_lu_work.json; rc=$?; cat $O/${T}_lu_work.json ;;
-    bench) run bench 600 python bench.py $BENCH_ARGS > $O/${T}_bench.json 2> $O/${T}_bench.err; rc=$?; cat $O/${T}_bench.json ;;
+    bench) run bench 600 python bench.py --full $BENCH_ARGS > $O/${T}_bench.json 2> $O/${T}_bench.err; rc=$?; cat $O/${T}_bench.json ;;
     profile|traffic)
-      B="python bench.py --steps 30 --warmup 3 --no-cpu-baseline --no-small-launch --abort-samples 0 --noisy-trials 0 --streams 1 --pipelined-streams 0"
+      B="python bench.py --full --steps 30 --warmup 3 --no-cpu-baseline --no-small-launch --abort-samples 0 --noisy-trials 0 --streams 1 --pipelined-streams 0"
       run trace 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${T}_trace -o run -- $B > $O/${T}_trace.log 2>&1; rc=$?
       if [ $step = profile ]; then
         SETS=("SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_LDS SQ_WAIT_INST_ANY SQ_WAIT_ANY"
@@ -64,7 +64,7 @@ for step in ${STEPS//,/ }; do
         cp $O/${T}_trace/run_kernel_stats.csv $O/${T}_kernel_stats.csv
       fi ;;
     datasets) run datasets 900 python scripts/datasets.py $L/libhc_trifocal_luwork.so "$@" > $O/${T}_datasets.jsonl; rc=$?; cat $O/${T}_datasets.jsonl ;;
-    n2) HC_BENCH_DEVICE=0 HC_BENCH_BACKEND=gloo run n2 700 python3 bench.py --gpus 2 > $O/${T}_bench_n2_rehearsal.json 2> $O/${T}_bench_n2.err; rc=$?; cat $O/${T}_bench_n2_rehearsal.json ;;
+    n2) HC_BENCH_DEVICE=0 HC_BENCH_BACKEND=gloo run n2 700 python3 bench.py --full --gpus 2 > $O/${T}_bench_n2_rehearsal.json 2> $O/${T}_bench_n2.err; rc=$?; cat $O/${T}_bench_n2_rehearsal.json ;;
     ab)
       args=""; last=""
       for kv in "$@"; do args="$args ${kv%%=*}=$P/${kv#*=}"; last=$P/${kv#*=}; done
