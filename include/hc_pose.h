@@ -72,6 +72,23 @@ hcStatus hc_trifocal_pose_support(int num_paths, const hcComplex *tracks, const 
                                   int num_edgels, const float *locations, const float *K, int flags,
                                   int32_t *inliers, hcPoseSelection *selection, hcStream stream);
 
+/* The same over the samples of several image triplets in one call (the layout
+ * of hc_trifocal_2op1p_30x30_track_abort_grouped): the candidates of sample s
+ * are scored on groups[sample_group[s]] (its edgels, its K), and selections[t]
+ * receives triplet t's selection (num_groups of them).  The key is
+ * count << 32 | b with b the call's batch id, and path21 / path31 are the
+ * call's batch ids; b is monotone in a group's own sample order, so each group
+ * selects the candidate that hc_trifocal_pose_support over just its samples
+ * selects, with the same counts and the same pose bits.  A group without a
+ * candidate gets the "none" selection (paths -1, counts -1, zero pose).
+ * HC_POSE_REFERENCE_QUIRKS is rejected (HC_ERROR_INVALID_VALUE): its literal
+ * indexing has no per-group meaning.  Group ids outside [0, num_groups) are a
+ * contract violation (not validated on the device). */
+hcStatus hc_trifocal_pose_support_grouped(int num_paths, const hcComplex *tracks, const uint8_t *converge,
+                                          int num_groups, const hcTripletGroup *groups,
+                                          const int32_t *sample_group, int flags,
+                                          int32_t *inliers, hcPoseSelection *selections /* T */, hcStream stream);
+
 /* Host: merges the selections of several launches / GPUs (each over its own
  * batch-id range starting at path_offsets[i]) into one, with global batch ids:
  * the keys are re-based and the maximal key wins per view, exactly as if one

@@ -156,6 +156,48 @@ hcStatus hc_trifocal_2op1p_30x30_track_abort(const hcTrackArgs *args, const hcAb
                                              void *workspace, size_t workspace_bytes,
                                              hcStream stream);
 
+/* ---- grouped (multi-triplet) abort tracking ----
+ * One launch over the samples of several image triplets, each with its own
+ * edgels, intrinsics and found flag.  (Plain tracking needs nothing of this: a
+ * sample is just its target_params / diff_params row.) */
+
+/* One image triplet's scene data, resident in device memory. */
+typedef struct {
+    const float *locations;   /* E x 6 floats, as hcAbortArgs::triplet_edge_locations */
+    const float *K;           /* 9 floats, row-major */
+    int32_t num_edgels;       /* E > 0 */
+    int32_t pad;
+} hcTripletGroup;             /* 24 bytes */
+
+typedef struct {
+    int num_groups;                    /* T >= 1 */
+    const hcTripletGroup *groups;      /* device array of T */
+    const int32_t *sample_group;       /* device, one per sample of the launch, each in [0, T) */
+    uint32_t *group_found;             /* device, T words, in/out: the live per-triplet flag */
+    int32_t *trifocal_sols_batch_index;/* 312*N ints, caller sets -1 (as hcAbortArgs) */
+    uint64_t *group_found_ticks;       /* optional, T words: s_memrealtime of each group's first
+                                          find, 0 = none; caller zeroes */
+    int inflight_stop;                 /* as hcAbortArgs::inflight_stop, applied per group */
+} hcGroupedAbortArgs;
+
+/* hc_trifocal_2op1p_30x30_track_abort with "the flag" replaced by "the flag of
+   the path's own triplet".  A path of sample s belongs to group
+   t = sample_group[s]: it is skipped iff group_found[t] is set when it is
+   dequeued (with inflight_stop it also stops at its next step boundary once
+   group_found[t] is set); on convergence it is scored on groups[t]'s edgels
+   with groups[t].K, the 0.90 gate dividing by groups[t].num_edgels; a pass sets
+   group_found[t], writes batch_index[b] = b, group_found_ticks[t] (the first
+   writer wins) and the inlier counts into stats.  A word of group_found that is
+   already set on entry makes that group's paths skip: the carry-over between
+   chunked launches.  The caller zeroes group_found for a fresh run.  Paths are
+   dequeued sample-major, so the caller's sample order decides how the triplets
+   interleave.  Single-GPU: there is no peer flag.  Group ids outside [0, T) are
+   a contract violation like a bad pointer (not validated on the device).  The
+   workspace's found timestamp stays 0; its start timestamp
+   (hc_trifocal_read_timestamps) is the one to subtract from group_found_ticks. */
+hcStatus hc_trifocal_2op1p_30x30_track_abort_grouped(const hcTrackArgs *args, const hcGroupedAbortArgs *g,
+                                                     void *workspace, size_t workspace_bytes, hcStream stream);
+
 /* The cross-process early-stop flag of hcAbortArgs::peer_found.  It lives in
    the creating process's device memory, allocated uncached
    (hipExtMallocWithFlags(hipDeviceMallocUncached): coherent across devices

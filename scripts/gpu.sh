@@ -17,6 +17,7 @@
 #             semantics, 12 runs each; the lone sample, 12 runs)      -> TAG_ttfp.jsonl
 #   phases    per-phase cycles of the HC_DIAG_PHASES build (scripts/diag_phases.py)
 #   stress    time slicing under concurrent streams (scripts/slice_stress.py: 4 cold, 4 warm, 8 cold)
+#   multi     T sequential single-triplet runs against one grouped run (scripts/multi_triplet.py) -> TAG_multi.json
 #   validate  tests,luwork,bench,profile,datasets
 # Extra environment: BENCH_ARGS (bench step), AB_ROUNDS (ab step, default 3), AB_ARGS (more ab_track.py options), TTFP_ARGS (ttfp_ab step,
 # e.g. "--dataset 10").
@@ -93,6 +94,7 @@ for l in open('$O/${T}_ttfp.jsonl'):
     d=json.loads(l); g[(d['build'],d['samples'],d['inflight_stop'])].append(d['median'])
 for k,v in sorted(g.items()): print(k, v)" ;;
     phases) HC_TRIFOCAL_LIB=$L/libhc_trifocal_phases.so run phases 300 python scripts/diag_phases.py > $O/${T}_phases.json; rc=$?; cat $O/${T}_phases.json ;;
+    multi) run multi 300 python scripts/multi_triplet.py "$@" > $O/${T}_multi.json; rc=$?; cat $O/${T}_multi.json ;;
     stress)
       run stress4 300 python scripts/slice_stress.py $O/${T}_stress4.jsonl 4 4 > /dev/null 2>&1; rc=$?
       [ $rc -eq 0 ] && { run stress4w 300 python scripts/slice_stress.py $O/${T}_stress4w.jsonl 4 4 --warm-streams > /dev/null 2>&1; rc=$?; }

@@ -71,6 +71,27 @@ class hcAbortArgs(C.Structure):
                 ("peer_found", C.c_void_p)]
 
 
+class hcTripletGroup(C.Structure):
+    """One image triplet's scene data (device pointers): 24 bytes."""
+    _fields_ = [("locations", C.c_void_p),
+                ("K", C.c_void_p),
+                ("num_edgels", C.c_int32),
+                ("pad", C.c_int32)]
+
+
+TRIPLET_GROUP_BYTES = C.sizeof(hcTripletGroup)
+
+
+class hcGroupedAbortArgs(C.Structure):
+    _fields_ = [("num_groups", C.c_int),
+                ("groups", C.c_void_p),
+                ("sample_group", C.c_void_p),
+                ("group_found", C.c_void_p),
+                ("trifocal_sols_batch_index", C.c_void_p),
+                ("group_found_ticks", C.c_void_p),
+                ("inflight_stop", C.c_int)]
+
+
 class hcIpcHandle(C.Structure):
     _fields_ = [("reserved", C.c_ubyte * 64)]
 
@@ -139,6 +160,15 @@ def lib() -> C.CDLL:
         L.hc_trifocal_pose_support.restype = C.c_int
         L.hc_trifocal_pose_support.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                                C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        # grouped (multi-triplet) launches (bound where present, as below)
+        if hasattr(L, "hc_trifocal_2op1p_30x30_track_abort_grouped"):
+            L.hc_trifocal_2op1p_30x30_track_abort_grouped.restype = C.c_int
+            L.hc_trifocal_2op1p_30x30_track_abort_grouped.argtypes = [C.POINTER(hcTrackArgs),
+                                                                      C.POINTER(hcGroupedAbortArgs), C.c_void_p,
+                                                                      C.c_size_t, C.c_void_p]
+            L.hc_trifocal_pose_support_grouped.restype = C.c_int
+            L.hc_trifocal_pose_support_grouped.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                                           C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.hc_pose_merge.restype = None
         L.hc_pose_merge.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(hcPoseSelection)]
         L.hc_pose_residuals.restype = C.c_int
@@ -188,6 +218,7 @@ DECLARED_SYMBOLS = (
     "hc_read_start_sols", "hc_read_start_params", "hc_read_int_table", "hc_read_float_table",
     "hc_count_triplet_edgels", "hc_read_triplet_edgels", "hc_split_samples", "hc_prepare_target_params",
     "hc_count_solutions",
+    "hc_trifocal_2op1p_30x30_track_abort_grouped", "hc_trifocal_pose_support_grouped",
     "hc_trifocal_pose_support", "hc_pose_merge", "hc_pose_residuals", "hc_write_converged_sols",
     "hc_add_pixel_noise", "hc_write_triplet_edgels",
 )

@@ -168,6 +168,12 @@ struct KArgs {
     unsigned *rq;                   // ring counters, one 256-B line each: [0] head, [64] tail, [128] avail, [192] meta
     unsigned long long *susp;       // suspend blocks, SUSP_WORDS per path id
     unsigned long long *ring;       // ring_tag(epoch, ticket) << 32 | path id
+    // grouped abort mode (hcGroupedAbortArgs): the scene and the found flag of
+    // a path's own triplet instead of edgels / K / ws->found / found_flag
+    const hcTripletGroup *groups;
+    const int32_t *sample_group;
+    unsigned *group_found;
+    unsigned long long *group_ticks;   // or null
 };
 // rq layout: counters zeroed by k_prep_tables every launch; meta: the launch
 // epoch, a magic word and the ring entries already cleared (persist)
@@ -873,6 +879,7 @@ __device__ unsigned long long g_diag_phase[13];
 typedef uint32_t T_hxd_t[HX_NSLOT / 2][32];
 template <bool ABORT, int MINW, bool GTAB, bool ARCH = false, bool LUS = true>
 __global__ void __launch_bounds__(WG_THREADS, MINW) k_track(KArgs a) {
+    constexpr bool GROUPED = false;   // (k_track_grouped below)
     // LU (hc_lu.hpp): the abort kernel's time to the first pose is a lone
     // path's latency, so it runs the latency mode (one LDS round trip per pivot
     // step, in batches of HC_LU_LATB_COLS columns); the tracking kernel the
@@ -898,9 +905,30 @@ __global__ void __launch_bounds__(WG_THREADS, MINW) k_track(KArgs a) {
 #endif
 template <bool LUS>
 __global__ void __launch_bounds__(WG_THREADS, HC_SMALL_MINW) k_track_small(KArgs a) {
-    constexpr bool ABORT = false, GTAB = true, ARCH = false;
+    constexpr bool ABORT = false, GTAB = true, ARCH = false, GROUPED = false;
     constexpr int LUCH = LU_CHUNK;
     constexpr int LULAT = HC_SMALL_LAT;
+#include "hc_track_body.inc"
+}
+
+// Grouped (multi-triplet) abort launches (hcGroupedAbortArgs): the abort
+// instantiation's body and configuration (k_track<true, HC_ABORT_MINW,
+// HC_ABORT_GTAB>) with GROUPED on: the scoring set, K and the found flag are
+// those of the path's own triplet, looked up from the slot's sample where they
+// are used (nothing of a group is carried across the stage loop).  A kernel of
+// its own rather than one more template parameter of k_track, so the existing
+// instantiations keep their code and their names in kernel traces.
+#ifndef HC_ABORT_GTAB
+#define HC_ABORT_GTAB true
+#endif
+#ifndef HC_ABORT_MINW
+#define HC_ABORT_MINW 4
+#endif
+template <bool LUS>
+__global__ void __launch_bounds__(WG_THREADS, HC_ABORT_MINW) k_track_grouped(KArgs a) {
+    constexpr bool ABORT = true, GTAB = HC_ABORT_GTAB, ARCH = false, GROUPED = true;
+    constexpr int LUCH = LU_CHUNK;
+    constexpr int LULAT = HC_LU_LATB_COLS;
 #include "hc_track_body.inc"
 }
 
@@ -1053,8 +1081,14 @@ static int grid_for(int waves_needed, const void *kernel) {
 static int resident_wgs(const void *kernel) { return grid_for(INT_MAX, kernel); }
 
 static hcStatus launch_track(const hcTrackArgs *t, const hcAbortArgs *ab, void *workspace, size_t wsb,
-                             hcStream stream, bool abort_mode, bool truncate = true, bool explicit_rk = false) {
+                             hcStream stream, bool abort_mode, bool truncate = true, bool explicit_rk = false,
+                             const hcGroupedAbortArgs *gr = nullptr) {
+    // gr: the grouped (multi-triplet) abort launch; abort_mode is set, ab is null
+    const bool grouped = gr != nullptr;
     if (!t || t->sub_ransac_iters < 0) return HC_ERROR_INVALID_VALUE;
+    if (grouped && (gr->num_groups < 1 || !gr->groups || !gr->sample_group || !gr->group_found ||
+                    !gr->trifocal_sols_batch_index))
+        return HC_ERROR_INVALID_VALUE;
     if (!workspace || wsb < ws_bytes_needed()) return HC_ERROR_WORKSPACE;
     if (t->sub_ransac_iters == 0) return HC_SUCCESS;
     if ((!t->start_sols && !t->start_sols_array) || (!t->tracks && !t->track_array) || !t->start_params ||
@@ -1062,7 +1096,7 @@ static hcStatus launch_track(const hcTrackArgs *t, const hcAbortArgs *ab, void *
         return HC_ERROR_INVALID_VALUE;
     if (t->settings.max_steps < 0 || t->settings.max_corrections < 0 || t->settings.delta_t_inc_steps < 0)
         return HC_ERROR_INVALID_VALUE;
-    if (abort_mode && (!ab || ab->num_triplet_edgels <= 0 || !ab->triplet_edge_locations || !ab->intrinsic_matrix ||
+    if (abort_mode && !grouped && (!ab || ab->num_triplet_edgels <= 0 || !ab->triplet_edge_locations || !ab->intrinsic_matrix ||
                        !ab->found_trifocal_sols || !ab->trifocal_sols_batch_index))
         return HC_ERROR_INVALID_VALUE;
     const long long paths = (long long)t->sub_ransac_iters * NTRK;
@@ -1107,8 +1141,9 @@ static hcStatus launch_track(const hcTrackArgs *t, const hcAbortArgs *ab, void *
         k.ring_test = g_ring_test.load(std::memory_order_relaxed);
     }
     // control block reset, compacted tables (skipped when cached), ring reset
-    PrepArgs pa{t->unified_index, ws, abort_mode ? ab->found_trifocal_sols : nullptr,
-                abort_mode ? ab->peer_found : nullptr, k.rq, k.ring, k.ring_cap,
+    // (a grouped launch's flags are the caller's group_found words: Workspace::found stays 0, unused)
+    PrepArgs pa{t->unified_index, ws, abort_mode && !grouped ? ab->found_trifocal_sols : nullptr,
+                abort_mode && !grouped ? ab->peer_found : nullptr, k.rq, k.ring, k.ring_cap,
                 k.rq ? (unsigned)(ring_bytes(k.ring_cap) / 8) : 0u,
                 k.rq ? (unsigned)susp_end : 0u};
     hipLaunchKernelGGL(k_prep_tables, dim3(1), dim3(PREP_THREADS), 0, s, pa);
@@ -1126,12 +1161,14 @@ static hcStatus launch_track(const hcTrackArgs *t, const hcAbortArgs *ab, void *
 #ifndef HC_ABORT_MINW
 #define HC_ABORT_MINW 4
 #endif
-    const void *kern = abort_mode ? (const void *)k_track<true, HC_ABORT_MINW, HC_ABORT_GTAB>
+    const void *kern = grouped      ? (const void *)k_track_grouped<true>
+                       : abort_mode ? (const void *)k_track<true, HC_ABORT_MINW, HC_ABORT_GTAB>
                        : archived ? (const void *)k_track<false, 5, true, true>
                                   : (const void *)k_track<false, 5, true>;
     // the structure-agnostic twin, enqueued after it: exactly one of the two
     // tracks (EvalTables::lu_struct), the other returns at its first load
-    const void *kern_any = abort_mode ? (const void *)k_track<true, HC_ABORT_MINW, HC_ABORT_GTAB, false, false>
+    const void *kern_any = grouped      ? (const void *)k_track_grouped<false>
+                           : abort_mode ? (const void *)k_track<true, HC_ABORT_MINW, HC_ABORT_GTAB, false, false>
                            : archived ? (const void *)k_track<false, 5, true, true, false>
                                       : (const void *)k_track<false, 5, true, false, false>;
 #ifndef HC_SMALL_LAUNCH
@@ -1152,7 +1189,14 @@ static hcStatus launch_track(const hcTrackArgs *t, const hcAbortArgs *ab, void *
     const int grid = grid_for((int)((paths + 1) / 2), kern);
     const int grid_any = grid_for((int)((paths + 1) / 2), kern_any);
     if (grid <= 0 || grid_any <= 0) return HC_ERROR_DEVICE;
-    if (abort_mode) {
+    if (grouped) {
+        k.inflight_stop = gr->inflight_stop ? 1 : 0;
+        k.batch_index = gr->trifocal_sols_batch_index;
+        k.groups = gr->groups;
+        k.sample_group = gr->sample_group;
+        k.group_found = gr->group_found;
+        k.group_ticks = (unsigned long long *)gr->group_found_ticks;
+    } else if (abort_mode) {
         k.num_edgels = ab->num_triplet_edgels;
         k.inflight_stop = ab->inflight_stop ? 1 : 0;
         k.peer_found = ab->peer_found;
@@ -1246,6 +1290,12 @@ hcStatus hc_trifocal_2op1p_30x30_track(const hcTrackArgs *args, void *workspace,
 hcStatus hc_trifocal_2op1p_30x30_track_abort(const hcTrackArgs *args, const hcAbortArgs *abort_args,
                                              void *workspace, size_t workspace_bytes, hcStream stream) {
     return hc::launch_track(args, abort_args, workspace, workspace_bytes, stream, true);
+}
+
+hcStatus hc_trifocal_2op1p_30x30_track_abort_grouped(const hcTrackArgs *args, const hcGroupedAbortArgs *g,
+                                                     void *workspace, size_t workspace_bytes, hcStream stream) {
+    if (!g) return HC_ERROR_INVALID_VALUE;
+    return hc::launch_track(args, nullptr, workspace, workspace_bytes, stream, true, true, false, g);
 }
 
 hcStatus hc_trifocal_2op1p_30x30_track_ph_codeopt(const hcTrackArgs *args, void *workspace, size_t workspace_bytes,

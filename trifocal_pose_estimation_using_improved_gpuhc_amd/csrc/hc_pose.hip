@@ -15,6 +15,8 @@
 // view on key = count << 32 | b (largest count, ties -> largest b = the last
 // candidate attaining the maximum, the rule of Evaluations.cpp:460,466); a
 // one-wave epilogue decodes the keys and writes the selected poses.
+// The grouped kernels do the same for the samples of several triplets at
+// once, each candidate on its own triplet's scene, one selection per triplet.
 #include "../../include/hc_pose.h"
 #include "hc_device.hpp"
 
@@ -93,6 +95,22 @@ __device__ __forceinline__ bool reproj_inlier(float g0, float g1, float h0, floa
     return err < 2.0f;   // REPROJ_ERROR_INLIER_THRESH (definitions.hpp:17)
 }
 
+// Inlier counts of one candidate pose over a triplet's edgels: the 64 lanes
+// stride over the edgels, the counts are wave-reduced (every lane gets them).
+__device__ __forceinline__ void count_inliers(const Pose &P, int E, const float *__restrict__ loc, float K0, float K2,
+                                              float K4, float K5, int lane, int &c21, int &c31) {
+    int a21 = 0, a31 = 0;
+    for (int e = lane; e < E; e += WAVE) {
+        const float2 g01 = *reinterpret_cast<const float2 *>(loc + (size_t)e * 6);
+        const float2 g23 = *reinterpret_cast<const float2 *>(loc + (size_t)e * 6 + 2);
+        const float2 g45 = *reinterpret_cast<const float2 *>(loc + (size_t)e * 6 + 4);
+        a21 += reproj_inlier(g01.x, g01.y, g23.x, g23.y, P.R, P.t, K0, K2, K4, K5) ? 1 : 0;
+        a31 += reproj_inlier(g01.x, g01.y, g45.x, g45.y, P.R + 9, P.t + 3, K0, K2, K4, K5) ? 1 : 0;
+    }
+    c21 = wave_sum_i(a21);
+    c31 = wave_sum_i(a31);
+}
+
 __device__ __forceinline__ bool is_converged(const uint8_t *conv, int b, int num_paths, bool quirks) {
     if (!quirks) return conv[b] != 0;
     const long long ci = (long long)b + (long long)NTRK * (b / NTRK);   // Evaluations.cpp:317
@@ -122,16 +140,7 @@ __global__ void __launch_bounds__(256) k_pose_support(int num_paths, const cf *_
             if ((im & 0x3F000000ull) == 0x3F000000ull && (dp & 0xFFull) == 0xFFull) {
                 Pose P;
                 make_pose(quirks ? tracks : x, P);   // quirk: converted from the base pointer (:334-341)
-                int a21 = 0, a31 = 0;
-                for (int e = lane; e < E; e += WAVE) {
-                    const float2 g01 = *reinterpret_cast<const float2 *>(loc + (size_t)e * 6);
-                    const float2 g23 = *reinterpret_cast<const float2 *>(loc + (size_t)e * 6 + 2);
-                    const float2 g45 = *reinterpret_cast<const float2 *>(loc + (size_t)e * 6 + 4);
-                    a21 += reproj_inlier(g01.x, g01.y, g23.x, g23.y, P.R, P.t, K0, K2, K4, K5) ? 1 : 0;
-                    a31 += reproj_inlier(g01.x, g01.y, g45.x, g45.y, P.R + 9, P.t + 3, K0, K2, K4, K5) ? 1 : 0;
-                }
-                c21 = wave_sum_i(a21);
-                c31 = wave_sum_i(a31);
+                count_inliers(P, E, loc, K0, K2, K4, K5, lane, c21, c31);
                 if (lane == 0) {
                     atomicAdd(&sel->num_candidates, 1);
                     atomicMax(reinterpret_cast<unsigned long long *>(&sel->key21),
@@ -148,11 +157,9 @@ __global__ void __launch_bounds__(256) k_pose_support(int num_paths, const cf *_
     }
 }
 
-// decode the keys; pose of the selected path (Evaluations.cpp:496-501)
-__global__ void __launch_bounds__(64) k_pose_final(int num_paths, const cf *__restrict__ tracks,
-                                                   const int32_t *__restrict__ inl, int flags, hcPoseSelection *sel) {
-    if (threadIdx.x != 0) return;
-    const bool quirks = (flags & HC_POSE_REFERENCE_QUIRKS) != 0;
+// decode the keys of one selection; pose of the selected path (Evaluations.cpp:496-501)
+__device__ __forceinline__ void decode_selection(int num_paths, const cf *__restrict__ tracks,
+                                                 const int32_t *__restrict__ inl, bool quirks, hcPoseSelection *sel) {
     const bool any = sel->num_candidates > 0;
     for (int v = 0; v < 2; v++) {
         const uint64_t key = v == 0 ? sel->key21 : sel->key31;
@@ -172,6 +179,64 @@ __global__ void __launch_bounds__(64) k_pose_final(int num_paths, const cf *__re
         if (v == 0) { sel->path21 = b; sel->inliers21 = cnt; }
         else { sel->path31 = b; sel->inliers31 = cnt; }
     }
+}
+
+__global__ void __launch_bounds__(64) k_pose_final(int num_paths, const cf *__restrict__ tracks,
+                                                   const int32_t *__restrict__ inl, int flags, hcPoseSelection *sel) {
+    if (threadIdx.x != 0) return;
+    decode_selection(num_paths, tracks, inl, (flags & HC_POSE_REFERENCE_QUIRKS) != 0, sel);
+}
+
+// Grouped (multi-triplet) scoring: k_pose_support with the scene of the
+// candidate's own triplet.  A wave reads its group id from its sample and the
+// group's descriptor with wave-uniform loads; the selection atomics go to the
+// group's own hcPoseSelection.  The pose and reprojection arithmetic is the
+// single-triplet kernel's (make_pose, count_inliers), so the counts and the
+// selected pose are the bits a single-triplet call over the group's samples gives.
+__global__ void __launch_bounds__(256) k_pose_support_grouped(int num_paths, const cf *__restrict__ tracks,
+                                                              const uint8_t *__restrict__ conv,
+                                                              const hcTripletGroup *__restrict__ groups,
+                                                              const int32_t *__restrict__ sample_group,
+                                                              int32_t *__restrict__ inl, hcPoseSelection *sels) {
+    const int lane = lane_id();
+    const int nw = gridDim.x * (blockDim.x / WAVE);
+    for (int b = blockIdx.x * (blockDim.x / WAVE) + threadIdx.x / WAVE; b < num_paths; b += nw) {
+        int c21 = -1, c31 = -1;
+        if (conv[b] != 0) {
+            const cf *x = tracks + (size_t)b * (NV + 1);
+            const cf xv = lane < NV ? x[lane] : cmk(0.0f, 0.0f);
+            const unsigned long long im = __ballot(lane >= 24 && lane < NV && (double)__builtin_fabsf(xv.y) < 1e-5);
+            const unsigned long long dp = __ballot(lane < 8 && xv.x >= 0.0f);
+            if ((im & 0x3F000000ull) == 0x3F000000ull && (dp & 0xFFull) == 0xFFull) {
+                const int t = __builtin_amdgcn_readfirstlane(sample_group[b / NTRK]);   // wave-uniform
+                const hcTripletGroup g = groups[t];
+                const float K0 = g.K[0], K2 = g.K[2], K4 = g.K[4], K5 = g.K[5];
+                Pose P;
+                make_pose(x, P);
+                count_inliers(P, g.num_edgels, g.locations, K0, K2, K4, K5, lane, c21, c31);
+                if (lane == 0) {
+                    hcPoseSelection *sel = sels + t;
+                    atomicAdd(&sel->num_candidates, 1);
+                    atomicMax(reinterpret_cast<unsigned long long *>(&sel->key21),
+                              (unsigned long long)sel_key(c21, b, false));
+                    atomicMax(reinterpret_cast<unsigned long long *>(&sel->key31),
+                              (unsigned long long)sel_key(c31, b, false));
+                }
+            }
+        }
+        if (lane == 0) {
+            inl[2 * (size_t)b] = c21;
+            inl[2 * (size_t)b + 1] = c31;
+        }
+    }
+}
+
+// one thread per triplet decodes its selection
+__global__ void __launch_bounds__(64) k_pose_final_grouped(int num_paths, const cf *__restrict__ tracks,
+                                                           const int32_t *__restrict__ inl, int num_groups,
+                                                           hcPoseSelection *sels) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < num_groups) decode_selection(num_paths, tracks, inl, false, sels + t);
 }
 
 }  // namespace
@@ -201,6 +266,35 @@ extern "C" hcStatus hc_trifocal_pose_support(int num_paths, const hcComplex *tra
     }
     hipLaunchKernelGGL(k_pose_final, dim3(1), dim3(64), 0, s, num_paths, (const cf *)tracks, (const int32_t *)inliers,
                        flags, selection);
+    if ((g_last_hip_error = hipGetLastError()) != hipSuccess) return HC_ERROR_LAUNCH;
+    return HC_SUCCESS;
+}
+
+extern "C" hcStatus hc_trifocal_pose_support_grouped(int num_paths, const hcComplex *tracks, const uint8_t *converge,
+                                                     int num_groups, const hcTripletGroup *groups,
+                                                     const int32_t *sample_group, int flags, int32_t *inliers,
+                                                     hcPoseSelection *selections, hcStream stream) {
+    using namespace hc;
+    // (the quirks flag's literal indexing has no per-group meaning: no flag is accepted)
+    if (num_paths < 0 || num_paths % NTRK != 0 || num_groups < 1 || !groups || !selections || flags != 0)
+        return HC_ERROR_INVALID_VALUE;
+    if (num_paths > 0 && (!tracks || !converge || !inliers || !sample_group)) return HC_ERROR_INVALID_VALUE;
+    hipStream_t s = (hipStream_t)stream;
+    (void)hipGetLastError();
+    if ((g_last_hip_error = hipMemsetAsync(selections, 0, sizeof(hcPoseSelection) * (size_t)num_groups, s)) != hipSuccess)
+        return HC_ERROR_LAUNCH;
+    if (num_paths > 0) {
+        int dev = 0, cus = 256;
+        if (hipGetDevice(&dev) != hipSuccess) return HC_ERROR_DEVICE;
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return HC_ERROR_DEVICE;
+        const long long waves = num_paths < cus * 32 ? num_paths : (long long)cus * 32;
+        const int blocks = (int)((waves + 3) / 4);
+        hipLaunchKernelGGL(k_pose_support_grouped, dim3(blocks), dim3(256), 0, s, num_paths, (const cf *)tracks, converge,
+                           groups, sample_group, inliers, selections);
+        if ((g_last_hip_error = hipGetLastError()) != hipSuccess) return HC_ERROR_LAUNCH;
+    }
+    hipLaunchKernelGGL(k_pose_final_grouped, dim3((num_groups + 63) / 64), dim3(64), 0, s, num_paths, (const cf *)tracks,
+                       (const int32_t *)inliers, num_groups, selections);
     if ((g_last_hip_error = hipGetLastError()) != hipSuccess) return HC_ERROR_LAUNCH;
     return HC_SUCCESS;
 }

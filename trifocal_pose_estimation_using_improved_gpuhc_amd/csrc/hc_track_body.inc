@@ -1,5 +1,5 @@
-// The body of the tracker kernels k_track and k_track_small (hc_kernels.hip),
-// included inside each: ABORT, GTAB, ARCH, LUS, LUCH and LULAT are their
+// The body of the tracker kernels k_track, k_track_small and k_track_grouped (hc_kernels.hip),
+// included inside each: ABORT, GROUPED, GTAB, ARCH, LUS, LUCH and LULAT are their
 // template parameters or constants, `a` their argument block.
 // kernel_GPUHC_trifocal_pose_PH_CodeOpt_TrunPaths (..._TrunPaths.cu:45-290) and,
 // with ABORT, ..._TrunPaths_TrunRANSAC (..._TrunRANSAC.cu:45-327).
@@ -88,7 +88,24 @@
                     if (rl) S.x[r] = x;
                     wave_lds_sync();
                     const unsigned long long im = __ballot(r >= 18 && rl && (double)__builtin_fabsf(x.y) < 1e-5);
-                    if (((unsigned)(im >> hb) & 0x3FFC0000u) == 0x3FFC0000u) {   // eval.cuh:46-53
+                    if constexpr (GROUPED) {
+                        if (((unsigned)(im >> hb) & 0x3FFC0000u) == 0x3FFC0000u) {
+                            // the path's own triplet: its scoring set, its K, its flag
+                            const int grp = a.sample_group[smp_loaded];
+                            const hcTripletGroup g = a.groups[grp];
+                            const int2 c = score_half(S.x, g.locations, g.num_edgels, g.K, r);
+                            in21 = c.x;
+                            in31 = c.y;
+                            const float r21 = (float)in21 / (float)g.num_edgels, r31 = (float)in31 / (float)g.num_edgels;
+                            if ((double)r21 >= 0.90 && (double)r31 >= 0.90 && r == 0) {
+                                __hip_atomic_store(&a.group_found[grp], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                                a.batch_index[b] = b;
+                                if (a.group_ticks)
+                                    atomicCAS(&a.group_ticks[grp], 0ull,
+                                              (unsigned long long)__builtin_amdgcn_s_memrealtime());
+                            }
+                        }
+                    } else if (((unsigned)(im >> hb) & 0x3FFC0000u) == 0x3FFC0000u) {   // eval.cuh:46-53
                         const int2 c = score_half(S.x, a.edgels, a.num_edgels, a.K, r);
                         in21 = c.x;
                         in31 = c.y;
@@ -163,7 +180,18 @@
                     b = path_of_queue_pos(nb, a.num_paths, a.ordered);
                     qpos = nb;
                     bool skip = false;
-                    if (ABORT) {                                              // TrunRANSAC.cu:152
+                    if constexpr (GROUPED) {
+                        // the flag of the path's own triplet (set by this launch, or by
+                        // the caller: the carry-over of an earlier launch's find)
+                        skip = __hip_atomic_load(&a.group_found[a.sample_group[b / NTRK]], __ATOMIC_RELAXED,
+                                                 __HIP_MEMORY_SCOPE_AGENT) != 0u;
+                        skip = bcast_half0((int)skip) != 0;
+                        if (skip && r == 0) {
+                            a.conv[b] = 0;
+                            a.inf[b] = 0;
+                            if (a.stats) a.stats[b] = hcPathStats{0, 0, 0, 0};
+                        }
+                    } else if (ABORT) {                                       // TrunRANSAC.cu:152
                         skip = __hip_atomic_load(&ws->found, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u;
                         if (!skip && a.peer_found &&
                             __hip_atomic_load(a.peer_found, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0u) {
@@ -346,7 +374,13 @@
         }
         HC_DIAG_MARK(0);
         // the found flag for the next step boundary: read now, used after the stage
-        if (ABORT && a.inflight_stop) {
+        if constexpr (GROUPED) {
+            // (the group id re-derived from the slot's sample: not held across the stage)
+            if (a.inflight_stop)
+                found_seen = ph == PH_STAGE ? __hip_atomic_load(&a.group_found[a.sample_group[smp_loaded]],
+                                                                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+                                            : 0u;
+        } else if (ABORT && a.inflight_stop) {
             found_seen = __hip_atomic_load(&ws->found, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             // (the peer flag's xGMI round trip is hidden by the stage that follows)
             if (a.peer_found) found_seen |= __hip_atomic_load(a.peer_found, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);

@@ -68,6 +68,46 @@ def pose_support(tracks: torch.Tensor, converge: torch.Tensor, data_edgels: torc
     return inl.cpu().numpy(), selection_dict(selection_struct(sel))
 
 
+def launch_pose_support_grouped(tracks: torch.Tensor, converge: torch.Tensor, batch, inliers: torch.Tensor,
+                                selections: torch.Tensor, stream=None) -> None:
+    """Enqueue the pose support of several triplets' samples in one call (no
+    sync): hc_trifocal_pose_support_grouped.  batch is a
+    multi.DeviceTripletBatch; tracks / converge cover its samples in its order;
+    selections (T * SEL_BYTES,) u8 receives one hcPoseSelection per triplet."""
+    n = converge.numel()
+    T = batch.num_groups
+    if tracks.shape[0] != n or n != batch.num_samples * _abi.NUM_TRACKS or inliers.numel() < 2 * n or \
+            selections.numel() < T * SEL_BYTES:
+        raise _abi.HCError("pose_support_grouped: buffer sizes do not match")
+    for t in (tracks, converge, inliers, selections):
+        if not t.is_cuda or not t.is_contiguous() or t.device != batch.target.device:
+            raise _abi.HCError("pose_support_grouped: buffers must be contiguous tensors on the batch's device")
+    batch.check()   # group ids and edgel counts: the kernels do not validate them
+    L = _abi.lib()
+    _abi.check(L.hc_trifocal_pose_support_grouped(n, C.c_void_p(tracks.data_ptr()), C.c_void_p(converge.data_ptr()),
+                                                  T, C.c_void_p(batch.groups.data_ptr()),
+                                                  C.c_void_p(batch.sample_group.data_ptr()), 0,
+                                                  C.c_void_p(inliers.data_ptr()), C.c_void_p(selections.data_ptr()),
+                                                  _stream_handle(stream, tracks.device)),
+               "hc_trifocal_pose_support_grouped")
+
+
+def pose_support_grouped(tracks: torch.Tensor, converge: torch.Tensor, batch):
+    """Synchronous wrapper: returns (inliers (n, 2) numpy, [selection dict] * T).
+    Paths in the selections are the call's batch ids."""
+    if not hasattr(batch, "groups"):
+        batch = batch.to(tracks.device)
+    dev = tracks.device
+    n = converge.numel()
+    inl = torch.empty((n, 2), dtype=torch.int32, device=dev)
+    sel = torch.empty(batch.num_groups * SEL_BYTES, dtype=torch.uint8, device=dev)
+    launch_pose_support_grouped(tracks, converge, batch, inl, sel)
+    torch.cuda.synchronize(dev)
+    raw = sel.cpu().numpy()
+    return inl.cpu().numpy(), [selection_dict(selection_struct(raw[t * SEL_BYTES:(t + 1) * SEL_BYTES]))
+                               for t in range(batch.num_groups)]
+
+
 def merge(parts: list, path_offsets: list, quirks: bool = False) -> dict:
     """hc_pose_merge: per-GPU selections (raw bytes or structs) with their first
     batch ids -> one selection with global batch ids."""

@@ -36,13 +36,20 @@ class TrackResult:
     stats: torch.Tensor | None    # (312N, 4) int32 [steps, corrections, inliers21, inliers31]
     found: torch.Tensor | None = None         # abort mode: (1,) uint8
     batch_index: torch.Tensor | None = None   # abort mode: (312N,) int32
+    # grouped abort mode: found is the (T,) int32 per-triplet flag, found_ticks the (T,) int64
+    # device clock of each triplet's first find (0: none)
+    found_ticks: torch.Tensor | None = None
 
     def host(self):
         out = dict(tracks=self.tracks.cpu().numpy(), converge=self.converge.cpu().numpy(),
                    infinity=self.infinity.cpu().numpy())
         if self.stats is not None:
             out["stats"] = self.stats.cpu().numpy().view(PATH_STATS_DTYPE).reshape(-1)
-        if self.found is not None:
+        if self.found_ticks is not None:
+            out["found"] = self.found.cpu().numpy()
+            out["found_ticks"] = self.found_ticks.cpu().numpy()
+            out["batch_index"] = self.batch_index.cpu().numpy()
+        elif self.found is not None:
             out["found"] = bool(self.found.cpu().item())
             out["batch_index"] = self.batch_index.cpu().numpy()
         return out
@@ -98,6 +105,81 @@ class DeviceTracker:
         if r.found is not None:
             r.found.zero_()
             r.batch_index.fill_(-1)
+        if r.found_ticks is not None:
+            r.found_ticks.zero_()
+
+    def allocate_grouped(self, batch, stats: bool = True) -> TrackResult:
+        """Buffers of a grouped launch over batch (a multi.DeviceTripletBatch):
+        as allocate(abort=True), with one found word and one tick per triplet."""
+        r = self.allocate(batch.num_samples, stats=stats, abort=True)
+        r.found = torch.zeros(batch.num_groups, dtype=torch.int32, device=self.device)
+        r.found_ticks = torch.zeros(batch.num_groups, dtype=torch.int64, device=self.device)
+        return r
+
+    def launch_grouped(self, batch, r: TrackResult, stream: torch.cuda.Stream | None = None,
+                       workspace: torch.Tensor | None = None, inflight_stop: bool = False) -> None:
+        """Enqueue one grouped (multi-triplet) abort-mode run on `stream` (no
+        synchronisation): hc_trifocal_2op1p_30x30_track_abort_grouped over all of
+        batch's samples (a multi.DeviceTripletBatch) into r (allocate_grouped).
+        A path is skipped once the flag of its own triplet is set -- also when
+        the caller set it: r.found is in/out, the carry-over between launches --
+        and scored on its own triplet's edgels; r.found_ticks[t] receives the
+        device clock of triplet t's first find (read_timestamps gives the
+        launch's start).  inflight_stop as in launch()."""
+        if batch.target.device != self.start_sols.device:
+            raise _abi.HCError("the batch lives on another device")
+        batch.check()   # group ids and edgel counts: the kernels do not validate them
+        n, T = batch.num_samples, batch.num_groups
+        if n * 312 > r.tracks.shape[0] or r.found is None or r.found_ticks is None or r.found.numel() < T or \
+                r.found_ticks.numel() < T or r.found.dtype != torch.int32 or r.found_ticks.dtype != torch.int64:
+            raise _abi.HCError("result buffers do not fit the batch (allocate_grouped)")
+        ws_t = workspace if workspace is not None else self.workspace
+        if ws_t.numel() < self.ws_bytes:
+            raise _abi.HCError("workspace too small")
+        a = _abi.hcTrackArgs()
+        a.sub_ransac_iters = n
+        a.settings = self.settings
+        a.start_sols = self.start_sols.data_ptr()
+        a.start_sols_array = None
+        a.tracks = r.tracks.data_ptr()
+        a.track_array = None
+        a.start_params = self.start_params.data_ptr()
+        a.target_params = batch.target.data_ptr()
+        a.diff_params = batch.diff.data_ptr()
+        a.unified_index = self.unified.data_ptr()
+        a.converge = r.converge.data_ptr()
+        a.infinity = r.infinity.data_ptr()
+        a.stats = r.stats.data_ptr() if r.stats is not None else None
+        g = _abi.hcGroupedAbortArgs()
+        g.num_groups = T
+        g.groups = batch.groups.data_ptr()
+        g.sample_group = batch.sample_group.data_ptr()
+        g.group_found = r.found.data_ptr()
+        g.trifocal_sols_batch_index = r.batch_index.data_ptr()
+        g.group_found_ticks = r.found_ticks.data_ptr()
+        g.inflight_stop = 1 if inflight_stop else 0
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        _abi.check(self.L.hc_trifocal_2op1p_30x30_track_abort_grouped(
+            C.byref(a), C.byref(g), C.c_void_p(ws_t.data_ptr()), self.ws_bytes, C.c_void_p(s.cuda_stream)),
+            "hc_trifocal_2op1p_30x30_track_abort_grouped")
+
+    def track_grouped(self, batch, inflight_stop: bool = False, stats: bool = True, found=None) -> TrackResult:
+        """Synchronous convenience wrapper of launch_grouped, as track(abort=True):
+        batch is a multi.TripletBatch or its device copy.  found (optional, T
+        values): the triplets' flags on entry (a set one skips its triplet)."""
+        if not hasattr(batch, "groups"):
+            batch = batch.to(self.device)
+        r = self.allocate_grouped(batch, stats=stats)
+        self.reset_tracks(r)
+        if found is not None:
+            f = np.ascontiguousarray(found, np.int32).reshape(-1)
+            if f.shape[0] != batch.num_groups:
+                raise _abi.HCError("one initial flag per triplet")
+            r.found.copy_(torch.from_numpy(f))
+        self.launch_grouped(batch, r, inflight_stop=inflight_stop)
+        torch.cuda.synchronize(self.device)
+        self.workspace_status()
+        return r
 
     def launch(self, target: torch.Tensor, diff: torch.Tensor, r: TrackResult, abort: bool = False,
                stream: torch.cuda.Stream | None = None, workspace: torch.Tensor | None = None,
