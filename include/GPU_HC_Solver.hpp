@@ -52,6 +52,10 @@ public:
     // maximal-support pose of the last run (Evaluations.cpp:298-543 on the device,
     // include/hc_pose.h) and its error against GT_Poses21/31 of the data index
     hcPoseSelection pose_selection{};
+    // with the setting Pose_Selection_Joint: the one hypothesis selected for both
+    // views (hc_trifocal_pose_support_joint); pose_selection then repeats its path,
+    // per-view counts and pose for both views
+    hcTrifocalSelection joint_selection{};
     float pose_residuals[4] = {-1.0f, -1.0f, -1.0f, -1.0f};   // rot21, rot31 (rad), transl21, transl31
     bool pose_success = false;
     struct PoseRecord {
@@ -106,6 +110,7 @@ private:
     uint32_t *d_peer_found = nullptr;   // on the first GPU's device, read and set by every GPU's launch
     const char *peer_flag_kind_ = nullptr;   // memory the flag got: "uncached", "fine-grained" or "coarse-grained (hipMalloc)"
     int Pose_Flags = 0;   // Pose_Selection_Reference_Quirks -> HC_POSE_REFERENCE_QUIRKS
+    bool Pose_Selection_Joint = false;   // not in the reference: hc_trifocal_pose_support_joint instead
     int Num_Of_GPUs = 1;
     int Num_Of_RANSAC_Iterations = 100;   // NUM_OF_RANSAC_ITERATIONS (definitions.hpp:12), runtime here
     int sub_RANSAC_iters[MAX_NUM_OF_GPUS] = {0};

@@ -96,6 +96,60 @@ hcStatus hc_trifocal_pose_support_grouped(int num_paths, const hcComplex *tracks
 void hc_pose_merge(int n, const hcPoseSelection *parts, const int32_t *path_offsets, int flags,
                    hcPoseSelection *out);
 
+/* ---- Joint selection: one hypothesis for both views ------------------------
+ * hc_trifocal_pose_support selects views 1-2 and 1-3 independently, so the two
+ * halves of its pose usually come from different hypotheses.  The calls below
+ * select ONE candidate: the one with the most edgels that are inliers (< 2 px)
+ * in view 1-2 AND in view 1-3; ties -> the last candidate in batch-id order,
+ * as above.  Candidate filter, pose conversion and reprojection test are the
+ * ones of hc_trifocal_pose_support: a path's per-view counts and the pose bits
+ * are identical. */
+typedef struct {
+    int32_t num_candidates;
+    int32_t path;                 /* batch id, -1: none */
+    int32_t inliers;              /* edgels within 2 px in both views */
+    int32_t inliers21, inliers31; /* the same path's per-view counts */
+    int32_t pad;
+    uint64_t key;                 /* inliers << 32 | b */
+    float R21[9], t21[3], R31[9], t31[3];   /* R row-major, unit t */
+    float scale31, pad2;          /* |Re x[21..23]| / |Re x[18..20]|: the length of t31 in units of t21 */
+} hcTrifocalSelection;            /* 136 bytes */
+
+/* hc_trifocal_pose_support with the joint rule.
+ *   inliers     3 x 312N int32 out: (joint, inliers21, inliers31) per path, -1
+ *               for non-candidates
+ *   selection   one hcTrifocalSelection out; without a candidate the "none"
+ *               selection: path -1, counts -1, zero pose, scale31 0
+ *   flags       must be 0 */
+hcStatus hc_trifocal_pose_support_joint(int num_paths, const hcComplex *tracks, const uint8_t *converge,
+                                        int num_edgels, const float *locations, const float *K, int flags,
+                                        int32_t *inliers, hcTrifocalSelection *selection, hcStream stream);
+
+/* The same over the samples of several image triplets (arguments and batch-id
+ * conventions of hc_trifocal_pose_support_grouped): selections[t] is what the
+ * call above gives over triplet t's own samples, with the call's batch ids. */
+hcStatus hc_trifocal_pose_support_joint_grouped(int num_paths, const hcComplex *tracks, const uint8_t *converge,
+                                                int num_groups, const hcTripletGroup *groups,
+                                                const int32_t *sample_group, int flags, int32_t *inliers,
+                                                hcTrifocalSelection *selections /* T */, hcStream stream);
+
+/* Inlier mask of a selection: bit e % 64 of mask[e / 64] is set when edgel e is
+ * within 2 px in both views under the selection's own R and t (so the number
+ * of set bits is selection->inliers when the scene is the one it was scored
+ * on).  selection is a DEVICE pointer (the output of the calls above, or an
+ * uploaded hc_pose_merge_joint result); mask is (num_edgels + 63) / 64 words;
+ * bits at or beyond num_edgels are 0, and so is every word when path < 0.
+ * One selection per call: a grouped caller loops over its triplets. */
+hcStatus hc_trifocal_pose_inlier_mask(const hcTrifocalSelection *selection, int num_edgels, const float *locations,
+                                      const float *K, uint64_t *mask, hcStream stream);
+
+/* Host: hc_pose_merge for joint selections: the keys are re-based by
+ * path_offsets[i] and the maximal key wins, as if one launch had covered all
+ * paths; parts without candidates are ignored; n = 0 (or no candidate at all)
+ * gives the "none" selection.  parts are host copies. */
+void hc_pose_merge_joint(int n, const hcTrifocalSelection *parts, const int32_t *path_offsets,
+                         hcTrifocalSelection *out);
+
 /* Host: relative pose error of a selected pose against ground-truth poses
  * (12 floats each: R row-major then t, GT_Poses21/31 files).
  * out[0..3] = rotation residual 21, 31 (rad), translation residual 21, 31;

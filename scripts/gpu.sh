@@ -18,6 +18,7 @@
 #   phases    per-phase cycles of the HC_DIAG_PHASES build (scripts/diag_phases.py)
 #   stress    time slicing under concurrent streams (scripts/slice_stress.py: 4 cold, 4 warm, 8 cold)
 #   multi     T sequential single-triplet runs against one grouped run (scripts/multi_triplet.py) -> TAG_multi.json
+#   joint     per-view against joint pose selection, config-5 protocol (scripts/joint_pose.py [TRIALS [REPS]]) -> TAG_joint.json
 #   validate  tests,luwork,bench,profile,datasets
 # Extra environment: BENCH_ARGS (bench step), AB_ROUNDS (ab step, default 3), AB_ARGS (more ab_track.py options), TTFP_ARGS (ttfp_ab step,
 # e.g. "--dataset 10").
@@ -95,6 +96,7 @@ for l in open('$O/${T}_ttfp.jsonl'):
 for k,v in sorted(g.items()): print(k, v)" ;;
     phases) HC_TRIFOCAL_LIB=$L/libhc_trifocal_phases.so run phases 300 python scripts/diag_phases.py > $O/${T}_phases.json; rc=$?; cat $O/${T}_phases.json ;;
     multi) run multi 300 python scripts/multi_triplet.py "$@" > $O/${T}_multi.json; rc=$?; cat $O/${T}_multi.json ;;
+    joint) run joint 600 python scripts/joint_pose.py "$@" > $O/${T}_joint.json; rc=$?; cat $O/${T}_joint.json ;;
     stress)
       run stress4 300 python scripts/slice_stress.py $O/${T}_stress4.jsonl 4 4 > /dev/null 2>&1; rc=$?
       [ $rc -eq 0 ] && { run stress4w 300 python scripts/slice_stress.py $O/${T}_stress4w.jsonl 4 4 --warm-streams > /dev/null 2>&1; rc=$?; }

@@ -58,6 +58,18 @@ class hcPoseSelection(C.Structure):
 
 
 POSE_SELECTION_BYTES = C.sizeof(hcPoseSelection)
+
+
+class hcTrifocalSelection(C.Structure):
+    """include/hc_pose.h: one hypothesis for both views (joint selection)"""
+    _fields_ = [("num_candidates", C.c_int32), ("path", C.c_int32), ("inliers", C.c_int32),
+                ("inliers21", C.c_int32), ("inliers31", C.c_int32), ("pad", C.c_int32),
+                ("key", C.c_uint64),
+                ("R21", C.c_float * 9), ("t21", C.c_float * 3), ("R31", C.c_float * 9), ("t31", C.c_float * 3),
+                ("scale31", C.c_float), ("pad2", C.c_float)]
+
+
+TRIFOCAL_SELECTION_BYTES = C.sizeof(hcTrifocalSelection)   # 136
 HC_POSE_REFERENCE_QUIRKS = 1
 
 
@@ -171,6 +183,16 @@ def lib() -> C.CDLL:
                                                            C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.hc_pose_merge.restype = None
         L.hc_pose_merge.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(hcPoseSelection)]
+        L.hc_trifocal_pose_support_joint.restype = C.c_int
+        L.hc_trifocal_pose_support_joint.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                                     C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.hc_trifocal_pose_support_joint_grouped.restype = C.c_int
+        L.hc_trifocal_pose_support_joint_grouped.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                                             C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.hc_trifocal_pose_inlier_mask.restype = C.c_int
+        L.hc_trifocal_pose_inlier_mask.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.hc_pose_merge_joint.restype = None
+        L.hc_pose_merge_joint.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.POINTER(hcTrifocalSelection)]
         L.hc_pose_residuals.restype = C.c_int
         L.hc_pose_residuals.argtypes = [C.c_void_p] * 6 + [C.c_void_p]
         L.hc_add_pixel_noise.restype = None
@@ -221,6 +243,8 @@ DECLARED_SYMBOLS = (
     "hc_trifocal_2op1p_30x30_track_abort_grouped", "hc_trifocal_pose_support_grouped",
     "hc_trifocal_pose_support", "hc_pose_merge", "hc_pose_residuals", "hc_write_converged_sols",
     "hc_add_pixel_noise", "hc_write_triplet_edgels",
+    "hc_trifocal_pose_support_joint", "hc_trifocal_pose_support_joint_grouped", "hc_trifocal_pose_inlier_mask",
+    "hc_pose_merge_joint",
 )
 
 

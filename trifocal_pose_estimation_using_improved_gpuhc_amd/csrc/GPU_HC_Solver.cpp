@@ -95,6 +95,7 @@ struct GPU_HC_Solver::PerGPU {
     int32_t *d_inliers = nullptr;
     hcPoseSelection *d_sel = nullptr;
     hcPoseSelection h_sel{};
+    hcTrifocalSelection h_jsel{};   // Pose_Selection_Joint: d_sel holds this struct instead
     int edgel_capacity = 0;
     std::vector<hcComplex> h_track;
     std::vector<uint8_t> h_conv, h_inf;
@@ -120,6 +121,9 @@ GPU_HC_Solver::GPU_HC_Solver(const HC_Settings &S, const std::string &root_dir) 
     Num_Of_GPUs = S.i("Num_Of_GPUs", 1);
     Num_Of_RANSAC_Iterations = S.i("Num_Of_RANSAC_Iterations", 100);
     Pose_Flags = S.b("Pose_Selection_Reference_Quirks", false) ? HC_POSE_REFERENCE_QUIRKS : 0;
+    Pose_Selection_Joint = S.b("Pose_Selection_Joint", false);
+    if (Pose_Selection_Joint && Pose_Flags != 0)
+        throw std::runtime_error("Pose_Selection_Joint and Pose_Selection_Reference_Quirks exclude each other");
     if (HC_problem != "trifocal_2op1p_30x30" || Num_Of_Vars != NV || Num_Of_Params != NPP - 1 || Num_Of_Tracks != NT)
         throw std::runtime_error("this build implements trifocal_2op1p_30x30 (30 vars, 33 params, 312 tracks) only");
     int device_count = 0;
@@ -180,8 +184,8 @@ void GPU_HC_Solver::Allocate_Arrays() {
         HC_HIP_CHECK(hipMalloc(&p->d_inf, std::max<size_t>(1, n)));
         HC_HIP_CHECK(hipMalloc(&p->d_stats, std::max<size_t>(1, n) * sizeof(hcPathStats)));
         HC_HIP_CHECK(hipMalloc(&p->d_ws, wsb));
-        HC_HIP_CHECK(hipMalloc(&p->d_inliers, std::max<size_t>(1, n) * 2 * sizeof(int32_t)));
-        HC_HIP_CHECK(hipMalloc(&p->d_sel, sizeof(hcPoseSelection)));
+        HC_HIP_CHECK(hipMalloc(&p->d_inliers, std::max<size_t>(1, n) * (Pose_Selection_Joint ? 3 : 2) * sizeof(int32_t)));
+        HC_HIP_CHECK(hipMalloc(&p->d_sel, std::max(sizeof(hcPoseSelection), sizeof(hcTrifocalSelection))));
         p->ws_bytes = wsb;
         p->h_track.resize(n * (NV + 1));
         p->h_conv.resize(n);
@@ -411,13 +415,21 @@ void GPU_HC_Solver::Solve_by_GPU_HC() {
     const double tp = now_s();
     for (PerGPU *p : gpus_) {
         HC_HIP_CHECK(hipSetDevice(p->dev));
-        const hcStatus st = hc_trifocal_pose_support(NT * p->N, p->d_Track, p->d_conv, Num_Of_Triplet_Edgels,
-                                                     p->d_edgels, p->d_K, Pose_Flags, p->d_inliers, p->d_sel,
-                                                     (hcStream)p->stream);
+        const hcStatus st =
+            Pose_Selection_Joint
+                ? hc_trifocal_pose_support_joint(NT * p->N, p->d_Track, p->d_conv, Num_Of_Triplet_Edgels, p->d_edgels,
+                                                 p->d_K, 0, p->d_inliers,
+                                                 reinterpret_cast<hcTrifocalSelection *>(p->d_sel), (hcStream)p->stream)
+                : hc_trifocal_pose_support(NT * p->N, p->d_Track, p->d_conv, Num_Of_Triplet_Edgels, p->d_edgels,
+                                           p->d_K, Pose_Flags, p->d_inliers, p->d_sel, (hcStream)p->stream);
         if (st != HC_SUCCESS)
             throw std::runtime_error(std::string("pose support launch failed: status ") + std::to_string((int)st) +
                                      " (" + hc_last_error_string() + ")");
-        HC_HIP_CHECK(hipMemcpyAsync(&p->h_sel, p->d_sel, sizeof(hcPoseSelection), hipMemcpyDeviceToHost, p->stream));
+        if (Pose_Selection_Joint)
+            HC_HIP_CHECK(hipMemcpyAsync(&p->h_jsel, p->d_sel, sizeof(hcTrifocalSelection), hipMemcpyDeviceToHost,
+                                        p->stream));
+        else
+            HC_HIP_CHECK(hipMemcpyAsync(&p->h_sel, p->d_sel, sizeof(hcPoseSelection), hipMemcpyDeviceToHost, p->stream));
     }
     for (PerGPU *p : gpus_) {
         HC_HIP_CHECK(hipSetDevice(p->dev));
@@ -482,14 +494,30 @@ void GPU_HC_Solver::Solve_by_GPU_HC() {
     Collect_Num_Of_Inf_Sols.push_back(counts[2]);
     {
         std::vector<hcPoseSelection> parts;
+        std::vector<hcTrifocalSelection> jparts;
         std::vector<int32_t> offs;
         int off = 0;
         for (PerGPU *p : gpus_) {
             parts.push_back(p->h_sel);
+            jparts.push_back(p->h_jsel);
             offs.push_back(off);
             off += NT * p->N;
         }
-        hc_pose_merge((int)parts.size(), parts.data(), offs.data(), Pose_Flags, &pose_selection);
+        if (Pose_Selection_Joint) {
+            // one hypothesis for both views: pose_selection carries it as both views' selection
+            hc_pose_merge_joint((int)jparts.size(), jparts.data(), offs.data(), &joint_selection);
+            const hcTrifocalSelection &j = joint_selection;
+            pose_selection = hcPoseSelection{};
+            pose_selection.num_candidates = j.num_candidates;
+            pose_selection.path21 = pose_selection.path31 = j.path;
+            pose_selection.inliers21 = j.inliers21;
+            pose_selection.inliers31 = j.inliers31;
+            pose_selection.key21 = pose_selection.key31 = j.key;
+            for (int k = 0; k < 9; k++) { pose_selection.R21[k] = j.R21[k]; pose_selection.R31[k] = j.R31[k]; }
+            for (int k = 0; k < 3; k++) { pose_selection.t21[k] = j.t21[k]; pose_selection.t31[k] = j.t31[k]; }
+        } else {
+            hc_pose_merge((int)parts.size(), parts.data(), offs.data(), Pose_Flags, &pose_selection);
+        }
         pose_success = false;
         for (float &v : pose_residuals) v = -1.0f;
         if (pose_selection.num_candidates > 0) {                                // :490-503
@@ -501,6 +529,9 @@ void GPU_HC_Solver::Solve_by_GPU_HC() {
                pose_time * 1e3);
         printf(" - views 1-2: path %d, %d inliers; views 1-3: path %d, %d inliers\n", pose_selection.path21,
                pose_selection.inliers21, pose_selection.path31, pose_selection.inliers31);
+        if (Pose_Selection_Joint)
+            printf(" - joint selection: path %d, %d edgels within 2 px in both views, |t31| / |t21| = %g\n",
+                   joint_selection.path, joint_selection.inliers, joint_selection.scale31);
         std::cout << (pose_success ? "## Found solution matched with GT: " : "## Not found a solution matched with GT: ")
                   << std::endl;                                                 // :552-565
         printf(" - Residual of R21: %g (rad)\n - Residual of R31: %g (rad)\n", pose_residuals[0], pose_residuals[1]);

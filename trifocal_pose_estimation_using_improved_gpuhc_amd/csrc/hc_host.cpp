@@ -244,6 +244,29 @@ void hc_pose_merge(int n, const hcPoseSelection *parts, const int32_t *off, int 
     *out = r;
 }
 
+void hc_pose_merge_joint(int n, const hcTrifocalSelection *parts, const int32_t *off, hcTrifocalSelection *out) {
+    // one joint launch over all paths would have max-reduced the same keys (hc_pose.hip)
+    hcTrifocalSelection r{};
+    r.path = r.inliers = r.inliers21 = r.inliers31 = -1;
+    bool have = false;
+    for (int i = 0; i < n; i++) {
+        const hcTrifocalSelection &p = parts[i];
+        if (p.num_candidates <= 0) continue;
+        r.num_candidates += p.num_candidates;
+        const uint64_t g = ((p.key >> 32) << 32) | (uint64_t)((uint32_t)p.key + (uint32_t)off[i]);
+        if (have && g <= r.key) continue;
+        have = true;
+        const int32_t total = r.num_candidates;
+        r = p;
+        r.num_candidates = total;
+        r.key = g;
+        r.path = p.path + off[i];
+        r.pad = 0;
+        r.pad2 = 0.0f;
+    }
+    *out = r;
+}
+
 namespace {
 // Evaluations.cpp:360-374: acos(0.5 * (trace(R_gt' R) - 1.0)), float matrix product / trace
 float rotation_residual(const float *gt, const float *R) {

@@ -34,6 +34,7 @@ static void usage() {
            "                    default: one flag per GPU as in the reference)\n"
            "      --write-sols  write Output_Write_Files/GPU_Converged_HC_tracks.txt\n"
            "      --quirks      reference-literal pose selection (Pose_Selection_Reference_Quirks)\n"
+           "      --joint       one hypothesis for both views, by joint two-view support (Pose_Selection_Joint)\n"
            "  -s, --dataset     RANSAC dataset directory name (default Synthetic)\n");
 }
 
@@ -41,7 +42,7 @@ int main(int argc, char **argv) {
     std::string problem, root = "../../";
     int samples = -1, gpus = -1, times = 1;
     bool abort_flag = false, write_sols = false, quirks = false, inflight_stop = false, share = false,
-         across = false;
+         across = false, joint = false;
     std::string dataset;
     if (argc <= 1) { usage(); return 0; }
     for (int i = 1; i < argc; i++) {
@@ -62,6 +63,7 @@ int main(int argc, char **argv) {
         else if (a == "--share-devices") share = true;
         else if (a == "--write-sols") write_sols = true;
         else if (a == "--quirks") quirks = true;
+        else if (a == "--joint") joint = true;
         else if (a == "-s" || a == "--dataset") dataset = next("-s");
         else { printf("\033[1;31m[ERROR] Invalid input arguments!\033[0m\n"); usage(); return 0; }
     }
@@ -81,6 +83,7 @@ int main(int argc, char **argv) {
         if (share) s.set("Share_Devices", "true");
         if (write_sols) s.set("Write_Converged_Sols", "true");
         if (quirks) s.set("Pose_Selection_Reference_Quirks", "true");
+        if (joint) s.set("Pose_Selection_Joint", "true");
         if (!dataset.empty()) s.set("RANSAC_Dataset", dataset);
         if (!run_GPU_HC_Solver(s, root, times)) return 1;
     } catch (const std::exception &e) {

@@ -5,6 +5,12 @@ replaces the host loops of Evaluations::Transform_GPUHC_Sols_to_Trifocal_Relativ
 (magmaHC/Evaluations.cpp:298-358) and get_Solution_with_Maximal_Support
 (:382-504).  Host side: hc_pose_merge (per-GPU selections -> one) and
 hc_pose_residuals (Measure_Relative_Pose_Error, :523-543).
+
+Joint selection (not in the reference): hc_trifocal_pose_support_joint and its
+grouped form select one hypothesis for both views, by the number of edgels that
+are inliers in both; hc_trifocal_pose_inlier_mask lists those edgels and
+hc_pose_merge_joint merges per-launch selections (pose_support_joint,
+pose_support_joint_grouped, inlier_mask, merge_joint below).
 """
 from __future__ import annotations
 
@@ -120,6 +126,160 @@ def merge(parts: list, path_offsets: list, quirks: bool = False) -> dict:
     _abi.lib().hc_pose_merge(n, C.cast(arr, C.c_void_p), C.c_void_p(offs.ctypes.data),
                              _abi.HC_POSE_REFERENCE_QUIRKS if quirks else 0, C.byref(out))
     return selection_dict(out)
+
+
+# ----------------------------------------------------------------- joint selection
+# One hypothesis for both views, scored on the edgels that are inliers in view
+# 1-2 and in view 1-3 (hcTrifocalSelection, include/hc_pose.h).
+JOINT_SEL_BYTES = _abi.TRIFOCAL_SELECTION_BYTES
+
+
+def joint_selection_struct(raw) -> _abi.hcTrifocalSelection:
+    if isinstance(raw, _abi.hcTrifocalSelection):
+        return raw
+    b = raw.cpu().numpy() if isinstance(raw, torch.Tensor) else np.asarray(raw)
+    return _abi.hcTrifocalSelection.from_buffer_copy(np.ascontiguousarray(b, np.uint8).tobytes()[:JOINT_SEL_BYTES])
+
+
+def joint_selection_dict(s: _abi.hcTrifocalSelection) -> dict:
+    return dict(num_candidates=s.num_candidates, path=s.path, inliers=s.inliers, inliers21=s.inliers21,
+                inliers31=s.inliers31, key=s.key,
+                R21=np.array(s.R21[:], np.float32), t21=np.array(s.t21[:], np.float32),
+                R31=np.array(s.R31[:], np.float32), t31=np.array(s.t31[:], np.float32),
+                scale31=np.float32(s.scale31))
+
+
+def joint_selection_from_dict(d: dict) -> _abi.hcTrifocalSelection:
+    s = _abi.hcTrifocalSelection()
+    for k in ("num_candidates", "path", "inliers", "inliers21", "inliers31", "key"):
+        setattr(s, k, int(d[k]))
+    for k in ("R21", "t21", "R31", "t31"):
+        getattr(s, k)[:] = [float(v) for v in d[k]]
+    s.scale31 = float(d["scale31"])
+    return s
+
+
+def launch_pose_support_joint(tracks: torch.Tensor, converge: torch.Tensor, edgels: torch.Tensor, K: torch.Tensor,
+                              inliers: torch.Tensor, selection: torch.Tensor, stream=None) -> None:
+    """Enqueue candidate filter + pose + joint inlier scoring + selection (no
+    sync): hc_trifocal_pose_support_joint.  Buffers as in launch_pose_support,
+    but inliers is (n, 3) i32 (joint, 21, 31) and selection (JOINT_SEL_BYTES,) u8."""
+    n = converge.numel()
+    if tracks.shape[0] != n or inliers.numel() < 3 * n or selection.numel() < JOINT_SEL_BYTES:
+        raise _abi.HCError("pose_support_joint: buffer sizes do not match")
+    for t in (tracks, converge, edgels, K, inliers, selection):
+        if not t.is_cuda or not t.is_contiguous():
+            raise _abi.HCError("pose_support_joint: buffers must be contiguous device tensors")
+    L = _abi.lib()
+    _abi.check(L.hc_trifocal_pose_support_joint(n, C.c_void_p(tracks.data_ptr()), C.c_void_p(converge.data_ptr()),
+                                                int(edgels.shape[0]), C.c_void_p(edgels.data_ptr()),
+                                                C.c_void_p(K.data_ptr()), 0, C.c_void_p(inliers.data_ptr()),
+                                                C.c_void_p(selection.data_ptr()),
+                                                _stream_handle(stream, tracks.device)),
+               "hc_trifocal_pose_support_joint")
+
+
+def pose_support_joint(tracks: torch.Tensor, converge: torch.Tensor, data_edgels: torch.Tensor, K: torch.Tensor,
+                       return_device_selection: bool = False):
+    """Synchronous wrapper: returns (inliers (n, 3) numpy, selection dict), and
+    with return_device_selection also the selection's device bytes (the input of
+    inlier_mask)."""
+    dev = tracks.device
+    n = converge.numel()
+    inl = torch.empty((n, 3), dtype=torch.int32, device=dev)
+    sel = torch.empty(JOINT_SEL_BYTES, dtype=torch.uint8, device=dev)
+    launch_pose_support_joint(tracks, converge, data_edgels, K, inl, sel)
+    torch.cuda.synchronize(dev)
+    out = inl.cpu().numpy(), joint_selection_dict(joint_selection_struct(sel))
+    return out + (sel,) if return_device_selection else out
+
+
+def launch_pose_support_joint_grouped(tracks: torch.Tensor, converge: torch.Tensor, batch, inliers: torch.Tensor,
+                                      selections: torch.Tensor, stream=None) -> None:
+    """launch_pose_support_grouped with the joint rule
+    (hc_trifocal_pose_support_joint_grouped): inliers (n, 3) i32, selections
+    (T * JOINT_SEL_BYTES,) u8."""
+    n = converge.numel()
+    T = batch.num_groups
+    if tracks.shape[0] != n or n != batch.num_samples * _abi.NUM_TRACKS or inliers.numel() < 3 * n or \
+            selections.numel() < T * JOINT_SEL_BYTES:
+        raise _abi.HCError("pose_support_joint_grouped: buffer sizes do not match")
+    for t in (tracks, converge, inliers, selections):
+        if not t.is_cuda or not t.is_contiguous() or t.device != batch.target.device:
+            raise _abi.HCError("pose_support_joint_grouped: buffers must be contiguous tensors on the batch's device")
+    batch.check()   # group ids and edgel counts: the kernels do not validate them
+    L = _abi.lib()
+    _abi.check(L.hc_trifocal_pose_support_joint_grouped(n, C.c_void_p(tracks.data_ptr()),
+                                                        C.c_void_p(converge.data_ptr()), T,
+                                                        C.c_void_p(batch.groups.data_ptr()),
+                                                        C.c_void_p(batch.sample_group.data_ptr()), 0,
+                                                        C.c_void_p(inliers.data_ptr()),
+                                                        C.c_void_p(selections.data_ptr()),
+                                                        _stream_handle(stream, tracks.device)),
+               "hc_trifocal_pose_support_joint_grouped")
+
+
+def pose_support_joint_grouped(tracks: torch.Tensor, converge: torch.Tensor, batch):
+    """Synchronous wrapper: returns (inliers (n, 3) numpy, [selection dict] * T).
+    Paths in the selections are the call's batch ids."""
+    if not hasattr(batch, "groups"):
+        batch = batch.to(tracks.device)
+    dev = tracks.device
+    n = converge.numel()
+    inl = torch.empty((n, 3), dtype=torch.int32, device=dev)
+    sel = torch.empty(batch.num_groups * JOINT_SEL_BYTES, dtype=torch.uint8, device=dev)
+    launch_pose_support_joint_grouped(tracks, converge, batch, inl, sel)
+    torch.cuda.synchronize(dev)
+    raw = sel.cpu().numpy()
+    return inl.cpu().numpy(), [joint_selection_dict(joint_selection_struct(raw[t * JOINT_SEL_BYTES:
+                                                                               (t + 1) * JOINT_SEL_BYTES]))
+                               for t in range(batch.num_groups)]
+
+
+def inlier_mask(selection, edgels: torch.Tensor, K: torch.Tensor, packed: bool = False, stream=None) -> np.ndarray:
+    """hc_trifocal_pose_inlier_mask: which of the E edgels are within 2 px in
+    both views under the selection's pose.  selection: the device bytes of an
+    hcTrifocalSelection, or a struct / dict (e.g. a merge_joint result), which is
+    uploaded.  Returns a bool array of length E, or with packed the (E + 63) // 64
+    uint64 words."""
+    dev = edgels.device
+    if isinstance(selection, dict):
+        selection = joint_selection_from_dict(selection)
+    if isinstance(selection, _abi.hcTrifocalSelection):
+        selection = torch.from_numpy(np.frombuffer(bytes(selection), np.uint8).copy()).to(dev)
+    E = int(edgels.shape[0])
+    for t in (selection, edgels, K):
+        if not t.is_cuda or not t.is_contiguous() or t.device != dev:
+            raise _abi.HCError("inlier_mask: buffers must be contiguous tensors on one device")
+    if selection.numel() * selection.element_size() < JOINT_SEL_BYTES:
+        raise _abi.HCError("inlier_mask: selection is smaller than hcTrifocalSelection")
+    words = torch.empty((E + 63) // 64, dtype=torch.int64, device=dev)
+    _abi.check(_abi.lib().hc_trifocal_pose_inlier_mask(C.c_void_p(selection.data_ptr()), E,
+                                                       C.c_void_p(edgels.data_ptr()), C.c_void_p(K.data_ptr()),
+                                                       C.c_void_p(words.data_ptr()), _stream_handle(stream, dev)),
+               "hc_trifocal_pose_inlier_mask")
+    if stream is not None:
+        stream.synchronize()
+    else:
+        torch.cuda.synchronize(dev)
+    w = words.cpu().numpy().view(np.uint64)
+    if packed:
+        return w
+    return np.unpackbits(w.view(np.uint8), bitorder="little")[:E].astype(bool)
+
+
+def merge_joint(parts: list, path_offsets: list) -> dict:
+    """hc_pose_merge_joint: per-launch / per-GPU joint selections (raw bytes,
+    structs or dicts) with their first batch ids -> one selection with global
+    batch ids."""
+    n = len(parts)
+    arr = (_abi.hcTrifocalSelection * max(1, n))()
+    for i, p in enumerate(parts):
+        arr[i] = joint_selection_from_dict(p) if isinstance(p, dict) else joint_selection_struct(p)
+    offs = np.ascontiguousarray(path_offsets if n else [0], np.int32)
+    out = _abi.hcTrifocalSelection()
+    _abi.lib().hc_pose_merge_joint(n, C.cast(arr, C.c_void_p), C.c_void_p(offs.ctypes.data), C.byref(out))
+    return joint_selection_dict(out)
 
 
 def residuals(data: RansacData, sel: dict):
