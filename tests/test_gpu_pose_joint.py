@@ -4,7 +4,9 @@ solver's Pose_Selection_Joint setting through the CLI).
 
 Expected values come from the unmodified oracle (tests/joint_reference.py: one
 oracle call per edgel gives every candidate's per-view inlier masks), pose bits
-from hc_trifocal_pose_support with only the selected path converged.
+from hc_trifocal_pose_support with only the selected path converged.  The
+per-view call, which shares the joint call's edgel loop, is checked against the
+same masks at the same remainder sizes.
 
 Common inputs: the 36 candidate tracks of pose_N100_seed0.npz at scattered batch
 ids of a 624-path buffer whose other paths are not converged; the scene is the
@@ -139,6 +141,30 @@ def test_joint_single_triplet_and_mask(common, dev_inputs, E):
     assert sum(bin(int(v)).count("1") for v in words) == sel["inliers"]
     mask = pose.inlier_mask(sel_dev, d["edgels"][:E], d["K"])
     assert mask.dtype == bool and mask.shape == (E,) and np.array_equal(mask, ref["mask"])
+
+
+@pytest.mark.parametrize("E", SIZES)
+def test_per_view_counts_at_remainder_sizes(common, dev_inputs, E):
+    """hc_trifocal_pose_support runs the edgel loop it shares with the joint
+    call: its counts and per-view winners over the first E edgels against the
+    oracle's masks alone."""
+    from trifocal_pose_estimation_using_improved_gpuhc_amd import pose
+    d = dev_inputs
+    ids = common["ids"]
+    counts = np.stack([common["m21"][:, :E].sum(1), common["m31"][:, :E].sum(1)], axis=1).astype(np.int32)
+    inl, sel = pose.pose_support(d["tracks"], d["conv"], d["edgels"][:E], d["K"])
+    assert inl.shape == (NPATHS, 2)
+    assert np.array_equal(inl[ids], counts), np.nonzero((inl[ids] != counts).any(1))[0]
+    other = np.ones(NPATHS, bool)
+    other[ids] = False
+    assert (inl[other] == -1).all()
+    assert sel["num_candidates"] == len(ids) == 36
+    for v, view in enumerate(("21", "31")):
+        c = counts[:, v]
+        w = int(np.nonzero(c == c.max())[0][-1])    # ids ascend: the last candidate attaining the maximum
+        path = int(ids[w])
+        assert (sel["path" + view], sel["inliers" + view]) == (path, int(c[w])), view
+        assert sel["key" + view] == (int(c[w]) << 32) | path, view
 
 
 def test_joint_tie_selects_the_larger_batch_id(common, dev_inputs):

@@ -7,19 +7,27 @@
 // with the multiview helpers of magmaHC/util.hpp restated op for op (FP32,
 // no contraction: -ffp-contract=off; IEEE division and sqrt).
 //
-// Layout: one wavefront per batch id b (grid-stride).  Non-converged paths
-// cost one byte load.  A candidate's pose is computed redundantly by every
-// lane (uniform loads of x[18..29]), then the 64 lanes stride over the
-// triplet edgels (E x 24 B, L2-resident after the first candidate) and the two
-// inlier counts are wave-reduced.  Selection is a single 64-bit atomicMax per
-// view on key = count << 32 | b (largest count, ties -> largest b = the last
-// candidate attaining the maximum, the rule of Evaluations.cpp:460,466); a
-// one-wave epilogue decodes the keys and writes the selected poses.
-// The grouped kernels do the same for the samples of several triplets at
-// once, each candidate on its own triplet's scene, one selection per triplet.
-// The joint kernels select ONE candidate for both views by the number of
-// edgels that are inliers in both (hcTrifocalSelection), and k_pose_inlier_mask
-// lists those edgels as a bit mask.
+// One support kernel, k_pose_support<JOINT, GROUPED>, serves the four entry
+// points.  Layout: one wavefront per batch id b (grid-stride).  Non-converged
+// paths cost one byte load.  A candidate's pose is computed redundantly by
+// every lane (uniform loads of x[18..29]), then the 64 lanes stride over the
+// triplet edgels (E x 24 B, L2-resident after the first candidate), evaluate
+// both views of an edgel (edgel_views) and the inlier counts are wave-reduced.
+// Selection is a 64-bit atomicMax on key = count << 32 | b (largest count,
+// ties -> largest b = the last candidate attaining the maximum, the rule of
+// Evaluations.cpp:460,466); k_pose_final decodes the keys, one thread per
+// selection, and writes the selected poses.
+//   GROUPED: the samples of several triplets at once; a candidate is scored on
+//            its own triplet's scene and published to its triplet's selection.
+//   JOINT:   ONE candidate for both views, by the number of edgels that are
+//            inliers in both (hcTrifocalSelection, one key); otherwise one key
+//            per view (hcPoseSelection).
+// The switches choose the scene, a third count and the key; the converged test,
+// the candidate filter, make_pose and the edgel loop exist once, so a path's
+// counts and pose bits are the same in every form.  k_pose_inlier_mask lists a
+// joint selection's inlier edgels as a bit mask, through the same edgel_views.
+#include <type_traits>
+
 #include "../../include/hc_pose.h"
 #include "hc_device.hpp"
 
@@ -98,20 +106,25 @@ __device__ __forceinline__ bool reproj_inlier(float g0, float g1, float h0, floa
     return err < 2.0f;   // REPROJ_ERROR_INLIER_THRESH (definitions.hpp:17)
 }
 
-// Inlier counts of one candidate pose over a triplet's edgels: the 64 lanes
-// stride over the edgels, the counts are wave-reduced (every lane gets them).
-__device__ __forceinline__ void count_inliers(const Pose &P, int E, const float *__restrict__ loc, float K0, float K2,
-                                              float K4, float K5, int lane, int &c21, int &c31) {
-    int a21 = 0, a31 = 0;
-    for (int e = lane; e < E; e += WAVE) {
-        const float2 g01 = *reinterpret_cast<const float2 *>(loc + (size_t)e * 6);
-        const float2 g23 = *reinterpret_cast<const float2 *>(loc + (size_t)e * 6 + 2);
-        const float2 g45 = *reinterpret_cast<const float2 *>(loc + (size_t)e * 6 + 4);
-        a21 += reproj_inlier(g01.x, g01.y, g23.x, g23.y, P.R, P.t, K0, K2, K4, K5) ? 1 : 0;
-        a31 += reproj_inlier(g01.x, g01.y, g45.x, g45.y, P.R + 9, P.t + 3, K0, K2, K4, K5) ? 1 : 0;
-    }
-    c21 = wave_sum_i(a21);
-    c31 = wave_sum_i(a31);
+// One triplet's scoring set: E edgels of 6 floats and the four intrinsics used.
+struct Scene {
+    int E;
+    const float *loc;
+    float K0, K2, K4, K5;
+};
+
+__device__ __forceinline__ Scene load_scene(int E, const float *__restrict__ loc, const float *__restrict__ K) {
+    return Scene{E, loc, K[0], K[2], K[4], K[5]};
+}
+
+// Edgel e of a scene under one pose: inlier in view 1-2, inlier in view 1-3.
+__device__ __forceinline__ void edgel_views(const Scene &sc, int e, const float *R21, const float *t21,
+                                            const float *R31, const float *t31, bool &in21, bool &in31) {
+    const float2 g01 = *reinterpret_cast<const float2 *>(sc.loc + (size_t)e * 6);
+    const float2 g23 = *reinterpret_cast<const float2 *>(sc.loc + (size_t)e * 6 + 2);
+    const float2 g45 = *reinterpret_cast<const float2 *>(sc.loc + (size_t)e * 6 + 4);
+    in21 = reproj_inlier(g01.x, g01.y, g23.x, g23.y, R21, t21, sc.K0, sc.K2, sc.K4, sc.K5);
+    in31 = reproj_inlier(g01.x, g01.y, g45.x, g45.y, R31, t31, sc.K0, sc.K2, sc.K4, sc.K5);
 }
 
 __device__ __forceinline__ bool is_converged(const uint8_t *conv, int b, int num_paths, bool quirks) {
@@ -120,42 +133,94 @@ __device__ __forceinline__ bool is_converged(const uint8_t *conv, int b, int num
     return ci < num_paths && conv[ci] != 0;
 }
 
+// x[0..30] of a converged path: Evaluations.cpp:322-331, |Im x[24..29]| <
+// IMAG_PART_TOL and Re x[0..7] >= 0 (wave-uniform result)
+__device__ __forceinline__ bool is_candidate(const cf *__restrict__ x, int lane) {
+    const cf xv = lane < NV ? x[lane] : cmk(0.0f, 0.0f);
+    const unsigned long long im = __ballot(lane >= 24 && lane < NV && (double)__builtin_fabsf(xv.y) < 1e-5);
+    const unsigned long long dp = __ballot(lane < 8 && xv.x >= 0.0f);
+    return (im & 0x3F000000ull) == 0x3F000000ull && (dp & 0xFFull) == 0xFFull;
+}
+
 __device__ __forceinline__ uint64_t sel_key(int count, int b, bool quirks) {
     return quirks ? (uint64_t)(0xFFFFFFFFu - (uint32_t)b) : (((uint64_t)(uint32_t)count << 32) | (uint32_t)b);
 }
 
-__global__ void __launch_bounds__(256) k_pose_support(int num_paths, const cf *__restrict__ tracks,
-                                                      const uint8_t *__restrict__ conv, int E,
-                                                      const float *__restrict__ loc, const float *__restrict__ K,
-                                                      int flags, int32_t *__restrict__ inl, hcPoseSelection *sel) {
+__device__ __forceinline__ void key_max(uint64_t *key, uint64_t v) {
+    atomicMax(reinterpret_cast<unsigned long long *>(key), (unsigned long long)v);
+}
+
+template <bool JOINT>
+using Selection = std::conditional_t<JOINT, hcTrifocalSelection, hcPoseSelection>;
+
+// Arguments of a pose-support call, by value to both kernels.
+template <bool JOINT>
+struct PoseArgs {
+    int num_paths;
+    const cf *tracks;
+    const uint8_t *conv;
+    // the scene: (E, loc, K), or with GROUPED that of groups[sample_group[b / NTRK]]
+    int E;
+    const float *loc;
+    const float *K;
+    const hcTripletGroup *groups;
+    const int32_t *sample_group;
+    int flags;             // HC_POSE_REFERENCE_QUIRKS: <false, false> only
+    int32_t *inl;          // per path (c21, c31), or with JOINT (joint, c21, c31); -1 for non-candidates
+    Selection<JOINT> *sels;
+    int num_sel;           // 1, or with GROUPED the number of triplets
+};
+
+template <bool JOINT, bool GROUPED>
+__global__ void __launch_bounds__(256) k_pose_support(const PoseArgs<JOINT> a) {
     const int lane = lane_id();
     const int nw = gridDim.x * (blockDim.x / WAVE);
-    const bool quirks = (flags & HC_POSE_REFERENCE_QUIRKS) != 0;
-    const float K0 = K[0], K2 = K[2], K4 = K[4], K5 = K[5];
-    for (int b = blockIdx.x * (blockDim.x / WAVE) + threadIdx.x / WAVE; b < num_paths; b += nw) {
-        int c21 = -1, c31 = -1;
-        if (is_converged(conv, b, num_paths, quirks)) {
-            const cf *x = tracks + (size_t)b * (NV + 1);
-            const cf xv = lane < NV ? x[lane] : cmk(0.0f, 0.0f);
-            // Evaluations.cpp:322-331: |Im x[24..29]| < IMAG_PART_TOL, Re x[0..7] >= 0
-            const unsigned long long im = __ballot(lane >= 24 && lane < NV && (double)__builtin_fabsf(xv.y) < 1e-5);
-            const unsigned long long dp = __ballot(lane < 8 && xv.x >= 0.0f);
-            if ((im & 0x3F000000ull) == 0x3F000000ull && (dp & 0xFFull) == 0xFFull) {
-                Pose P;
-                make_pose(quirks ? tracks : x, P);   // quirk: converted from the base pointer (:334-341)
-                count_inliers(P, E, loc, K0, K2, K4, K5, lane, c21, c31);
-                if (lane == 0) {
-                    atomicAdd(&sel->num_candidates, 1);
-                    atomicMax(reinterpret_cast<unsigned long long *>(&sel->key21),
-                              (unsigned long long)sel_key(c21, b, quirks));
-                    atomicMax(reinterpret_cast<unsigned long long *>(&sel->key31),
-                              (unsigned long long)sel_key(c31, b, quirks));
+    const bool quirks = !JOINT && !GROUPED && (a.flags & HC_POSE_REFERENCE_QUIRKS) != 0;
+    Scene sc{};
+    if constexpr (!GROUPED) sc = load_scene(a.E, a.loc, a.K);
+    for (int b = blockIdx.x * (blockDim.x / WAVE) + threadIdx.x / WAVE; b < a.num_paths; b += nw) {
+        int c21 = -1, c31 = -1, cJ = -1;
+        const cf *x = a.tracks + (size_t)b * (NV + 1);
+        if (is_converged(a.conv, b, a.num_paths, quirks) && is_candidate(x, lane)) {
+            Selection<JOINT> *sel = a.sels;
+            if constexpr (GROUPED) {
+                const int t = __builtin_amdgcn_readfirstlane(a.sample_group[b / NTRK]);   // wave-uniform
+                const hcTripletGroup g = a.groups[t];
+                sc = load_scene(g.num_edgels, g.locations, g.K);
+                sel += t;
+            }
+            Pose P;
+            make_pose(quirks ? a.tracks : x, P);   // quirk: converted from the base pointer (:334-341)
+            int a21 = 0, a31 = 0, aJ = 0;
+            for (int e = lane; e < sc.E; e += WAVE) {
+                bool in21, in31;
+                edgel_views(sc, e, P.R, P.t, P.R + 9, P.t + 3, in21, in31);
+                a21 += in21 ? 1 : 0;
+                a31 += in31 ? 1 : 0;
+                if constexpr (JOINT) aJ += (in21 && in31) ? 1 : 0;
+            }
+            c21 = wave_sum_i(a21);
+            c31 = wave_sum_i(a31);
+            if constexpr (JOINT) cJ = wave_sum_i(aJ);
+            if (lane == 0) {
+                atomicAdd(&sel->num_candidates, 1);
+                if constexpr (JOINT) {
+                    key_max(&sel->key, sel_key(cJ, b, false));
+                } else {
+                    key_max(&sel->key21, sel_key(c21, b, quirks));
+                    key_max(&sel->key31, sel_key(c31, b, quirks));
                 }
             }
         }
         if (lane == 0) {
-            inl[2 * (size_t)b] = c21;
-            inl[2 * (size_t)b + 1] = c31;
+            if constexpr (JOINT) {
+                a.inl[3 * (size_t)b] = cJ;
+                a.inl[3 * (size_t)b + 1] = c21;
+                a.inl[3 * (size_t)b + 2] = c31;
+            } else {
+                a.inl[2 * (size_t)b] = c21;
+                a.inl[2 * (size_t)b + 1] = c31;
+            }
         }
     }
 }
@@ -181,157 +246,6 @@ __device__ __forceinline__ void decode_selection(int num_paths, const cf *__rest
         for (int i = 0; i < 3; i++) t[i] = P.t[v * 3 + i];
         if (v == 0) { sel->path21 = b; sel->inliers21 = cnt; }
         else { sel->path31 = b; sel->inliers31 = cnt; }
-    }
-}
-
-__global__ void __launch_bounds__(64) k_pose_final(int num_paths, const cf *__restrict__ tracks,
-                                                   const int32_t *__restrict__ inl, int flags, hcPoseSelection *sel) {
-    if (threadIdx.x != 0) return;
-    decode_selection(num_paths, tracks, inl, (flags & HC_POSE_REFERENCE_QUIRKS) != 0, sel);
-}
-
-// Grouped (multi-triplet) scoring: k_pose_support with the scene of the
-// candidate's own triplet.  A wave reads its group id from its sample and the
-// group's descriptor with wave-uniform loads; the selection atomics go to the
-// group's own hcPoseSelection.  The pose and reprojection arithmetic is the
-// single-triplet kernel's (make_pose, count_inliers), so the counts and the
-// selected pose are the bits a single-triplet call over the group's samples gives.
-__global__ void __launch_bounds__(256) k_pose_support_grouped(int num_paths, const cf *__restrict__ tracks,
-                                                              const uint8_t *__restrict__ conv,
-                                                              const hcTripletGroup *__restrict__ groups,
-                                                              const int32_t *__restrict__ sample_group,
-                                                              int32_t *__restrict__ inl, hcPoseSelection *sels) {
-    const int lane = lane_id();
-    const int nw = gridDim.x * (blockDim.x / WAVE);
-    for (int b = blockIdx.x * (blockDim.x / WAVE) + threadIdx.x / WAVE; b < num_paths; b += nw) {
-        int c21 = -1, c31 = -1;
-        if (conv[b] != 0) {
-            const cf *x = tracks + (size_t)b * (NV + 1);
-            const cf xv = lane < NV ? x[lane] : cmk(0.0f, 0.0f);
-            const unsigned long long im = __ballot(lane >= 24 && lane < NV && (double)__builtin_fabsf(xv.y) < 1e-5);
-            const unsigned long long dp = __ballot(lane < 8 && xv.x >= 0.0f);
-            if ((im & 0x3F000000ull) == 0x3F000000ull && (dp & 0xFFull) == 0xFFull) {
-                const int t = __builtin_amdgcn_readfirstlane(sample_group[b / NTRK]);   // wave-uniform
-                const hcTripletGroup g = groups[t];
-                const float K0 = g.K[0], K2 = g.K[2], K4 = g.K[4], K5 = g.K[5];
-                Pose P;
-                make_pose(x, P);
-                count_inliers(P, g.num_edgels, g.locations, K0, K2, K4, K5, lane, c21, c31);
-                if (lane == 0) {
-                    hcPoseSelection *sel = sels + t;
-                    atomicAdd(&sel->num_candidates, 1);
-                    atomicMax(reinterpret_cast<unsigned long long *>(&sel->key21),
-                              (unsigned long long)sel_key(c21, b, false));
-                    atomicMax(reinterpret_cast<unsigned long long *>(&sel->key31),
-                              (unsigned long long)sel_key(c31, b, false));
-                }
-            }
-        }
-        if (lane == 0) {
-            inl[2 * (size_t)b] = c21;
-            inl[2 * (size_t)b + 1] = c31;
-        }
-    }
-}
-
-// one thread per triplet decodes its selection
-__global__ void __launch_bounds__(64) k_pose_final_grouped(int num_paths, const cf *__restrict__ tracks,
-                                                           const int32_t *__restrict__ inl, int num_groups,
-                                                           hcPoseSelection *sels) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t < num_groups) decode_selection(num_paths, tracks, inl, false, sels + t);
-}
-
-// ---------------------------------------------------------------------------
-// Joint selection: ONE hypothesis for both views, scored on the edgels that
-// are inliers in view 1-2 AND in view 1-3 (hcTrifocalSelection).  The layout,
-// the candidate filter, make_pose and reproj_inlier are those of the kernels
-// above, so the two marginal counts and the pose bits are theirs; per edgel
-// both views are evaluated once and three counts are wave-reduced.
-
-// x[0..30] of a converged path: Evaluations.cpp:322-331 (wave-uniform result)
-__device__ __forceinline__ bool is_candidate(const cf *__restrict__ x, int lane) {
-    const cf xv = lane < NV ? x[lane] : cmk(0.0f, 0.0f);
-    const unsigned long long im = __ballot(lane >= 24 && lane < NV && (double)__builtin_fabsf(xv.y) < 1e-5);
-    const unsigned long long dp = __ballot(lane < 8 && xv.x >= 0.0f);
-    return (im & 0x3F000000ull) == 0x3F000000ull && (dp & 0xFFull) == 0xFFull;
-}
-
-__device__ __forceinline__ bool joint_views(const float *__restrict__ loc, int e, const float *R21, const float *t21,
-                                            const float *R31, const float *t31, float K0, float K2, float K4, float K5,
-                                            bool &in21, bool &in31) {
-    const float2 g01 = *reinterpret_cast<const float2 *>(loc + (size_t)e * 6);
-    const float2 g23 = *reinterpret_cast<const float2 *>(loc + (size_t)e * 6 + 2);
-    const float2 g45 = *reinterpret_cast<const float2 *>(loc + (size_t)e * 6 + 4);
-    in21 = reproj_inlier(g01.x, g01.y, g23.x, g23.y, R21, t21, K0, K2, K4, K5);
-    in31 = reproj_inlier(g01.x, g01.y, g45.x, g45.y, R31, t31, K0, K2, K4, K5);
-    return in21 && in31;
-}
-
-// Scores candidate b on one scene, publishes its key to sel and writes its
-// three counts (joint, 21, 31) to inl[3b..3b+2].
-__device__ __forceinline__ void score_joint(const cf *__restrict__ x, int b, int E, const float *__restrict__ loc,
-                                            float K0, float K2, float K4, float K5, int lane, int32_t *__restrict__ inl,
-                                            hcTrifocalSelection *sel) {
-    Pose P;
-    make_pose(x, P);
-    int a21 = 0, a31 = 0, aJ = 0;
-    for (int e = lane; e < E; e += WAVE) {
-        bool in21, in31;
-        const bool both = joint_views(loc, e, P.R, P.t, P.R + 9, P.t + 3, K0, K2, K4, K5, in21, in31);
-        a21 += in21 ? 1 : 0;
-        a31 += in31 ? 1 : 0;
-        aJ += both ? 1 : 0;
-    }
-    const int c21 = wave_sum_i(a21), c31 = wave_sum_i(a31), cJ = wave_sum_i(aJ);
-    if (lane == 0) {
-        atomicAdd(&sel->num_candidates, 1);
-        atomicMax(reinterpret_cast<unsigned long long *>(&sel->key), (unsigned long long)sel_key(cJ, b, false));
-        inl[3 * (size_t)b] = cJ;
-        inl[3 * (size_t)b + 1] = c21;
-        inl[3 * (size_t)b + 2] = c31;
-    }
-}
-
-__device__ __forceinline__ void not_a_candidate(int b, int lane, int32_t *__restrict__ inl) {
-    if (lane == 0) {
-        inl[3 * (size_t)b] = -1;
-        inl[3 * (size_t)b + 1] = -1;
-        inl[3 * (size_t)b + 2] = -1;
-    }
-}
-
-__global__ void __launch_bounds__(256) k_pose_support_joint(int num_paths, const cf *__restrict__ tracks,
-                                                            const uint8_t *__restrict__ conv, int E,
-                                                            const float *__restrict__ loc, const float *__restrict__ K,
-                                                            int32_t *__restrict__ inl, hcTrifocalSelection *sel) {
-    const int lane = lane_id();
-    const int nw = gridDim.x * (blockDim.x / WAVE);
-    const float K0 = K[0], K2 = K[2], K4 = K[4], K5 = K[5];
-    for (int b = blockIdx.x * (blockDim.x / WAVE) + threadIdx.x / WAVE; b < num_paths; b += nw) {
-        const cf *x = tracks + (size_t)b * (NV + 1);
-        if (conv[b] != 0 && is_candidate(x, lane)) score_joint(x, b, E, loc, K0, K2, K4, K5, lane, inl, sel);
-        else not_a_candidate(b, lane, inl);
-    }
-}
-
-__global__ void __launch_bounds__(256) k_pose_support_joint_grouped(int num_paths, const cf *__restrict__ tracks,
-                                                                    const uint8_t *__restrict__ conv,
-                                                                    const hcTripletGroup *__restrict__ groups,
-                                                                    const int32_t *__restrict__ sample_group,
-                                                                    int32_t *__restrict__ inl,
-                                                                    hcTrifocalSelection *sels) {
-    const int lane = lane_id();
-    const int nw = gridDim.x * (blockDim.x / WAVE);
-    for (int b = blockIdx.x * (blockDim.x / WAVE) + threadIdx.x / WAVE; b < num_paths; b += nw) {
-        const cf *x = tracks + (size_t)b * (NV + 1);
-        if (conv[b] != 0 && is_candidate(x, lane)) {
-            const int t = __builtin_amdgcn_readfirstlane(sample_group[b / NTRK]);   // wave-uniform
-            const hcTripletGroup g = groups[t];
-            score_joint(x, b, g.num_edgels, g.locations, g.K[0], g.K[2], g.K[4], g.K[5], lane, inl, sels + t);
-        } else {
-            not_a_candidate(b, lane, inl);
-        }
     }
 }
 
@@ -366,12 +280,13 @@ __device__ __forceinline__ void decode_joint(int num_paths, const cf *__restrict
     sel->scale31 = scale;
 }
 
-// one thread per selection (num_sel = 1 for the single-triplet call)
-__global__ void __launch_bounds__(64) k_pose_final_joint(int num_paths, const cf *__restrict__ tracks,
-                                                         const int32_t *__restrict__ inl, int num_sel,
-                                                         hcTrifocalSelection *sels) {
+// one thread per selection (num_sel = 1 for the single-triplet calls)
+template <bool JOINT>
+__global__ void __launch_bounds__(64) k_pose_final(const PoseArgs<JOINT> a) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t < num_sel) decode_joint(num_paths, tracks, inl, sels + t);
+    if (t >= a.num_sel) return;
+    if constexpr (JOINT) decode_joint(a.num_paths, a.tracks, a.inl, a.sels + t);
+    else decode_selection(a.num_paths, a.tracks, a.inl, (a.flags & HC_POSE_REFERENCE_QUIRKS) != 0, a.sels + t);
 }
 
 // Inlier mask of a device-resident selection: one wave per 64-bit word, lane l
@@ -384,7 +299,7 @@ __global__ void __launch_bounds__(256) k_pose_inlier_mask(const hcTrifocalSelect
                                                           int num_words, unsigned long long *__restrict__ mask) {
     const int lane = lane_id();
     const int nw = gridDim.x * (blockDim.x / WAVE);
-    const float K0 = K[0], K2 = K[2], K4 = K[4], K5 = K[5];
+    const Scene sc = load_scene(E, loc, K);
     const bool have = sel->path >= 0;
     float R21[9], t21[3], R31[9], t31[3];
 #pragma unroll
@@ -393,12 +308,9 @@ __global__ void __launch_bounds__(256) k_pose_inlier_mask(const hcTrifocalSelect
     for (int i = 0; i < 3; i++) { t21[i] = sel->t21[i]; t31[i] = sel->t31[i]; }
     for (int w = blockIdx.x * (blockDim.x / WAVE) + threadIdx.x / WAVE; w < num_words; w += nw) {
         const int e = w * WAVE + lane;
-        bool both = false;
-        if (have && e < E) {
-            bool in21, in31;
-            both = joint_views(loc, e, R21, t21, R31, t31, K0, K2, K4, K5, in21, in31);
-        }
-        const unsigned long long word = __ballot(both);
+        bool in21 = false, in31 = false;
+        if (have && e < E) edgel_views(sc, e, R21, t21, R31, t31, in21, in31);
+        const unsigned long long word = __ballot(in21 && in31);
         if (lane == 0) mask[w] = word;
     }
 }
@@ -413,34 +325,79 @@ inline hcStatus path_grid(int num_paths, int &blocks) {
     return HC_SUCCESS;
 }
 
+// The launch sequence of the four entry points (arguments already validated):
+// zeroed selections, the support kernel over the paths, the decoding epilogue.
+// Without paths there is no device query and no support launch, and the
+// epilogue writes the "none" selections.
+template <bool JOINT, bool GROUPED>
+hcStatus launch_pose_support(const PoseArgs<JOINT> &a, hcStream stream) {
+    hipStream_t s = (hipStream_t)stream;
+    (void)hipGetLastError();
+    if ((g_last_hip_error = hipMemsetAsync(a.sels, 0, sizeof(Selection<JOINT>) * (size_t)a.num_sel, s)) != hipSuccess)
+        return HC_ERROR_LAUNCH;
+    if (a.num_paths > 0) {
+        int blocks = 0;
+        const hcStatus st = path_grid(a.num_paths, blocks);
+        if (st != HC_SUCCESS) return st;
+        hipLaunchKernelGGL((k_pose_support<JOINT, GROUPED>), dim3(blocks), dim3(256), 0, s, a);
+        if ((g_last_hip_error = hipGetLastError()) != hipSuccess) return HC_ERROR_LAUNCH;
+    }
+    hipLaunchKernelGGL(k_pose_final<JOINT>, dim3((a.num_sel + 63) / 64), dim3(64), 0, s, a);
+    if ((g_last_hip_error = hipGetLastError()) != hipSuccess) return HC_ERROR_LAUNCH;
+    return HC_SUCCESS;
+}
+
+template <bool JOINT>
+hcStatus pose_support_single(int num_paths, const hcComplex *tracks, const uint8_t *converge, int num_edgels,
+                             const float *locations, const float *K, int flags, int32_t *inliers,
+                             Selection<JOINT> *selection, hcStream stream) {
+    constexpr int allowed_flags = JOINT ? 0 : HC_POSE_REFERENCE_QUIRKS;
+    if (num_paths < 0 || num_edgels < 0 || !selection || (flags & ~allowed_flags) != 0) return HC_ERROR_INVALID_VALUE;
+    if (num_paths > 0 && (!tracks || !converge || !inliers || !K || (num_edgels > 0 && !locations)))
+        return HC_ERROR_INVALID_VALUE;
+    const PoseArgs<JOINT> a{num_paths, (const cf *)tracks, converge, num_edgels, locations, K, nullptr, nullptr,
+                            flags, inliers, selection, 1};
+    return launch_pose_support<JOINT, false>(a, stream);
+}
+
+// (the quirks flag's literal indexing has no per-group meaning: no flag is accepted)
+template <bool JOINT>
+hcStatus pose_support_grouped(int num_paths, const hcComplex *tracks, const uint8_t *converge, int num_groups,
+                              const hcTripletGroup *groups, const int32_t *sample_group, int flags, int32_t *inliers,
+                              Selection<JOINT> *selections, hcStream stream) {
+    if (num_paths < 0 || num_paths % NTRK != 0 || num_groups < 1 || !groups || !selections || flags != 0)
+        return HC_ERROR_INVALID_VALUE;
+    if (num_paths > 0 && (!tracks || !converge || !inliers || !sample_group)) return HC_ERROR_INVALID_VALUE;
+    const PoseArgs<JOINT> a{num_paths, (const cf *)tracks, converge, 0, nullptr, nullptr, groups, sample_group,
+                            0, inliers, selections, num_groups};
+    return launch_pose_support<JOINT, true>(a, stream);
+}
+
 }  // namespace
 
 }  // namespace hc
+
+extern "C" hcStatus hc_trifocal_pose_support(int num_paths, const hcComplex *tracks, const uint8_t *converge,
+                                             int num_edgels, const float *locations, const float *K, int flags,
+                                             int32_t *inliers, hcPoseSelection *selection, hcStream stream) {
+    return hc::pose_support_single<false>(num_paths, tracks, converge, num_edgels, locations, K, flags, inliers,
+                                          selection, stream);
+}
 
 extern "C" hcStatus hc_trifocal_pose_support_joint(int num_paths, const hcComplex *tracks, const uint8_t *converge,
                                                    int num_edgels, const float *locations, const float *K, int flags,
                                                    int32_t *inliers, hcTrifocalSelection *selection,
                                                    hcStream stream) {
-    using namespace hc;
-    if (num_paths < 0 || num_edgels < 0 || !selection || flags != 0) return HC_ERROR_INVALID_VALUE;
-    if (num_paths > 0 && (!tracks || !converge || !inliers || !K || (num_edgels > 0 && !locations)))
-        return HC_ERROR_INVALID_VALUE;
-    hipStream_t s = (hipStream_t)stream;
-    (void)hipGetLastError();
-    if ((g_last_hip_error = hipMemsetAsync(selection, 0, sizeof(hcTrifocalSelection), s)) != hipSuccess)
-        return HC_ERROR_LAUNCH;
-    if (num_paths > 0) {
-        int blocks = 0;
-        const hcStatus st = path_grid(num_paths, blocks);
-        if (st != HC_SUCCESS) return st;
-        hipLaunchKernelGGL(k_pose_support_joint, dim3(blocks), dim3(256), 0, s, num_paths, (const cf *)tracks, converge,
-                           num_edgels, locations, K, inliers, selection);
-        if ((g_last_hip_error = hipGetLastError()) != hipSuccess) return HC_ERROR_LAUNCH;
-    }
-    hipLaunchKernelGGL(k_pose_final_joint, dim3(1), dim3(64), 0, s, num_paths, (const cf *)tracks,
-                       (const int32_t *)inliers, 1, selection);
-    if ((g_last_hip_error = hipGetLastError()) != hipSuccess) return HC_ERROR_LAUNCH;
-    return HC_SUCCESS;
+    return hc::pose_support_single<true>(num_paths, tracks, converge, num_edgels, locations, K, flags, inliers,
+                                         selection, stream);
+}
+
+extern "C" hcStatus hc_trifocal_pose_support_grouped(int num_paths, const hcComplex *tracks, const uint8_t *converge,
+                                                     int num_groups, const hcTripletGroup *groups,
+                                                     const int32_t *sample_group, int flags, int32_t *inliers,
+                                                     hcPoseSelection *selections, hcStream stream) {
+    return hc::pose_support_grouped<false>(num_paths, tracks, converge, num_groups, groups, sample_group, flags,
+                                           inliers, selections, stream);
 }
 
 extern "C" hcStatus hc_trifocal_pose_support_joint_grouped(int num_paths, const hcComplex *tracks,
@@ -448,27 +405,8 @@ extern "C" hcStatus hc_trifocal_pose_support_joint_grouped(int num_paths, const 
                                                            const hcTripletGroup *groups, const int32_t *sample_group,
                                                            int flags, int32_t *inliers,
                                                            hcTrifocalSelection *selections, hcStream stream) {
-    using namespace hc;
-    if (num_paths < 0 || num_paths % NTRK != 0 || num_groups < 1 || !groups || !selections || flags != 0)
-        return HC_ERROR_INVALID_VALUE;
-    if (num_paths > 0 && (!tracks || !converge || !inliers || !sample_group)) return HC_ERROR_INVALID_VALUE;
-    hipStream_t s = (hipStream_t)stream;
-    (void)hipGetLastError();
-    if ((g_last_hip_error = hipMemsetAsync(selections, 0, sizeof(hcTrifocalSelection) * (size_t)num_groups, s)) !=
-        hipSuccess)
-        return HC_ERROR_LAUNCH;
-    if (num_paths > 0) {
-        int blocks = 0;
-        const hcStatus st = path_grid(num_paths, blocks);
-        if (st != HC_SUCCESS) return st;
-        hipLaunchKernelGGL(k_pose_support_joint_grouped, dim3(blocks), dim3(256), 0, s, num_paths, (const cf *)tracks,
-                           converge, groups, sample_group, inliers, selections);
-        if ((g_last_hip_error = hipGetLastError()) != hipSuccess) return HC_ERROR_LAUNCH;
-    }
-    hipLaunchKernelGGL(k_pose_final_joint, dim3((num_groups + 63) / 64), dim3(64), 0, s, num_paths, (const cf *)tracks,
-                       (const int32_t *)inliers, num_groups, selections);
-    if ((g_last_hip_error = hipGetLastError()) != hipSuccess) return HC_ERROR_LAUNCH;
-    return HC_SUCCESS;
+    return hc::pose_support_grouped<true>(num_paths, tracks, converge, num_groups, groups, sample_group, flags,
+                                          inliers, selections, stream);
 }
 
 extern "C" hcStatus hc_trifocal_pose_inlier_mask(const hcTrifocalSelection *selection, int num_edgels,
@@ -485,62 +423,6 @@ extern "C" hcStatus hc_trifocal_pose_inlier_mask(const hcTrifocalSelection *sele
     (void)hipGetLastError();
     hipLaunchKernelGGL(k_pose_inlier_mask, dim3(blocks), dim3(256), 0, (hipStream_t)stream, selection, num_edgels,
                        locations, K, words, reinterpret_cast<unsigned long long *>(mask));
-    if ((g_last_hip_error = hipGetLastError()) != hipSuccess) return HC_ERROR_LAUNCH;
-    return HC_SUCCESS;
-}
-
-extern "C" hcStatus hc_trifocal_pose_support(int num_paths, const hcComplex *tracks, const uint8_t *converge,
-                                             int num_edgels, const float *locations, const float *K, int flags,
-                                             int32_t *inliers, hcPoseSelection *selection, hcStream stream) {
-    using namespace hc;
-    if (num_paths < 0 || num_edgels < 0 || !selection || (flags & ~HC_POSE_REFERENCE_QUIRKS) != 0)
-        return HC_ERROR_INVALID_VALUE;
-    if (num_paths > 0 && (!tracks || !converge || !inliers || !K || (num_edgels > 0 && !locations)))
-        return HC_ERROR_INVALID_VALUE;
-    hipStream_t s = (hipStream_t)stream;
-    (void)hipGetLastError();
-    if ((g_last_hip_error = hipMemsetAsync(selection, 0, sizeof(hcPoseSelection), s)) != hipSuccess) return HC_ERROR_LAUNCH;
-    if (num_paths > 0) {
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) != hipSuccess) return HC_ERROR_DEVICE;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return HC_ERROR_DEVICE;
-        const long long waves = num_paths < cus * 32 ? num_paths : (long long)cus * 32;
-        const int blocks = (int)((waves + 3) / 4);
-        hipLaunchKernelGGL(k_pose_support, dim3(blocks), dim3(256), 0, s, num_paths, (const cf *)tracks, converge,
-                           num_edgels, locations, K, flags, inliers, selection);
-        if ((g_last_hip_error = hipGetLastError()) != hipSuccess) return HC_ERROR_LAUNCH;
-    }
-    hipLaunchKernelGGL(k_pose_final, dim3(1), dim3(64), 0, s, num_paths, (const cf *)tracks, (const int32_t *)inliers,
-                       flags, selection);
-    if ((g_last_hip_error = hipGetLastError()) != hipSuccess) return HC_ERROR_LAUNCH;
-    return HC_SUCCESS;
-}
-
-extern "C" hcStatus hc_trifocal_pose_support_grouped(int num_paths, const hcComplex *tracks, const uint8_t *converge,
-                                                     int num_groups, const hcTripletGroup *groups,
-                                                     const int32_t *sample_group, int flags, int32_t *inliers,
-                                                     hcPoseSelection *selections, hcStream stream) {
-    using namespace hc;
-    // (the quirks flag's literal indexing has no per-group meaning: no flag is accepted)
-    if (num_paths < 0 || num_paths % NTRK != 0 || num_groups < 1 || !groups || !selections || flags != 0)
-        return HC_ERROR_INVALID_VALUE;
-    if (num_paths > 0 && (!tracks || !converge || !inliers || !sample_group)) return HC_ERROR_INVALID_VALUE;
-    hipStream_t s = (hipStream_t)stream;
-    (void)hipGetLastError();
-    if ((g_last_hip_error = hipMemsetAsync(selections, 0, sizeof(hcPoseSelection) * (size_t)num_groups, s)) != hipSuccess)
-        return HC_ERROR_LAUNCH;
-    if (num_paths > 0) {
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) != hipSuccess) return HC_ERROR_DEVICE;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return HC_ERROR_DEVICE;
-        const long long waves = num_paths < cus * 32 ? num_paths : (long long)cus * 32;
-        const int blocks = (int)((waves + 3) / 4);
-        hipLaunchKernelGGL(k_pose_support_grouped, dim3(blocks), dim3(256), 0, s, num_paths, (const cf *)tracks, converge,
-                           groups, sample_group, inliers, selections);
-        if ((g_last_hip_error = hipGetLastError()) != hipSuccess) return HC_ERROR_LAUNCH;
-    }
-    hipLaunchKernelGGL(k_pose_final_grouped, dim3((num_groups + 63) / 64), dim3(64), 0, s, num_paths, (const cf *)tracks,
-                       (const int32_t *)inliers, num_groups, selections);
     if ((g_last_hip_error = hipGetLastError()) != hipSuccess) return HC_ERROR_LAUNCH;
     return HC_SUCCESS;
 }

@@ -11,10 +11,14 @@ grouped form select one hypothesis for both views, by the number of edgels that
 are inliers in both; hc_trifocal_pose_inlier_mask lists those edgels and
 hc_pose_merge_joint merges per-launch selections (pose_support_joint,
 pose_support_joint_grouped, inlier_mask, merge_joint below).
+
+The four pose-support calls (per view / joint, one triplet / grouped) share one
+launcher and one synchronous wrapper (_launch, _run), parameterised by a _Rule.
 """
 from __future__ import annotations
 
 import ctypes as C
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -23,6 +27,7 @@ from . import _abi
 from .problem import RansacData
 
 SEL_BYTES = _abi.POSE_SELECTION_BYTES
+JOINT_SEL_BYTES = _abi.TRIFOCAL_SELECTION_BYTES
 
 
 def _stream_handle(stream, device):
@@ -30,29 +35,13 @@ def _stream_handle(stream, device):
     return C.c_void_p(s.cuda_stream)
 
 
-def launch_pose_support(tracks: torch.Tensor, converge: torch.Tensor, edgels: torch.Tensor, K: torch.Tensor,
-                        inliers: torch.Tensor, selection: torch.Tensor, quirks: bool = False, stream=None) -> None:
-    """Enqueue candidate filter + pose + inlier scoring + selection (no sync).
-    tracks (n, 31, 2) f32, converge (n,) u8, edgels (E, 6) f32, K (9,) f32 on the
-    same device; inliers (n, 2) i32 and selection (SEL_BYTES,) u8 are outputs."""
-    n = converge.numel()
-    if tracks.shape[0] != n or inliers.numel() < 2 * n or selection.numel() < SEL_BYTES:
-        raise _abi.HCError("pose_support: buffer sizes do not match")
-    for t in (tracks, converge, edgels, K, inliers, selection):
-        if not t.is_cuda or not t.is_contiguous():
-            raise _abi.HCError("pose_support: buffers must be contiguous device tensors")
-    L = _abi.lib()
-    _abi.check(L.hc_trifocal_pose_support(n, C.c_void_p(tracks.data_ptr()), C.c_void_p(converge.data_ptr()),
-                                          int(edgels.shape[0]), C.c_void_p(edgels.data_ptr()),
-                                          C.c_void_p(K.data_ptr()), _abi.HC_POSE_REFERENCE_QUIRKS if quirks else 0,
-                                          C.c_void_p(inliers.data_ptr()), C.c_void_p(selection.data_ptr()),
-                                          _stream_handle(stream, tracks.device)),
-               "hc_trifocal_pose_support")
+def _struct_from_raw(cls, nbytes, raw):
+    b = raw.cpu().numpy() if isinstance(raw, torch.Tensor) else np.asarray(raw)
+    return cls.from_buffer_copy(np.ascontiguousarray(b, np.uint8).tobytes()[:nbytes])
 
 
 def selection_struct(raw: np.ndarray | torch.Tensor) -> _abi.hcPoseSelection:
-    b = raw.cpu().numpy() if isinstance(raw, torch.Tensor) else np.asarray(raw)
-    return _abi.hcPoseSelection.from_buffer_copy(np.ascontiguousarray(b, np.uint8).tobytes()[:SEL_BYTES])
+    return _struct_from_raw(_abi.hcPoseSelection, SEL_BYTES, raw)
 
 
 def selection_dict(s: _abi.hcPoseSelection) -> dict:
@@ -62,83 +51,12 @@ def selection_dict(s: _abi.hcPoseSelection) -> dict:
                 R31=np.array(s.R31[:], np.float32), t31=np.array(s.t31[:], np.float32))
 
 
-def pose_support(tracks: torch.Tensor, converge: torch.Tensor, data_edgels: torch.Tensor, K: torch.Tensor,
-                 quirks: bool = False):
-    """Synchronous wrapper: returns (inliers (n, 2) numpy, selection dict)."""
-    dev = tracks.device
-    n = converge.numel()
-    inl = torch.empty((n, 2), dtype=torch.int32, device=dev)
-    sel = torch.empty(SEL_BYTES, dtype=torch.uint8, device=dev)
-    launch_pose_support(tracks, converge, data_edgels, K, inl, sel, quirks)
-    torch.cuda.synchronize(dev)
-    return inl.cpu().numpy(), selection_dict(selection_struct(sel))
-
-
-def launch_pose_support_grouped(tracks: torch.Tensor, converge: torch.Tensor, batch, inliers: torch.Tensor,
-                                selections: torch.Tensor, stream=None) -> None:
-    """Enqueue the pose support of several triplets' samples in one call (no
-    sync): hc_trifocal_pose_support_grouped.  batch is a
-    multi.DeviceTripletBatch; tracks / converge cover its samples in its order;
-    selections (T * SEL_BYTES,) u8 receives one hcPoseSelection per triplet."""
-    n = converge.numel()
-    T = batch.num_groups
-    if tracks.shape[0] != n or n != batch.num_samples * _abi.NUM_TRACKS or inliers.numel() < 2 * n or \
-            selections.numel() < T * SEL_BYTES:
-        raise _abi.HCError("pose_support_grouped: buffer sizes do not match")
-    for t in (tracks, converge, inliers, selections):
-        if not t.is_cuda or not t.is_contiguous() or t.device != batch.target.device:
-            raise _abi.HCError("pose_support_grouped: buffers must be contiguous tensors on the batch's device")
-    batch.check()   # group ids and edgel counts: the kernels do not validate them
-    L = _abi.lib()
-    _abi.check(L.hc_trifocal_pose_support_grouped(n, C.c_void_p(tracks.data_ptr()), C.c_void_p(converge.data_ptr()),
-                                                  T, C.c_void_p(batch.groups.data_ptr()),
-                                                  C.c_void_p(batch.sample_group.data_ptr()), 0,
-                                                  C.c_void_p(inliers.data_ptr()), C.c_void_p(selections.data_ptr()),
-                                                  _stream_handle(stream, tracks.device)),
-               "hc_trifocal_pose_support_grouped")
-
-
-def pose_support_grouped(tracks: torch.Tensor, converge: torch.Tensor, batch):
-    """Synchronous wrapper: returns (inliers (n, 2) numpy, [selection dict] * T).
-    Paths in the selections are the call's batch ids."""
-    if not hasattr(batch, "groups"):
-        batch = batch.to(tracks.device)
-    dev = tracks.device
-    n = converge.numel()
-    inl = torch.empty((n, 2), dtype=torch.int32, device=dev)
-    sel = torch.empty(batch.num_groups * SEL_BYTES, dtype=torch.uint8, device=dev)
-    launch_pose_support_grouped(tracks, converge, batch, inl, sel)
-    torch.cuda.synchronize(dev)
-    raw = sel.cpu().numpy()
-    return inl.cpu().numpy(), [selection_dict(selection_struct(raw[t * SEL_BYTES:(t + 1) * SEL_BYTES]))
-                               for t in range(batch.num_groups)]
-
-
-def merge(parts: list, path_offsets: list, quirks: bool = False) -> dict:
-    """hc_pose_merge: per-GPU selections (raw bytes or structs) with their first
-    batch ids -> one selection with global batch ids."""
-    n = len(parts)
-    arr = (_abi.hcPoseSelection * max(1, n))()
-    for i, p in enumerate(parts):
-        arr[i] = p if isinstance(p, _abi.hcPoseSelection) else selection_struct(p)
-    offs = np.ascontiguousarray(path_offsets, np.int32)
-    out = _abi.hcPoseSelection()
-    _abi.lib().hc_pose_merge(n, C.cast(arr, C.c_void_p), C.c_void_p(offs.ctypes.data),
-                             _abi.HC_POSE_REFERENCE_QUIRKS if quirks else 0, C.byref(out))
-    return selection_dict(out)
-
-
-# ----------------------------------------------------------------- joint selection
 # One hypothesis for both views, scored on the edgels that are inliers in view
 # 1-2 and in view 1-3 (hcTrifocalSelection, include/hc_pose.h).
-JOINT_SEL_BYTES = _abi.TRIFOCAL_SELECTION_BYTES
-
-
 def joint_selection_struct(raw) -> _abi.hcTrifocalSelection:
     if isinstance(raw, _abi.hcTrifocalSelection):
         return raw
-    b = raw.cpu().numpy() if isinstance(raw, torch.Tensor) else np.asarray(raw)
-    return _abi.hcTrifocalSelection.from_buffer_copy(np.ascontiguousarray(b, np.uint8).tobytes()[:JOINT_SEL_BYTES])
+    return _struct_from_raw(_abi.hcTrifocalSelection, JOINT_SEL_BYTES, raw)
 
 
 def joint_selection_dict(s: _abi.hcTrifocalSelection) -> dict:
@@ -159,24 +77,93 @@ def joint_selection_from_dict(d: dict) -> _abi.hcTrifocalSelection:
     return s
 
 
+# A selection rule: the entry point's name (+ "_grouped"), the int32 columns of
+# its per-path counts, and its selection struct's size and converters.
+_Rule = namedtuple("_Rule", "name columns sel_bytes struct to_dict")
+_PER_VIEW = _Rule("pose_support", 2, SEL_BYTES, selection_struct, selection_dict)
+_JOINT = _Rule("pose_support_joint", 3, JOINT_SEL_BYTES, joint_selection_struct, joint_selection_dict)
+
+
+def _launch(rule, tracks, converge, scene, inliers, selections, flags, stream) -> None:
+    """Enqueue hc_trifocal_<rule.name> on scene = (edgels, K), or its grouped
+    form on scene = a multi.DeviceTripletBatch (no sync)."""
+    grouped = not isinstance(scene, tuple)
+    name = rule.name + ("_grouped" if grouped else "")
+    n = converge.numel()
+    T = scene.num_groups if grouped else 1
+    if tracks.shape[0] != n or (grouped and n != scene.num_samples * _abi.NUM_TRACKS) or \
+            inliers.numel() < rule.columns * n or selections.numel() < T * rule.sel_bytes:
+        raise _abi.HCError(f"{name}: buffer sizes do not match")
+    if grouped:
+        for t in (tracks, converge, inliers, selections):
+            if not t.is_cuda or not t.is_contiguous() or t.device != scene.target.device:
+                raise _abi.HCError(f"{name}: buffers must be contiguous tensors on the batch's device")
+        scene.check()   # group ids and edgel counts: the kernels do not validate them
+        scene_args = (T, scene.groups, scene.sample_group)
+    else:
+        for t in (tracks, converge, *scene, inliers, selections):
+            if not t.is_cuda or not t.is_contiguous():
+                raise _abi.HCError(f"{name}: buffers must be contiguous device tensors")
+        scene_args = (int(scene[0].shape[0]), *scene)
+    args = [C.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor) else a
+            for a in (n, tracks, converge, *scene_args, flags, inliers, selections)]
+    _abi.check(getattr(_abi.lib(), "hc_trifocal_" + name)(*args, _stream_handle(stream, tracks.device)),
+               "hc_trifocal_" + name)
+
+
+def _run(rule, tracks, converge, scene, flags=0):
+    """Synchronous call on fresh buffers: (inliers (n, columns) numpy, the T
+    selection dicts, the selections' device bytes)."""
+    if not isinstance(scene, tuple) and not hasattr(scene, "groups"):
+        scene = scene.to(tracks.device)
+    dev = tracks.device
+    n = converge.numel()
+    T = 1 if isinstance(scene, tuple) else scene.num_groups
+    inl = torch.empty((n, rule.columns), dtype=torch.int32, device=dev)
+    sel = torch.empty(T * rule.sel_bytes, dtype=torch.uint8, device=dev)
+    _launch(rule, tracks, converge, scene, inl, sel, flags, None)
+    torch.cuda.synchronize(dev)
+    raw = sel.cpu().numpy().reshape(T, rule.sel_bytes)
+    return inl.cpu().numpy(), [rule.to_dict(rule.struct(r)) for r in raw], sel
+
+
+def launch_pose_support(tracks: torch.Tensor, converge: torch.Tensor, edgels: torch.Tensor, K: torch.Tensor,
+                        inliers: torch.Tensor, selection: torch.Tensor, quirks: bool = False, stream=None) -> None:
+    """Enqueue candidate filter + pose + inlier scoring + selection (no sync).
+    tracks (n, 31, 2) f32, converge (n,) u8, edgels (E, 6) f32, K (9,) f32 on the
+    same device; inliers (n, 2) i32 and selection (SEL_BYTES,) u8 are outputs."""
+    _launch(_PER_VIEW, tracks, converge, (edgels, K), inliers, selection,
+            _abi.HC_POSE_REFERENCE_QUIRKS if quirks else 0, stream)
+
+
+def pose_support(tracks: torch.Tensor, converge: torch.Tensor, data_edgels: torch.Tensor, K: torch.Tensor,
+                 quirks: bool = False):
+    """Synchronous wrapper: returns (inliers (n, 2) numpy, selection dict)."""
+    inl, sels, _ = _run(_PER_VIEW, tracks, converge, (data_edgels, K), _abi.HC_POSE_REFERENCE_QUIRKS if quirks else 0)
+    return inl, sels[0]
+
+
+def launch_pose_support_grouped(tracks: torch.Tensor, converge: torch.Tensor, batch, inliers: torch.Tensor,
+                                selections: torch.Tensor, stream=None) -> None:
+    """Enqueue the pose support of several triplets' samples in one call (no
+    sync): hc_trifocal_pose_support_grouped.  batch is a
+    multi.DeviceTripletBatch; tracks / converge cover its samples in its order;
+    selections (T * SEL_BYTES,) u8 receives one hcPoseSelection per triplet."""
+    _launch(_PER_VIEW, tracks, converge, batch, inliers, selections, 0, stream)
+
+
+def pose_support_grouped(tracks: torch.Tensor, converge: torch.Tensor, batch):
+    """Synchronous wrapper: returns (inliers (n, 2) numpy, [selection dict] * T).
+    Paths in the selections are the call's batch ids."""
+    return _run(_PER_VIEW, tracks, converge, batch)[:2]
+
+
 def launch_pose_support_joint(tracks: torch.Tensor, converge: torch.Tensor, edgels: torch.Tensor, K: torch.Tensor,
                               inliers: torch.Tensor, selection: torch.Tensor, stream=None) -> None:
     """Enqueue candidate filter + pose + joint inlier scoring + selection (no
     sync): hc_trifocal_pose_support_joint.  Buffers as in launch_pose_support,
     but inliers is (n, 3) i32 (joint, 21, 31) and selection (JOINT_SEL_BYTES,) u8."""
-    n = converge.numel()
-    if tracks.shape[0] != n or inliers.numel() < 3 * n or selection.numel() < JOINT_SEL_BYTES:
-        raise _abi.HCError("pose_support_joint: buffer sizes do not match")
-    for t in (tracks, converge, edgels, K, inliers, selection):
-        if not t.is_cuda or not t.is_contiguous():
-            raise _abi.HCError("pose_support_joint: buffers must be contiguous device tensors")
-    L = _abi.lib()
-    _abi.check(L.hc_trifocal_pose_support_joint(n, C.c_void_p(tracks.data_ptr()), C.c_void_p(converge.data_ptr()),
-                                                int(edgels.shape[0]), C.c_void_p(edgels.data_ptr()),
-                                                C.c_void_p(K.data_ptr()), 0, C.c_void_p(inliers.data_ptr()),
-                                                C.c_void_p(selection.data_ptr()),
-                                                _stream_handle(stream, tracks.device)),
-               "hc_trifocal_pose_support_joint")
+    _launch(_JOINT, tracks, converge, (edgels, K), inliers, selection, 0, stream)
 
 
 def pose_support_joint(tracks: torch.Tensor, converge: torch.Tensor, data_edgels: torch.Tensor, K: torch.Tensor,
@@ -184,14 +171,8 @@ def pose_support_joint(tracks: torch.Tensor, converge: torch.Tensor, data_edgels
     """Synchronous wrapper: returns (inliers (n, 3) numpy, selection dict), and
     with return_device_selection also the selection's device bytes (the input of
     inlier_mask)."""
-    dev = tracks.device
-    n = converge.numel()
-    inl = torch.empty((n, 3), dtype=torch.int32, device=dev)
-    sel = torch.empty(JOINT_SEL_BYTES, dtype=torch.uint8, device=dev)
-    launch_pose_support_joint(tracks, converge, data_edgels, K, inl, sel)
-    torch.cuda.synchronize(dev)
-    out = inl.cpu().numpy(), joint_selection_dict(joint_selection_struct(sel))
-    return out + (sel,) if return_device_selection else out
+    inl, sels, sel_dev = _run(_JOINT, tracks, converge, (data_edgels, K))
+    return (inl, sels[0], sel_dev) if return_device_selection else (inl, sels[0])
 
 
 def launch_pose_support_joint_grouped(tracks: torch.Tensor, converge: torch.Tensor, batch, inliers: torch.Tensor,
@@ -199,41 +180,27 @@ def launch_pose_support_joint_grouped(tracks: torch.Tensor, converge: torch.Tens
     """launch_pose_support_grouped with the joint rule
     (hc_trifocal_pose_support_joint_grouped): inliers (n, 3) i32, selections
     (T * JOINT_SEL_BYTES,) u8."""
-    n = converge.numel()
-    T = batch.num_groups
-    if tracks.shape[0] != n or n != batch.num_samples * _abi.NUM_TRACKS or inliers.numel() < 3 * n or \
-            selections.numel() < T * JOINT_SEL_BYTES:
-        raise _abi.HCError("pose_support_joint_grouped: buffer sizes do not match")
-    for t in (tracks, converge, inliers, selections):
-        if not t.is_cuda or not t.is_contiguous() or t.device != batch.target.device:
-            raise _abi.HCError("pose_support_joint_grouped: buffers must be contiguous tensors on the batch's device")
-    batch.check()   # group ids and edgel counts: the kernels do not validate them
-    L = _abi.lib()
-    _abi.check(L.hc_trifocal_pose_support_joint_grouped(n, C.c_void_p(tracks.data_ptr()),
-                                                        C.c_void_p(converge.data_ptr()), T,
-                                                        C.c_void_p(batch.groups.data_ptr()),
-                                                        C.c_void_p(batch.sample_group.data_ptr()), 0,
-                                                        C.c_void_p(inliers.data_ptr()),
-                                                        C.c_void_p(selections.data_ptr()),
-                                                        _stream_handle(stream, tracks.device)),
-               "hc_trifocal_pose_support_joint_grouped")
+    _launch(_JOINT, tracks, converge, batch, inliers, selections, 0, stream)
 
 
 def pose_support_joint_grouped(tracks: torch.Tensor, converge: torch.Tensor, batch):
     """Synchronous wrapper: returns (inliers (n, 3) numpy, [selection dict] * T).
     Paths in the selections are the call's batch ids."""
-    if not hasattr(batch, "groups"):
-        batch = batch.to(tracks.device)
-    dev = tracks.device
-    n = converge.numel()
-    inl = torch.empty((n, 3), dtype=torch.int32, device=dev)
-    sel = torch.empty(batch.num_groups * JOINT_SEL_BYTES, dtype=torch.uint8, device=dev)
-    launch_pose_support_joint_grouped(tracks, converge, batch, inl, sel)
-    torch.cuda.synchronize(dev)
-    raw = sel.cpu().numpy()
-    return inl.cpu().numpy(), [joint_selection_dict(joint_selection_struct(raw[t * JOINT_SEL_BYTES:
-                                                                               (t + 1) * JOINT_SEL_BYTES]))
-                               for t in range(batch.num_groups)]
+    return _run(_JOINT, tracks, converge, batch)[:2]
+
+
+def merge(parts: list, path_offsets: list, quirks: bool = False) -> dict:
+    """hc_pose_merge: per-GPU selections (raw bytes or structs) with their first
+    batch ids -> one selection with global batch ids."""
+    n = len(parts)
+    arr = (_abi.hcPoseSelection * max(1, n))()
+    for i, p in enumerate(parts):
+        arr[i] = p if isinstance(p, _abi.hcPoseSelection) else selection_struct(p)
+    offs = np.ascontiguousarray(path_offsets, np.int32)
+    out = _abi.hcPoseSelection()
+    _abi.lib().hc_pose_merge(n, C.cast(arr, C.c_void_p), C.c_void_p(offs.ctypes.data),
+                             _abi.HC_POSE_REFERENCE_QUIRKS if quirks else 0, C.byref(out))
+    return selection_dict(out)
 
 
 def inlier_mask(selection, edgels: torch.Tensor, K: torch.Tensor, packed: bool = False, stream=None) -> np.ndarray:
