@@ -198,6 +198,39 @@ typedef struct {
 hcStatus hc_trifocal_2op1p_30x30_track_abort_grouped(const hcTrackArgs *args, const hcGroupedAbortArgs *g,
                                                      void *workspace, size_t workspace_bytes, hcStream stream);
 
+/* ---- gated abort tracking: the stop rule is joint inlier support ----
+ * The 0.90 per-view gate above is never reached on noisy edgels.  This launch
+ * stops a triplet at the first hypothesis whose joint inlier count -- the
+ * edgels within 2 px in view 1-2 AND in view 1-3, the count of
+ * hc_trifocal_pose_support_joint (hc_pose.h) -- reaches a caller-set share of
+ * the triplet's edgels. */
+typedef struct {
+    float    min_joint_ratio;   /* > 0, finite; a value > 1 never passes */
+    int32_t  pad;
+    int32_t *joint_inliers;     /* optional, 312*N ints, caller sets -1: the joint
+                                   count of every scored path */
+} hcJointGate;                  /* 16 bytes */
+
+/* hc_trifocal_2op1p_30x30_track_abort_grouped (T >= 1) with the scoring and the
+   gate replaced; the dequeue order, the skip at dequeue when group_found[t] is
+   set, inflight_stop, the carry-over of a preset flag, group_found_ticks and
+   batch_index[b] = b on a pass are as there.
+   Scored: a path that converged and passes the pose-support candidate filter,
+   |Im x[24..29]| < 1e-5 and Re x[0..7] >= 0 (not the abort kernels' filter over
+   x[18..29]).  Its pose and its per-edgel tests are those of the pose-support
+   calls, so its counts (cJ, c21, c31) over groups[t]'s E edgels are the ones
+   hc_trifocal_pose_support_joint_grouped reports for that path on the same
+   scene, bit for bit.  It passes iff
+       (double)cJ >= (double)min_joint_ratio * (double)E.
+   stats[b].inliers21 / inliers31 are c21 / c31 of a scored path, 0 otherwise;
+   gate->joint_inliers[b] is cJ of a scored path and is not written otherwise.
+   gate == NULL or a ratio that is <= 0, NaN or infinite returns
+   HC_ERROR_INVALID_VALUE, as does whatever the grouped call rejects, before
+   anything is enqueued. */
+hcStatus hc_trifocal_2op1p_30x30_track_abort_gated(const hcTrackArgs *args, const hcGroupedAbortArgs *g,
+                                                   const hcJointGate *gate, void *workspace,
+                                                   size_t workspace_bytes, hcStream stream);
+
 /* The cross-process early-stop flag of hcAbortArgs::peer_found.  It lives in
    the creating process's device memory, allocated uncached
    (hipExtMallocWithFlags(hipDeviceMallocUncached): coherent across devices

@@ -19,6 +19,10 @@
 #   stress    time slicing under concurrent streams (scripts/slice_stress.py: 4 cold, 4 warm, 8 cold)
 #   multi     T sequential single-triplet runs against one grouped run (scripts/multi_triplet.py) -> TAG_multi.json
 #   joint     per-view against joint pose selection, config-5 protocol (scripts/joint_pose.py [TRIALS [REPS]]) -> TAG_joint.json
+#   gated     the gated abort launch against plain tracking + joint selection, config-5 protocol
+#             (scripts/gated_stop.py [TRIALS]) -> TAG_gated.json
+#   gated_ab  the launches that existed before the gated one (scripts/gated_stop.py --existing) on builds
+#             NAME=lib/libX.so ... (package-relative), alternately, 2 rounds -> TAG_gated_existing.jsonl
 #   validate  tests,luwork,bench,profile,datasets
 # Extra environment: BENCH_ARGS (bench step), AB_ROUNDS (ab step, default 3), AB_ARGS (more ab_track.py options), TTFP_ARGS (ttfp_ab step,
 # e.g. "--dataset 10").
@@ -97,6 +101,17 @@ for k,v in sorted(g.items()): print(k, v)" ;;
     phases) HC_TRIFOCAL_LIB=$L/libhc_trifocal_phases.so run phases 300 python scripts/diag_phases.py > $O/${T}_phases.json; rc=$?; cat $O/${T}_phases.json ;;
     multi) run multi 300 python scripts/multi_triplet.py "$@" > $O/${T}_multi.json; rc=$?; cat $O/${T}_multi.json ;;
     joint) run joint 600 python scripts/joint_pose.py "$@" > $O/${T}_joint.json; rc=$?; cat $O/${T}_joint.json ;;
+    gated) run gated 900 python scripts/gated_stop.py "$@" > $O/${T}_gated.json; rc=$?; tail -c 600 $O/${T}_gated.json ;;
+    gated_ab)
+      rc=0
+      for rd in 0 1; do
+        for kv in "$@"; do
+          HC_TRIFOCAL_LIB=$P/${kv#*=} run existing_${kv%%=*} 200 python scripts/gated_stop.py --existing > $O/${T}_tmp.json; rc=$?
+          [ $rc -eq 0 ] || break 2
+          python -c "import json; d=json.load(open('$O/${T}_tmp.json')); d.update(build='${kv%%=*}', round=$rd); print(json.dumps(d))" >> $O/${T}_gated_existing.jsonl
+        done
+      done
+      [ -f $O/${T}_gated_existing.jsonl ] && cat $O/${T}_gated_existing.jsonl ;;
     stress)
       run stress4 300 python scripts/slice_stress.py $O/${T}_stress4.jsonl 4 4 > /dev/null 2>&1; rc=$?
       [ $rc -eq 0 ] && { run stress4w 300 python scripts/slice_stress.py $O/${T}_stress4w.jsonl 4 4 --warm-streams > /dev/null 2>&1; rc=$?; }

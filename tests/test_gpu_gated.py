@@ -1,0 +1,236 @@
+"""GPU tests of the gated abort launch (hc_trifocal_2op1p_30x30_track_abort_gated):
+grouped abort tracking whose stop rule is the joint inlier support of a path on
+its own triplet, (double)cJ >= (double)min_joint_ratio * (double)E.
+
+Expected values come from code that is pinned to the oracle elsewhere in the
+suite: the plain track() of the same samples for every tracked path,
+pose.pose_support_joint_grouped on those plain tracks for every count (the
+gated kernel scores with the same device functions, so the counts must agree
+bit for bit), and the committed golden pose_joint_noisy1px_N100.npz.  The
+verdict of every path is recomputed here in double from those counts.
+
+Facts of the inputs (CPU oracle / the golden): the noisy fixture (dataset 000,
+sigma = 1 px, seed 20250215, srand(0), 100 samples) has 31 candidates, the best
+one path 23612 (sample 75) with 1133 of 5117 joint inliers, the next 697; on
+clean data path 104 of dataset 000 has E of E joint inliers for any prefix of
+the edgels, the other candidates of 000's first 8 samples at most 195 of 5117,
+and no candidate of dataset 099's 128 samples reaches half its edgels.
+"""
+import os
+
+import numpy as np
+import pytest
+
+from conftest import same
+
+pytestmark = pytest.mark.gpu
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+NEVER = 2.0      # a ratio > 1 never passes: every path is tracked and scored
+
+
+class Case:
+    """A TripletBatch, its device copy, the plain track() of all its samples
+    and the grouped joint pose support of those plain tracks (n x 3 counts)."""
+
+    def __init__(self, problem, tracker, ds, samples, interleave=False, edgel_counts=None, plain=None):
+        from trifocal_pose_estimation_using_improved_gpuhc_amd import pose
+        from trifocal_pose_estimation_using_improved_gpuhc_amd.multi import TripletBatch
+        self.batch = TripletBatch(problem, ds, seeds=0, samples_per_triplet=samples, interleave=interleave,
+                                  edgel_counts=edgel_counts)
+        self.dev = self.batch.to(tracker.device)
+        self.plain_dev = plain if plain is not None else tracker.track(self.batch.target, self.batch.diff)
+        self.plain = self.plain_dev.host()
+        self.counts, _ = pose.pose_support_joint_grouped(self.plain_dev.tracks, self.plain_dev.converge, self.dev)
+        for v in list(self.plain.values()) + [self.counts]:
+            v.setflags(write=False)
+        self.E_of_path = np.repeat(self.batch.edgel_counts[self.batch.sample_group], 312)
+
+
+@pytest.fixture(scope="module")
+def noisy0(ransac0):
+    from trifocal_pose_estimation_using_improved_gpuhc_amd import synthcurves
+    d = synthcurves.noisy(ransac0, 1.0, 20250215)
+    d.locations.setflags(write=False)
+    return d
+
+
+@pytest.fixture(scope="module")
+def golden():
+    return np.load(os.path.join(GOLDEN, "pose_joint_noisy1px_N100.npz"))
+
+
+@pytest.fixture(scope="module")
+def noisy_case(problem, tracker, noisy0):   # tests 1 and 2
+    return Case(problem, tracker, [noisy0], 100)
+
+
+@pytest.fixture(scope="module")
+def mixed_case(problem, tracker):   # test 3
+    from trifocal_pose_estimation_using_improved_gpuhc_amd import load_ransac_data
+    return Case(problem, tracker, [load_ransac_data(0), load_ransac_data(99)], 128, interleave=True)
+
+
+@pytest.fixture(scope="module")
+def clean8(problem, tracker, ransac0):   # test 4: the plain tracks shared by every E
+    return Case(problem, tracker, [ransac0], 8)
+
+
+def _passes(counts, E, gate):
+    """The gate in double, as the kernel states it (the ratio is a float32)."""
+    return counts.astype(np.float64) >= float(np.float32(gate)) * E.astype(np.float64)
+
+
+def _check_gated(r, case, problem, gate, found, found_ids, all_tracked=(), none_tracked=(), tick_groups=None):
+    """The checks of a gated result r (host dict) of case's batch -- those of
+    an abort-mode result, with the pose-support counts in the oracle's place.
+    found: the expected flags; found_ids: the expected set of batch_index
+    entries (None: derived from the counts alone); all_tracked / none_tracked:
+    groups whose paths must all / must none be tracked; tick_groups: the groups
+    that found in this launch (default: those flagged).  Returns `tracked`."""
+    b, plain, ref = case.batch, case.plain, case.counts
+    n = b.num_samples * 312
+    assert r["found"].tolist() == found
+    ids = np.nonzero(r["batch_index"] >= 0)[0]
+    assert (r["batch_index"][ids] == ids).all()
+    st = r["stats"]
+    ji = r["joint_inliers"]
+    assert ji.shape == (n,) and ji.dtype == np.int32
+    tracked = st["steps"] > 0     # every path of these inputs takes >= 13 steps
+    group_of_path = np.repeat(b.sample_group, 312)
+    tick_groups = [t for t, f in enumerate(found) if f] if tick_groups is None else tick_groups
+    # the passing paths are exactly the tracked paths whose joint count meets the gate
+    scored = tracked & (ref[:, 0] >= 0)
+    expect = np.nonzero(scored & _passes(ref[:, 0], case.E_of_path, gate))[0]
+    assert ids.tolist() == expect.tolist()
+    if found_ids is not None:
+        assert set(ids.tolist()) == set(found_ids)
+    assert set(group_of_path[ids].tolist()) == set(tick_groups)
+    for p in ids:
+        assert tracked[p] and r["converge"][p] == 1 and ji[p] == ref[p, 0]
+    # every tracked path is the plain launch's path of the same batch id, and
+    # carries the pose-support counts of that path
+    assert (r["converge"][tracked] == plain["converge"][tracked]).all()
+    assert (r["infinity"][tracked] == plain["infinity"][tracked]).all()
+    assert (st["steps"][tracked] == plain["stats"]["steps"][tracked]).all()
+    assert (st["corrections"][tracked] == plain["stats"]["corrections"][tracked]).all()
+    assert same(r["tracks"][tracked, :30], plain["tracks"][tracked, :30]).all()
+    assert np.array_equal(ji[tracked], ref[tracked, 0])            # -1 where not scored
+    assert np.array_equal(st["inliers21"][tracked], np.maximum(ref[tracked, 1], 0))
+    assert np.array_equal(st["inliers31"][tracked], np.maximum(ref[tracked, 2], 0))
+    # every other path: conv 0, zero stats, the start solution, no count
+    un = ~tracked
+    assert (r["converge"][un] == 0).all() and (r["infinity"][un] == 0).all()
+    for k in ("steps", "corrections", "inliers21", "inliers31"):
+        assert (st[k][un] == 0).all(), k
+    assert (ji[un] == -1).all()
+    start = np.tile(problem.start_sols[None], (b.num_samples, 1, 1, 1)).reshape(n, 31, 2)
+    assert np.array_equal(r["tracks"][un], start[un])
+    for t in all_tracked:
+        assert tracked[b.path_index(t)].all(), f"group {t}: {(~tracked[b.path_index(t)]).sum()} paths not tracked"
+    for t in none_tracked:
+        assert not tracked[b.path_index(t)].any(), f"group {t}: {tracked[b.path_index(t)].sum()} paths tracked"
+    ticks = r["found_ticks"]
+    assert [t for t in range(b.num_groups) if ticks[t] != 0] == sorted(tick_groups)
+    return tracked
+
+
+def test_counts_nothing_fires(problem, tracker, noisy_case, golden):
+    """Test 1: the noisy fixture at a gate that never passes.  Every path is
+    tracked as the plain launch tracks it and scored as the pose support
+    scores it; the 31 candidates' counts are the golden's."""
+    c = noisy_case
+    r = tracker.track_grouped(c.dev, gate=NEVER).host()
+    tracked = _check_gated(r, c, problem, NEVER, [0], set(), all_tracked=(0,))
+    assert tracked.all() and tracked.shape == (31200,)
+    plain, st = c.plain, r["stats"]
+    assert same(r["tracks"][:, :30], plain["tracks"][:, :30]).all()
+    assert (r["converge"] == plain["converge"]).all() and (r["infinity"] == plain["infinity"]).all()
+    assert (st["steps"] == plain["stats"]["steps"]).all()
+    assert (st["corrections"] == plain["stats"]["corrections"]).all()
+    assert np.array_equal(r["joint_inliers"], c.counts[:, 0])
+    sc = c.counts[:, 0] >= 0
+    assert np.array_equal(st["inliers21"][sc], c.counts[sc, 1]) and np.array_equal(st["inliers31"][sc], c.counts[sc, 2])
+    assert (st["inliers21"][~sc] == 0).all() and (st["inliers31"][~sc] == 0).all()
+    ids = golden["cand_ids"]
+    assert np.nonzero(r["joint_inliers"] >= 0)[0].tolist() == ids.tolist() and len(ids) == 31
+    got = np.stack([r["joint_inliers"][ids], st["inliers21"][ids], st["inliers31"][ids]], axis=1)
+    assert np.array_equal(got, golden["counts"])
+    assert r["found"].tolist() == [0] and (r["batch_index"] == -1).all() and (r["found_ticks"] == 0).all()
+
+
+def test_fires_where_it_should(problem, tracker, noisy_case, golden):
+    """Test 2: gate 0.20 needs 1024 of 5117 joint inliers: the golden's winner
+    (1133, in sample 75) is the only candidate to pass.  Gate 0.23 needs 1177:
+    nothing fires.  The pair brackets the comparison."""
+    c = noisy_case
+    path = int(golden["path"])
+    assert path // 312 == 75 and golden["inliers"][0] == 1133
+    assert (golden["counts"][:, 0] >= 1024).sum() == 1
+    r = tracker.track_grouped(c.dev, gate=0.20).host()
+    tracked = _check_gated(r, c, problem, 0.20, [1], {path})
+    assert r["found_ticks"][0] != 0 and r["joint_inliers"][path] == 1133
+    assert tracked[:76 * 312].all()          # sample-major: nothing before the find is skipped
+    r = tracker.track_grouped(c.dev, gate=0.23).host()
+    tracked = _check_gated(r, c, problem, 0.23, [0], set(), all_tracked=(0,))
+    assert tracked.all() and (r["batch_index"] == -1).all() and r["joint_inliers"][path] == 1133
+
+
+@pytest.mark.parametrize("inflight_stop", [0, 1])
+def test_stops_per_group(problem, tracker, mixed_case, inflight_stop):
+    """Test 3: clean 000 and 099, 128 samples each, alternating, gate 0.5: 000
+    finds at path 104 (5117 of 5117), its later paths are skipped; 099 never
+    passes and all its 39 936 paths are tracked."""
+    c = mixed_case
+    assert c.batch.sample_group.tolist() == [s % 2 for s in range(256)]
+    assert c.counts[104].tolist() == [5117, 5117, 5117]
+    r = tracker.track_grouped(c.dev, inflight_stop=bool(inflight_stop), gate=0.5).host()
+    tracked = _check_gated(r, c, problem, 0.5, [1, 0], None, all_tracked=(1,))
+    assert r["batch_index"][104] == 104 and r["joint_inliers"][104] == 5117
+    assert tracked[c.batch.path_index(1)].sum() == 39936
+    assert (~tracked[c.batch.path_index(0)]).any(), "no path of the finding group was skipped"
+    start, _, hz = tracker.read_timestamps()
+    assert start > 0 and hz > 0 and r["found_ticks"][0] >= start
+
+
+def test_carry_over(problem, tracker, mixed_case):
+    """found = [1, 0] on entry (an earlier launch's find): no path of group 0
+    is tracked, group 1 behaves as in a fresh launch."""
+    r = tracker.track_grouped(mixed_case.dev, found=[1, 0], gate=0.5).host()
+    _check_gated(r, mixed_case, problem, 0.5, [1, 0], set(), all_tracked=(1,), none_tracked=(0,), tick_groups=[])
+
+
+@pytest.mark.parametrize("E", [1, 31, 32, 33, 65, 2049])
+def test_edgel_loop_tails(problem, tracker, ransac0, clean8, E):
+    """Test 4: the scoring set truncated to E edgels, one below, at and above
+    the half-wave width and the 2048-edgel chunk: the counts are the pose
+    support's on the same truncated scene, and path 104 counts E of E, so a
+    dropped last edgel or a read past E changes a number."""
+    c = Case(problem, tracker, [ransac0], 8, edgel_counts=[E], plain=clean8.plain_dev)
+    assert np.array_equal(c.batch.target, clean8.batch.target) and np.array_equal(c.batch.diff, clean8.batch.diff)
+    assert c.counts[104].tolist() == [E, E, E]
+    r = tracker.track_grouped(c.dev, gate=NEVER).host()
+    tracked = _check_gated(r, c, problem, NEVER, [0], set(), all_tracked=(0,))
+    assert tracked.all() and r["joint_inliers"][104] == E
+    assert (r["stats"]["inliers21"][104], r["stats"]["inliers31"][104]) == (E, E)
+    if E == 33:
+        r = tracker.track_grouped(c.dev, gate=1.0).host()
+        _check_gated(r, c, problem, 1.0, [1], None)
+        assert r["batch_index"][104] == 104
+
+
+def test_mixed_truncation_noisy(problem, tracker, noisy0, golden):
+    """Test 5: two triplets over the noisy fixture's data, scored on its first
+    777 edgels and on all of them, 16 samples each (the golden lists candidates
+    in samples 5, 8, 11, 14 and 15): per-group counts equal the grouped pose
+    support."""
+    assert len(set((golden["cand_ids"] // 312).tolist()) & set(range(16))) >= 4
+    c = Case(problem, tracker, [noisy0, noisy0], 16, edgel_counts=[777, None])
+    assert c.batch.edgel_counts.tolist() == [777, 5117]
+    sc = c.counts[:, 0] >= 0
+    assert sc[:16 * 312].sum() >= 4 and np.array_equal(sc[:16 * 312], sc[16 * 312:])
+    assert (c.counts[:16 * 312][sc[:16 * 312]] != c.counts[16 * 312:][sc[16 * 312:]]).any()
+    r = tracker.track_grouped(c.dev, gate=NEVER).host()
+    tracked = _check_gated(r, c, problem, NEVER, [0, 0], set(), all_tracked=(0, 1))
+    assert tracked.all()
+    assert r["joint_inliers"][:16 * 312].max() <= 777

@@ -104,6 +104,13 @@ class hcGroupedAbortArgs(C.Structure):
                 ("inflight_stop", C.c_int)]
 
 
+class hcJointGate(C.Structure):
+    """The stop rule of hc_trifocal_2op1p_30x30_track_abort_gated: 16 bytes."""
+    _fields_ = [("min_joint_ratio", C.c_float),
+                ("pad", C.c_int32),
+                ("joint_inliers", C.c_void_p)]
+
+
 class hcIpcHandle(C.Structure):
     _fields_ = [("reserved", C.c_ubyte * 64)]
 
@@ -181,6 +188,13 @@ def lib() -> C.CDLL:
             L.hc_trifocal_pose_support_grouped.restype = C.c_int
             L.hc_trifocal_pose_support_grouped.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                                            C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        # the gated abort launch (bound where present: A/B runs load earlier builds)
+        if hasattr(L, "hc_trifocal_2op1p_30x30_track_abort_gated"):
+            L.hc_trifocal_2op1p_30x30_track_abort_gated.restype = C.c_int
+            L.hc_trifocal_2op1p_30x30_track_abort_gated.argtypes = [C.POINTER(hcTrackArgs),
+                                                                    C.POINTER(hcGroupedAbortArgs),
+                                                                    C.POINTER(hcJointGate), C.c_void_p, C.c_size_t,
+                                                                    C.c_void_p]
         L.hc_pose_merge.restype = None
         L.hc_pose_merge.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(hcPoseSelection)]
         L.hc_trifocal_pose_support_joint.restype = C.c_int
@@ -245,6 +259,7 @@ DECLARED_SYMBOLS = (
     "hc_add_pixel_noise", "hc_write_triplet_edgels",
     "hc_trifocal_pose_support_joint", "hc_trifocal_pose_support_joint_grouped", "hc_trifocal_pose_inlier_mask",
     "hc_pose_merge_joint",
+    "hc_trifocal_2op1p_30x30_track_abort_gated",
 )
 
 

@@ -15,6 +15,7 @@
 // paths on the device and raises an agent-scope flag.
 #include "hc_device.hpp"
 #include "hc_lu.hpp"
+#include "hc_pose_device.hpp"
 #include "../../include/hc_trifocal.h"
 #include "../../include/hc_trifocal_testing.h"
 
@@ -174,6 +175,9 @@ struct KArgs {
     const int32_t *sample_group;
     unsigned *group_found;
     unsigned long long *group_ticks;   // or null
+    // gated abort mode (hcJointGate; k_track_gated only)
+    float gate_ratio;
+    int32_t *joint_inliers;            // or null
 };
 // rq layout: counters zeroed by k_prep_tables every launch; meta: the launch
 // epoch, a magic word and the ring entries already cleared (persist)
@@ -842,6 +846,47 @@ __device__ __forceinline__ int2 score_half(const cf *sx, const float *edgels, in
     return make_int2(half_sum_i(c21), half_sum_i(c31));
 }
 
+// Gated abort launches (k_track_gated): the pose-support counts of one half's
+// converged candidate -- make_pose and the per-edgel test of hc_pose_device.hpp,
+// so the three counts are those of k_pose_support<true, *> for the same track
+// and scene (integer sums: the order of summation is free).  32 lanes over the
+// triplet's edgels.  Both views of an edgel need 24 pose values; held live they
+// would set the kernel's register allocation (as score_half's note says), so
+// the edgels go in chunks of 2048, 64 per lane: a first pass keeps the lane's
+// view-1-2 verdicts as bits, a second one the view-1-3 verdicts, each from its
+// own evaluation of the pose (12 live values); the joint verdicts are the AND.
+struct JointCounts { int cJ, c21, c31; };
+__device__ __forceinline__ JointCounts score_joint_half(const cf *sx, const Scene sc, int r) {
+    constexpr unsigned CHUNK = 64u * 32u;
+    const unsigned E = sc.E > 0 ? (unsigned)sc.E : 0u;
+    int cJ = 0, c21 = 0, c31 = 0;
+    for (unsigned base = 0u; base < E; base += CHUNK) {
+        unsigned long long m21 = 0ull, m31 = 0ull;
+        {
+            const cf *s1 = sx;
+            asm volatile("" : "+v"(s1));   // evaluated here, per chunk and pass: not kept live
+            Pose P;
+            make_pose(s1, P);
+            unsigned e = base + (unsigned)r;
+            for (int j = 0; j < 64 && e < E; j++, e += 32u)
+                m21 |= (unsigned long long)(edgel_view<0>(sc, (int)e, P.R, P.t) ? 1u : 0u) << j;
+        }
+        {
+            const cf *s2 = sx;
+            asm volatile("" : "+v"(s2));
+            Pose P;
+            make_pose(s2, P);
+            unsigned e = base + (unsigned)r;
+            for (int j = 0; j < 64 && e < E; j++, e += 32u)
+                m31 |= (unsigned long long)(edgel_view<1>(sc, (int)e, P.R + 9, P.t + 3) ? 1u : 0u) << j;
+        }
+        c21 += __builtin_popcountll(m21);
+        c31 += __builtin_popcountll(m31);
+        cJ += __builtin_popcountll(m21 & m31);
+    }
+    return JointCounts{half_sum_i(cJ), half_sum_i(c21), half_sum_i(c31)};
+}
+
 #ifdef HC_DIAG_TIMES
 // diagnostic build: [0] first wave start, [1] last wave exit (s_memrealtime),
 // [2] summed wave lifetimes, [3] waves
@@ -879,7 +924,7 @@ __device__ unsigned long long g_diag_phase[13];
 typedef uint32_t T_hxd_t[HX_NSLOT / 2][32];
 template <bool ABORT, int MINW, bool GTAB, bool ARCH = false, bool LUS = true>
 __global__ void __launch_bounds__(WG_THREADS, MINW) k_track(KArgs a) {
-    constexpr bool GROUPED = false;   // (k_track_grouped below)
+    constexpr bool GROUPED = false, GATED = false;   // (k_track_grouped, k_track_gated below)
     // LU (hc_lu.hpp): the abort kernel's time to the first pose is a lone
     // path's latency, so it runs the latency mode (one LDS round trip per pivot
     // step, in batches of HC_LU_LATB_COLS columns); the tracking kernel the
@@ -905,7 +950,7 @@ __global__ void __launch_bounds__(WG_THREADS, MINW) k_track(KArgs a) {
 #endif
 template <bool LUS>
 __global__ void __launch_bounds__(WG_THREADS, HC_SMALL_MINW) k_track_small(KArgs a) {
-    constexpr bool ABORT = false, GTAB = true, ARCH = false, GROUPED = false;
+    constexpr bool ABORT = false, GTAB = true, ARCH = false, GROUPED = false, GATED = false;
     constexpr int LUCH = LU_CHUNK;
     constexpr int LULAT = HC_SMALL_LAT;
 #include "hc_track_body.inc"
@@ -926,7 +971,20 @@ __global__ void __launch_bounds__(WG_THREADS, HC_SMALL_MINW) k_track_small(KArgs
 #endif
 template <bool LUS>
 __global__ void __launch_bounds__(WG_THREADS, HC_ABORT_MINW) k_track_grouped(KArgs a) {
-    constexpr bool ABORT = true, GTAB = HC_ABORT_GTAB, ARCH = false, GROUPED = true;
+    constexpr bool ABORT = true, GTAB = HC_ABORT_GTAB, ARCH = false, GROUPED = true, GATED = false;
+    constexpr int LUCH = LU_CHUNK;
+    constexpr int LULAT = HC_LU_LATB_COLS;
+#include "hc_track_body.inc"
+}
+
+// Gated abort launches (hcJointGate): k_track_grouped's configuration and body
+// with GATED on, which replaces the scoring block alone: the candidate filter
+// and the counts are the pose-support ones (score_joint_half), and a triplet's
+// flag is raised by the joint count against KArgs::gate_ratio.  Again a kernel
+// of its own, so the grouped instantiations keep their code.
+template <bool LUS>
+__global__ void __launch_bounds__(WG_THREADS, HC_ABORT_MINW) k_track_gated(KArgs a) {
+    constexpr bool ABORT = true, GTAB = HC_ABORT_GTAB, ARCH = false, GROUPED = true, GATED = true;
     constexpr int LUCH = LU_CHUNK;
     constexpr int LULAT = HC_LU_LATB_COLS;
 #include "hc_track_body.inc"
@@ -1082,9 +1140,11 @@ static int resident_wgs(const void *kernel) { return grid_for(INT_MAX, kernel); 
 
 static hcStatus launch_track(const hcTrackArgs *t, const hcAbortArgs *ab, void *workspace, size_t wsb,
                              hcStream stream, bool abort_mode, bool truncate = true, bool explicit_rk = false,
-                             const hcGroupedAbortArgs *gr = nullptr) {
+                             const hcGroupedAbortArgs *gr = nullptr, const hcJointGate *jg = nullptr) {
     // gr: the grouped (multi-triplet) abort launch; abort_mode is set, ab is null
+    // jg: with gr, the gated launch (validated by its entry point)
     const bool grouped = gr != nullptr;
+    const bool gated = grouped && jg != nullptr;
     if (!t || t->sub_ransac_iters < 0) return HC_ERROR_INVALID_VALUE;
     if (grouped && (gr->num_groups < 1 || !gr->groups || !gr->sample_group || !gr->group_found ||
                     !gr->trifocal_sols_batch_index))
@@ -1161,13 +1221,15 @@ static hcStatus launch_track(const hcTrackArgs *t, const hcAbortArgs *ab, void *
 #ifndef HC_ABORT_MINW
 #define HC_ABORT_MINW 4
 #endif
-    const void *kern = grouped      ? (const void *)k_track_grouped<true>
+    const void *kern = gated        ? (const void *)k_track_gated<true>
+                       : grouped    ? (const void *)k_track_grouped<true>
                        : abort_mode ? (const void *)k_track<true, HC_ABORT_MINW, HC_ABORT_GTAB>
                        : archived ? (const void *)k_track<false, 5, true, true>
                                   : (const void *)k_track<false, 5, true>;
     // the structure-agnostic twin, enqueued after it: exactly one of the two
     // tracks (EvalTables::lu_struct), the other returns at its first load
-    const void *kern_any = grouped      ? (const void *)k_track_grouped<false>
+    const void *kern_any = gated        ? (const void *)k_track_gated<false>
+                           : grouped    ? (const void *)k_track_grouped<false>
                            : abort_mode ? (const void *)k_track<true, HC_ABORT_MINW, HC_ABORT_GTAB, false, false>
                            : archived ? (const void *)k_track<false, 5, true, true, false>
                                       : (const void *)k_track<false, 5, true, false, false>;
@@ -1196,6 +1258,10 @@ static hcStatus launch_track(const hcTrackArgs *t, const hcAbortArgs *ab, void *
         k.sample_group = gr->sample_group;
         k.group_found = gr->group_found;
         k.group_ticks = (unsigned long long *)gr->group_found_ticks;
+        if (gated) {
+            k.gate_ratio = jg->min_joint_ratio;
+            k.joint_inliers = jg->joint_inliers;
+        }
     } else if (abort_mode) {
         k.num_edgels = ab->num_triplet_edgels;
         k.inflight_stop = ab->inflight_stop ? 1 : 0;
@@ -1296,6 +1362,15 @@ hcStatus hc_trifocal_2op1p_30x30_track_abort_grouped(const hcTrackArgs *args, co
                                                      void *workspace, size_t workspace_bytes, hcStream stream) {
     if (!g) return HC_ERROR_INVALID_VALUE;
     return hc::launch_track(args, nullptr, workspace, workspace_bytes, stream, true, true, false, g);
+}
+
+hcStatus hc_trifocal_2op1p_30x30_track_abort_gated(const hcTrackArgs *args, const hcGroupedAbortArgs *g,
+                                                   const hcJointGate *gate, void *workspace,
+                                                   size_t workspace_bytes, hcStream stream) {
+    if (!g || !gate) return HC_ERROR_INVALID_VALUE;
+    // > 0 and finite (the comparison is false for NaN)
+    if (!(gate->min_joint_ratio > 0.0f) || gate->min_joint_ratio > 3.402823466e+38f) return HC_ERROR_INVALID_VALUE;
+    return hc::launch_track(args, nullptr, workspace, workspace_bytes, stream, true, true, false, g, gate);
 }
 
 hcStatus hc_trifocal_2op1p_30x30_track_ph_codeopt(const hcTrackArgs *args, void *workspace, size_t workspace_bytes,

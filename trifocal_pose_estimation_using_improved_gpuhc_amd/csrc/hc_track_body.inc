@@ -1,6 +1,7 @@
-// The body of the tracker kernels k_track, k_track_small and k_track_grouped (hc_kernels.hip),
-// included inside each: ABORT, GROUPED, GTAB, ARCH, LUS, LUCH and LULAT are their
-// template parameters or constants, `a` their argument block.
+// The body of the tracker kernels k_track, k_track_small, k_track_grouped and k_track_gated (hc_kernels.hip),
+// included inside each: ABORT, GROUPED, GATED, GTAB, ARCH, LUS, LUCH and LULAT are
+// their template parameters or constants, `a` their argument block.  GATED
+// (k_track_gated) replaces the scoring block of PH_FINISH and nothing else.
 // kernel_GPUHC_trifocal_pose_PH_CodeOpt_TrunPaths (..._TrunPaths.cu:45-290) and,
 // with ABORT, ..._TrunPaths_TrunRANSAC (..._TrunRANSAC.cu:45-327).
     constexpr bool LUSTRUCT = LUS;
@@ -87,38 +88,61 @@
                 if (ABORT && conv) {                                          // TrunRANSAC.cu:312-322
                     if (rl) S.x[r] = x;
                     wave_lds_sync();
-                    const unsigned long long im = __ballot(r >= 18 && rl && (double)__builtin_fabsf(x.y) < 1e-5);
-                    if constexpr (GROUPED) {
-                        if (((unsigned)(im >> hb) & 0x3FFC0000u) == 0x3FFC0000u) {
-                            // the path's own triplet: its scoring set, its K, its flag
+                    if constexpr (GATED) {
+                        // the stop rule of the gated launch: the pose-support candidate filter
+                        // and counts (hc_pose_device.hpp) on the path's own triplet, the gate on
+                        // the joint count
+                        if (is_candidate_half(x, r, hb)) {
                             const int grp = a.sample_group[smp_loaded];
                             const hcTripletGroup g = a.groups[grp];
-                            const int2 c = score_half(S.x, g.locations, g.num_edgels, g.K, r);
-                            in21 = c.x;
-                            in31 = c.y;
-                            const float r21 = (float)in21 / (float)g.num_edgels, r31 = (float)in31 / (float)g.num_edgels;
-                            if ((double)r21 >= 0.90 && (double)r31 >= 0.90 && r == 0) {
-                                __hip_atomic_store(&a.group_found[grp], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                                a.batch_index[b] = b;
-                                if (a.group_ticks)
-                                    atomicCAS(&a.group_ticks[grp], 0ull,
-                                              (unsigned long long)__builtin_amdgcn_s_memrealtime());
+                            const JointCounts c = score_joint_half(S.x, load_scene(g.num_edgels, g.locations, g.K), r);
+                            in21 = c.c21;
+                            in31 = c.c31;
+                            if (r == 0) {
+                                if (a.joint_inliers) a.joint_inliers[b] = c.cJ;
+                                if ((double)c.cJ >= (double)a.gate_ratio * (double)g.num_edgels) {
+                                    __hip_atomic_store(&a.group_found[grp], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                                    a.batch_index[b] = b;
+                                    if (a.group_ticks)
+                                        atomicCAS(&a.group_ticks[grp], 0ull,
+                                                  (unsigned long long)__builtin_amdgcn_s_memrealtime());
+                                }
                             }
                         }
-                    } else if (((unsigned)(im >> hb) & 0x3FFC0000u) == 0x3FFC0000u) {   // eval.cuh:46-53
-                        const int2 c = score_half(S.x, a.edgels, a.num_edgels, a.K, r);
-                        in21 = c.x;
-                        in31 = c.y;
-                        const float r21 = (float)in21 / (float)a.num_edgels, r31 = (float)in31 / (float)a.num_edgels;
-                        if ((double)r21 >= 0.90 && (double)r31 >= 0.90 && r == 0) {   // eval.cuh:241-246
-                            __hip_atomic_store(&ws->found, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            a.found_flag[0] = 1;
-                            // the other GPUs' launches poll this (system scope: written
-                            // through to the owner's memory over xGMI)
-                            if (a.peer_found)
-                                __hip_atomic_store(a.peer_found, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                            a.batch_index[b] = b;
-                            atomicCAS(&ws->t_found, 0ull, (unsigned long long)__builtin_amdgcn_s_memrealtime());
+                    } else {
+                        const unsigned long long im = __ballot(r >= 18 && rl && (double)__builtin_fabsf(x.y) < 1e-5);
+                        if constexpr (GROUPED) {
+                            if (((unsigned)(im >> hb) & 0x3FFC0000u) == 0x3FFC0000u) {
+                                // the path's own triplet: its scoring set, its K, its flag
+                                const int grp = a.sample_group[smp_loaded];
+                                const hcTripletGroup g = a.groups[grp];
+                                const int2 c = score_half(S.x, g.locations, g.num_edgels, g.K, r);
+                                in21 = c.x;
+                                in31 = c.y;
+                                const float r21 = (float)in21 / (float)g.num_edgels, r31 = (float)in31 / (float)g.num_edgels;
+                                if ((double)r21 >= 0.90 && (double)r31 >= 0.90 && r == 0) {
+                                    __hip_atomic_store(&a.group_found[grp], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                                    a.batch_index[b] = b;
+                                    if (a.group_ticks)
+                                        atomicCAS(&a.group_ticks[grp], 0ull,
+                                                  (unsigned long long)__builtin_amdgcn_s_memrealtime());
+                                }
+                            }
+                        } else if (((unsigned)(im >> hb) & 0x3FFC0000u) == 0x3FFC0000u) {   // eval.cuh:46-53
+                            const int2 c = score_half(S.x, a.edgels, a.num_edgels, a.K, r);
+                            in21 = c.x;
+                            in31 = c.y;
+                            const float r21 = (float)in21 / (float)a.num_edgels, r31 = (float)in31 / (float)a.num_edgels;
+                            if ((double)r21 >= 0.90 && (double)r31 >= 0.90 && r == 0) {   // eval.cuh:241-246
+                                __hip_atomic_store(&ws->found, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                                a.found_flag[0] = 1;
+                                // the other GPUs' launches poll this (system scope: written
+                                // through to the owner's memory over xGMI)
+                                if (a.peer_found)
+                                    __hip_atomic_store(a.peer_found, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                                a.batch_index[b] = b;
+                                atomicCAS(&ws->t_found, 0ull, (unsigned long long)__builtin_amdgcn_s_memrealtime());
+                            }
                         }
                     }
                 }

@@ -39,6 +39,8 @@ class TrackResult:
     # grouped abort mode: found is the (T,) int32 per-triplet flag, found_ticks the (T,) int64
     # device clock of each triplet's first find (0: none)
     found_ticks: torch.Tensor | None = None
+    # gated abort mode: (312N,) int32, the joint inlier count of every scored path, -1 elsewhere
+    joint_inliers: torch.Tensor | None = None
 
     def host(self):
         out = dict(tracks=self.tracks.cpu().numpy(), converge=self.converge.cpu().numpy(),
@@ -52,7 +54,20 @@ class TrackResult:
         elif self.found is not None:
             out["found"] = bool(self.found.cpu().item())
             out["batch_index"] = self.batch_index.cpu().numpy()
+        if self.joint_inliers is not None:
+            out["joint_inliers"] = self.joint_inliers.cpu().numpy()
         return out
+
+
+def gate_ratio(gate) -> float:
+    """The min_joint_ratio of a gated launch from the caller's `gate`: a float
+    (Python or numpy), finite and positive; anything else raises HCError."""
+    if not isinstance(gate, (float, np.floating)):
+        raise _abi.HCError(f"gate must be a float ratio, not {type(gate).__name__}")
+    v = float(np.float32(gate))
+    if not (np.isfinite(v) and v > 0.0):
+        raise _abi.HCError(f"gate must be finite and positive as a float32 (got {gate!r})")
+    return v
 
 
 class DeviceTracker:
@@ -107,17 +122,22 @@ class DeviceTracker:
             r.batch_index.fill_(-1)
         if r.found_ticks is not None:
             r.found_ticks.zero_()
+        if r.joint_inliers is not None:
+            r.joint_inliers.fill_(-1)
 
-    def allocate_grouped(self, batch, stats: bool = True) -> TrackResult:
+    def allocate_grouped(self, batch, stats: bool = True, gate: bool = False) -> TrackResult:
         """Buffers of a grouped launch over batch (a multi.DeviceTripletBatch):
-        as allocate(abort=True), with one found word and one tick per triplet."""
+        as allocate(abort=True), with one found word and one tick per triplet;
+        gate: also the per-path joint inlier counts of a gated launch."""
         r = self.allocate(batch.num_samples, stats=stats, abort=True)
         r.found = torch.zeros(batch.num_groups, dtype=torch.int32, device=self.device)
         r.found_ticks = torch.zeros(batch.num_groups, dtype=torch.int64, device=self.device)
+        if gate:
+            r.joint_inliers = torch.full((batch.num_samples * 312,), -1, dtype=torch.int32, device=self.device)
         return r
 
     def launch_grouped(self, batch, r: TrackResult, stream: torch.cuda.Stream | None = None,
-                       workspace: torch.Tensor | None = None, inflight_stop: bool = False) -> None:
+                       workspace: torch.Tensor | None = None, inflight_stop: bool = False, gate=None) -> None:
         """Enqueue one grouped (multi-triplet) abort-mode run on `stream` (no
         synchronisation): hc_trifocal_2op1p_30x30_track_abort_grouped over all of
         batch's samples (a multi.DeviceTripletBatch) into r (allocate_grouped).
@@ -125,7 +145,16 @@ class DeviceTracker:
         the caller set it: r.found is in/out, the carry-over between launches --
         and scored on its own triplet's edgels; r.found_ticks[t] receives the
         device clock of triplet t's first find (read_timestamps gives the
-        launch's start).  inflight_stop as in launch()."""
+        launch's start).  inflight_stop as in launch().
+        gate (a float ratio, default None: the launch above, unchanged): the
+        stop rule is the joint inlier support instead
+        (hc_trifocal_2op1p_30x30_track_abort_gated): a converged path that
+        passes the pose-support candidate filter is scored on its own triplet's
+        E edgels with the pose-support test, and sets its triplet's flag iff its
+        joint count (edgels within 2 px in both views) is at least gate * E.
+        r.joint_inliers (allocate_grouped(gate=True)) receives every scored
+        path's joint count, r.stats its two per-view counts."""
+        ratio = None if gate is None else gate_ratio(gate)
         if batch.target.device != self.start_sols.device:
             raise _abi.HCError("the batch lives on another device")
         batch.check()   # group ids and edgel counts: the kernels do not validate them
@@ -133,6 +162,9 @@ class DeviceTracker:
         if n * 312 > r.tracks.shape[0] or r.found is None or r.found_ticks is None or r.found.numel() < T or \
                 r.found_ticks.numel() < T or r.found.dtype != torch.int32 or r.found_ticks.dtype != torch.int64:
             raise _abi.HCError("result buffers do not fit the batch (allocate_grouped)")
+        if ratio is not None and (r.joint_inliers is None or r.joint_inliers.numel() < n * 312 or
+                                  r.joint_inliers.dtype != torch.int32):
+            raise _abi.HCError("a gated launch needs r.joint_inliers (allocate_grouped(gate=True))")
         ws_t = workspace if workspace is not None else self.workspace
         if ws_t.numel() < self.ws_bytes:
             raise _abi.HCError("workspace too small")
@@ -159,24 +191,36 @@ class DeviceTracker:
         g.group_found_ticks = r.found_ticks.data_ptr()
         g.inflight_stop = 1 if inflight_stop else 0
         s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        if ratio is not None:
+            jg = _abi.hcJointGate()
+            jg.min_joint_ratio = ratio
+            jg.joint_inliers = r.joint_inliers.data_ptr()
+            _abi.check(self.L.hc_trifocal_2op1p_30x30_track_abort_gated(
+                C.byref(a), C.byref(g), C.byref(jg), C.c_void_p(ws_t.data_ptr()), self.ws_bytes,
+                C.c_void_p(s.cuda_stream)), "hc_trifocal_2op1p_30x30_track_abort_gated")
+            return
         _abi.check(self.L.hc_trifocal_2op1p_30x30_track_abort_grouped(
             C.byref(a), C.byref(g), C.c_void_p(ws_t.data_ptr()), self.ws_bytes, C.c_void_p(s.cuda_stream)),
             "hc_trifocal_2op1p_30x30_track_abort_grouped")
 
-    def track_grouped(self, batch, inflight_stop: bool = False, stats: bool = True, found=None) -> TrackResult:
+    def track_grouped(self, batch, inflight_stop: bool = False, stats: bool = True, found=None,
+                      gate=None) -> TrackResult:
         """Synchronous convenience wrapper of launch_grouped, as track(abort=True):
         batch is a multi.TripletBatch or its device copy.  found (optional, T
-        values): the triplets' flags on entry (a set one skips its triplet)."""
+        values): the triplets' flags on entry (a set one skips its triplet).
+        gate (a float ratio): the gated launch; the result carries joint_inliers."""
+        if gate is not None:
+            gate_ratio(gate)
         if not hasattr(batch, "groups"):
             batch = batch.to(self.device)
-        r = self.allocate_grouped(batch, stats=stats)
+        r = self.allocate_grouped(batch, stats=stats, gate=gate is not None)
         self.reset_tracks(r)
         if found is not None:
             f = np.ascontiguousarray(found, np.int32).reshape(-1)
             if f.shape[0] != batch.num_groups:
                 raise _abi.HCError("one initial flag per triplet")
             r.found.copy_(torch.from_numpy(f))
-        self.launch_grouped(batch, r, inflight_stop=inflight_stop)
+        self.launch_grouped(batch, r, inflight_stop=inflight_stop, gate=gate)
         torch.cuda.synchronize(self.device)
         self.workspace_status()
         return r
