@@ -1,0 +1,90 @@
+// The component kernels k_cgesv and k_eval.
+#pragma once
+
+#include "hc_layout.hpp"
+
+namespace hc {
+
+// The tracker's building blocks alone, from HBM operands (component ABI entry
+// points; parity tests of dev-cgesv-batched-small.cuh and the index evals).
+
+// LU: two systems per wave; a row's structural pattern is its non-zero entries
+__global__ void __launch_bounds__(WG_THREADS) k_cgesv(int n, const cf *__restrict__ A, const cf *__restrict__ B,
+                                                      cf *__restrict__ X) {
+    __shared__ LUBuf s_lu[2 * WAVES_PER_WG];
+    __shared__ __attribute__((aligned(16))) cf s_scr[2 * WAVES_PER_WG][LU_SCRATCH_CF];
+    const int lane = lane_id();
+    const int r = lane & 31;
+    const int sys = (blockIdx.x * WAVES_PER_WG + threadIdx.x / WAVE) * 2 + (lane >> 5);
+    const bool ok = sys < n && r < NV;
+    cf rA[NV];
+    uint32_t pat = 0;
+#pragma unroll
+    for (int c = 0; c < NV; c++) {
+        rA[c] = ok ? A[((size_t)sys * NV + r) * NV + c] : cmk(0.0f, 0.0f);
+        if (rA[c].x != 0.0f || rA[c].y != 0.0f) pat |= 1u << c;   // NaN counts as non-zero
+    }
+    const cf rB = ok ? B[(size_t)sys * NV + r] : cmk(0.0f, 0.0f);
+    LUBuf &LB = s_lu[(threadIdx.x / WAVE) * 2 + (lane >> 5)];
+    cf *scr = s_scr[(threadIdx.x / WAVE) * 2 + (lane >> 5)];
+    bool redo;
+    cf x = lu_solve<false>(rA, rB, lane, pat, LB, scr, redo, __ballot(sys < n));
+    if (__builtin_expect(redo, 0)) {   // solved again densely from the original system
+#pragma unroll
+        for (int c = 0; c < NV; c++) rA[c] = ok ? A[((size_t)sys * NV + r) * NV + c] : cmk(0.0f, 0.0f);
+        x = lu_solve<true>(rA, rB, lane, pat, LB, scr, redo);
+    }
+    if (ok) X[(size_t)sys * NV + r] = x;
+}
+
+
+// dH/dx, dH/dt, H at n points: one point per half-wave
+__global__ void __launch_bounds__(WG_THREADS) k_eval(int n, const Workspace *ws, const cf *__restrict__ X,
+                                                     const cf *__restrict__ P, const cf *__restrict__ D,
+                                                     cf *__restrict__ HX, cf *__restrict__ HT, cf *__restrict__ H) {
+    __shared__ uint32_t s_hx[HX_SLOT_CAP * 32];
+    __shared__ uint2 s_ht[HT_TERMS * 32];
+    __shared__ uint32_t s_hxd[HX_NSLOT / 2 * 32];
+    __shared__ SlotLDS s_slot[2 * WAVES_PER_WG];
+    const EvalTables *T = &ws->tab;
+    if (ws->status != 0u) return;
+    for (int i = threadIdx.x; i < HX_SLOT_CAP * 32; i += WG_THREADS) s_hx[i] = T->hx[i];   // padded table
+    for (int i = threadIdx.x; i < HT_TERMS * 32; i += WG_THREADS) s_ht[i] = T->ht[i];
+    for (int i = threadIdx.x; i < HX_NSLOT / 2 * 32; i += WG_THREADS) s_hxd[i] = (&T->hxd[0][0])[i];
+    {
+        float *z = reinterpret_cast<float *>(s_slot);
+        for (int i = threadIdx.x; i < (int)(sizeof(s_slot) / 4); i += WG_THREADS) z[i] = 0.0f;
+    }
+    __syncthreads();
+    const int lane = lane_id();
+    const int r = lane & 31;
+    const int sys = (blockIdx.x * WAVES_PER_WG + threadIdx.x / WAVE) * 2 + (lane >> 5);
+    SlotLDS &S = s_slot[(threadIdx.x / WAVE) * 2 + (lane >> 5)];
+    const bool ok = sys < n;
+    if (ok && r < 31) S.x[r] = X[(size_t)sys * 31 + r];
+    if (ok) {   // the point's p and d, staged for the prefix tables
+        S.ent[r] = P[(size_t)sys * NPP + r];
+        S.ent[NPP + r] = D[(size_t)sys * NPP + r];
+        if (r < NPP - 32) {
+            S.ent[r + 32] = P[(size_t)sys * NPP + r + 32];
+            S.ent[NPP + r + 32] = D[(size_t)sys * NPP + r + 32];
+        }
+    }
+    __shared__ uint32_t s_gm[GM_WORDS][32];
+    if (threadIdx.x < 32)
+        for (int q = 0; q < GM_WORDS; q++) s_gm[q][threadIdx.x] = T->gm[q][threadIdx.x];
+    __syncthreads();
+    build_prefix_rounds(S, r, &T->pre[0][0]);
+    cf rA[NV];
+    eval_hx(rA, s_hx, s_hxd, &s_gm[0][0], S, r);
+    const cf ht = eval_rhs<RHS_HT>(s_ht, S, r, true, rhs_masks(T));
+    const cf h = eval_rhs<RHS_H>(s_ht, S, r, false, rhs_masks(T));
+    if (ok && r < NV) {
+#pragma unroll
+        for (int c = 0; c < NV; c++) HX[((size_t)sys * NV + r) * NV + c] = rA[c];
+        HT[(size_t)sys * NV + r] = ht;
+        H[(size_t)sys * NV + r] = h;
+    }
+}
+
+}  // namespace hc

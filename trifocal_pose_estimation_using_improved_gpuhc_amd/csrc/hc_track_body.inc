@@ -1,7 +1,18 @@
-// The body of the tracker kernels k_track, k_track_small, k_track_grouped and k_track_gated (hc_kernels.hip),
+// The body of the tracker kernels k_track, k_track_small, k_track_grouped and k_track_gated (hc_track.hpp),
 // included inside each: ABORT, GROUPED, GATED, GTAB, ARCH, LUS, LUCH and LULAT are
 // their template parameters or constants, `a` their argument block.  GATED
 // (k_track_gated) replaces the scoring block of PH_FINISH and nothing else.
+// Included textually on purpose (DESIGN.md §3.2): a change here is a codegen
+// change of all twelve instantiations.  The other names it takes from its
+// surroundings:
+//   hc_layout.hpp  KArgs, Workspace, WG_THREADS, WAVES_PER_WG, PRIO_TENTHS,
+//                  path_of_queue_pos, SLICE_Q, SLICE_QBIG, SUSP_WORDS, RQ_*
+//   hc_ring.hpp    ld_rlx, ld_cf_rlx, st_u64_h, ld_u64_h, pack2, drain_stores,
+//                  ring_push, ring_pop, ring_pop_paired, ring_wait_ticks
+//   hc_score.hpp   score_half, JointCounts, score_joint_half
+//   hc_track.hpp   PH_*, T_hxd_t, HC_ABORT_PRIO_DIV, the HC_DIAG_* globals
+//   hc_device.hpp, hc_slot.hpp, hc_eval.hpp, hc_lu.hpp, hc_pose_device.hpp
+//                  the arithmetic, SlotLDS, the evaluations, lu_solve, scenes
 // kernel_GPUHC_trifocal_pose_PH_CodeOpt_TrunPaths (..._TrunPaths.cu:45-290) and,
 // with ABORT, ..._TrunPaths_TrunRANSAC (..._TrunRANSAC.cu:45-327).
     constexpr bool LUSTRUCT = LUS;
@@ -355,9 +366,6 @@
             // results, do not depend on it (only on when the pose flag is set).
             const int qp = (ph == PH_STAGE) ? qpos : 0x7FFFFFFF;
             const int m = min(__builtin_amdgcn_readlane(qp, 0), __builtin_amdgcn_readlane(qp, 32));
-#ifndef HC_ABORT_PRIO_DIV
-#define HC_ABORT_PRIO_DIV 16
-#endif
             const int lvl = (int)((long long)m * HC_ABORT_PRIO_DIV / a.num_paths);
             if (lvl <= 0) __builtin_amdgcn_s_setprio(3);
             else if (lvl == 1) __builtin_amdgcn_s_setprio(2);

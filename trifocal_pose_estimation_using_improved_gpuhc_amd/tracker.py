@@ -125,6 +125,34 @@ class DeviceTracker:
         if r.joint_inliers is not None:
             r.joint_inliers.fill_(-1)
 
+    def _workspace(self, workspace: torch.Tensor | None) -> torch.Tensor:
+        """A launch's workspace (default: the tracker's own), at least the minimum size."""
+        ws_t = workspace if workspace is not None else self.workspace
+        if ws_t.numel() < self.ws_bytes:
+            raise _abi.HCError("workspace too small")
+        return ws_t
+
+    def _track_args(self, r: TrackResult, target: torch.Tensor, diff: torch.Tensor, sample_offset: int,
+                    num_samples: int) -> _abi.hcTrackArgs:
+        """hcTrackArgs of samples [sample_offset, sample_offset + num_samples) of
+        target / diff, tracked into the matching rows of r."""
+        p0 = sample_offset * 312
+        a = _abi.hcTrackArgs()
+        a.sub_ransac_iters = num_samples
+        a.settings = self.settings
+        a.start_sols = self.start_sols.data_ptr()
+        a.start_sols_array = None
+        a.tracks = r.tracks[p0:].data_ptr()
+        a.track_array = None
+        a.start_params = self.start_params.data_ptr()
+        a.target_params = target[sample_offset:].data_ptr()
+        a.diff_params = diff[sample_offset:].data_ptr()
+        a.unified_index = self.unified.data_ptr()
+        a.converge = r.converge[p0:].data_ptr()
+        a.infinity = r.infinity[p0:].data_ptr()
+        a.stats = r.stats[p0:].data_ptr() if r.stats is not None else None
+        return a
+
     def allocate_grouped(self, batch, stats: bool = True, gate: bool = False) -> TrackResult:
         """Buffers of a grouped launch over batch (a multi.DeviceTripletBatch):
         as allocate(abort=True), with one found word and one tick per triplet;
@@ -165,23 +193,8 @@ class DeviceTracker:
         if ratio is not None and (r.joint_inliers is None or r.joint_inliers.numel() < n * 312 or
                                   r.joint_inliers.dtype != torch.int32):
             raise _abi.HCError("a gated launch needs r.joint_inliers (allocate_grouped(gate=True))")
-        ws_t = workspace if workspace is not None else self.workspace
-        if ws_t.numel() < self.ws_bytes:
-            raise _abi.HCError("workspace too small")
-        a = _abi.hcTrackArgs()
-        a.sub_ransac_iters = n
-        a.settings = self.settings
-        a.start_sols = self.start_sols.data_ptr()
-        a.start_sols_array = None
-        a.tracks = r.tracks.data_ptr()
-        a.track_array = None
-        a.start_params = self.start_params.data_ptr()
-        a.target_params = batch.target.data_ptr()
-        a.diff_params = batch.diff.data_ptr()
-        a.unified_index = self.unified.data_ptr()
-        a.converge = r.converge.data_ptr()
-        a.infinity = r.infinity.data_ptr()
-        a.stats = r.stats.data_ptr() if r.stats is not None else None
+        ws_t = self._workspace(workspace)
+        a = self._track_args(r, batch.target, batch.diff, 0, n)
         g = _abi.hcGroupedAbortArgs()
         g.num_groups = T
         g.groups = batch.groups.data_ptr()
@@ -251,7 +264,6 @@ class DeviceTracker:
         if num_samples < 0 or sample_offset < 0 or sample_offset + num_samples > target.shape[0] or \
                 (sample_offset + num_samples) * 312 > r.tracks.shape[0]:
             raise _abi.HCError("sample range outside the buffers")
-        p0, p1 = sample_offset * 312, (sample_offset + num_samples) * 312
         if workspace is None and not abort and time_slicing:
             need = int(self.L.hc_trifocal_workspace_size_for_steps(num_samples, self.settings.max_steps))
             if self.workspace.numel() < need:
@@ -262,24 +274,9 @@ class DeviceTracker:
                 torch.cuda.synchronize(self.device)
                 self.workspace = torch.zeros(need, dtype=torch.uint8, device=self.device)
                 torch.cuda.synchronize(self.device)
-        ws_t = workspace if workspace is not None else self.workspace
-        if ws_t.numel() < self.ws_bytes:
-            raise _abi.HCError("workspace too small")
+        ws_t = self._workspace(workspace)
         wsb = ws_t.numel() if (time_slicing and not abort) else self.ws_bytes
-        a = _abi.hcTrackArgs()
-        a.sub_ransac_iters = num_samples
-        a.settings = self.settings
-        a.start_sols = self.start_sols.data_ptr()
-        a.start_sols_array = None
-        a.tracks = r.tracks[p0:p1].data_ptr()
-        a.track_array = None
-        a.start_params = self.start_params.data_ptr()
-        a.target_params = target[sample_offset:].data_ptr()
-        a.diff_params = diff[sample_offset:].data_ptr()
-        a.unified_index = self.unified.data_ptr()
-        a.converge = r.converge[p0:p1].data_ptr()
-        a.infinity = r.infinity[p0:p1].data_ptr()
-        a.stats = r.stats[p0:p1].data_ptr() if r.stats is not None else None
+        a = self._track_args(r, target, diff, sample_offset, num_samples)
         s = stream if stream is not None else torch.cuda.current_stream(self.device)
         hs = C.c_void_p(s.cuda_stream)
         ws = C.c_void_p(ws_t.data_ptr())
@@ -295,7 +292,7 @@ class DeviceTracker:
             ab.triplet_edge_locations = self.edgels.data_ptr()
             ab.intrinsic_matrix = self.K.data_ptr()
             ab.found_trifocal_sols = r.found.data_ptr()
-            ab.trifocal_sols_batch_index = r.batch_index[p0:p1].data_ptr()
+            ab.trifocal_sols_batch_index = r.batch_index[sample_offset * 312:].data_ptr()
             ab.inflight_stop = 1 if inflight_stop else 0
             ab.peer_found = None if peer_found is None else peer_found.ptr
             _abi.check(self.L.hc_trifocal_2op1p_30x30_track_abort(C.byref(a), C.byref(ab), ws, wsb, hs),
