@@ -28,6 +28,14 @@ void hc_trifocal_set_ring_test(int delay_ticks);
    launch time. */
 void hc_trifocal_set_small_launch(int mode);
 
+/* Whether a sliced tracking launch keeps the first RK4 slope of every step in
+   the path's suspend block and starts the retry of a rejected step from it
+   instead of solving the same system again: 1 (the default) on, 0 off.  The
+   results are identical up to the sign of zeros; only the speed differs.
+   Launches without time slicing, the abort launches and the archived
+   ablations never reuse it.  Read at launch time. */
+void hc_trifocal_set_retry_reuse(int on);
+
 /* The end-of-launch ring check of a sliced launch (k_ring_check) on ring
    counters set by hand: head, tail and avail are written into the workspace's
    time-slicing area (workspace_bytes must cover the workspace and the ring

@@ -131,6 +131,7 @@ def main():
             "solves_rerun_densely": lw.get("solves_rerun_densely"),
             "live_groups_per_wave_solve": lw.get("live_groups_per_wave_solve"),
             "executed_fraction": lw.get("executed_fraction"),
+            "reused_stage0": lw.get("reused_stage0"), "path_stages_executed": lw.get("path_stages_executed"),
             "pose": {"gt_match": bool(ok), "gt_match_acos_clamped": pose.success_clamped(data, sel, res),
                      "candidates": sel["num_candidates"],
                      "residuals": [round(float(v), 6) for v in res]},

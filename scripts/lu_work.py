@@ -35,7 +35,7 @@ def main():
     fn = L.hc_diag_luwork
     fn.argtypes = [C.POINTER(C.c_ulonglong), C.c_int]
     fn.restype = C.c_int
-    out = (C.c_ulonglong * 10)()
+    out = (C.c_ulonglong * 11)()   # DIAG_LUWORK_WORDS (csrc/hc_lu.hpp)
     dev = torch.device("cuda:0")
     problem = load_problem()
     argv = sys.argv[1:]
@@ -70,15 +70,19 @@ def main():
     elems, solves, dense = int(out[0]), int(out[1]), int(out[2])
     wsolves, groups, rare = int(out[3]), int(out[4]), int(out[5])
     ev = [int(out[6]), int(out[7]), int(out[8])]
+    # retry reuse: a rejected step's retry takes stage 0 from the kept slope, so
+    # the stages run are fewer than the statistics' 4 * steps + corrections
+    reused = int(out[10])
     res = {"config": ("sample 0 of config 2 + its target params x 2^40, x 2^70 (one launch)" if scaled
                       else "config 2 (100 samples, abort off), one launch" +
                       ("" if (ds, seed) == (0, 0) and "--sigma" not in argv else
                        f", dataset {ds:03d}, srand({seed})" + (f", sigma {argv[argv.index('--sigma') + 1]} px"
                                                               if "--sigma" in argv else ""))),
            "sparse_solves_completed": solves, "path_stages": stages,
+           "reused_stage0": reused, "path_stages_executed": stages - reused,
            "solves_rerun_densely": dense,
-           "check": "sparse_solves_completed + solves_rerun_densely == path_stages",
-           "check_ok": solves + dense == stages,
+           "check": "sparse_solves_completed + solves_rerun_densely == path_stages_executed",
+           "check_ok": solves + dense == stages - reused,
            "executed_update_elements": elems,
            "executed_update_elements_per_solve": elems / max(1, solves),
            "dense_update_elements_per_solve": DENSE_UPDATE_ELEMENTS,

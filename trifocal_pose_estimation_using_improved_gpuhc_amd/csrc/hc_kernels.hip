@@ -65,6 +65,9 @@ static std::atomic<int> g_ring_test{0};
 // tests only (hc_trifocal_set_small_launch): -1 never the small-launch
 // kernels, 0 by size, 1 always (tracking launches)
 static std::atomic<int> g_small_launch{0};
+// tests only (hc_trifocal_set_retry_reuse): 0 a sliced launch's retries
+// recompute their first slope, as unsliced launches always do
+static std::atomic<int> g_retry_reuse{1};
 
 // Persistent grid: resident workgroups (occupancy API, cached per device and
 // kernel) x CUs, capped by the work.  resident_wgs(k) = grid_for(INT_MAX, k).
@@ -226,6 +229,7 @@ static hcStatus launch_track(const hcTrackArgs *t, const TrackLaunch &l, void *w
         k.susp = (unsigned long long *)(base + RQ_WORDS * sizeof(unsigned) + ring_bytes(k.ring_cap));
         k.slice_q = SLICE_Q;
         k.ring_test = g_ring_test.load(std::memory_order_relaxed);
+        k.retry_reuse = g_retry_reuse.load(std::memory_order_relaxed);   // (the slope is kept in the suspend block)
     }
     // control block reset, compacted tables (skipped when cached), ring reset
     // (a grouped launch's flags are the caller's group_found words: Workspace::found stays 0, unused)
@@ -517,8 +521,10 @@ void hc_trifocal_set_small_launch(int mode) {
     hc::g_small_launch.store(mode < 0 ? -1 : mode > 0 ? 1 : 0, std::memory_order_relaxed);
 }
 
+void hc_trifocal_set_retry_reuse(int on) { hc::g_retry_reuse.store(on ? 1 : 0, std::memory_order_relaxed); }
+
 const char *hc_trifocal_version(void) {
-    return "hc_trifocal gfx950 v10.7 (2 paths/wave, structurally sparse LDS-broadcast LU with lean pivot steps, "
+    return "hc_trifocal gfx950 v10.8 (2 paths/wave, structurally sparse LDS-broadcast LU with lean pivot steps, "
            "one exec region per pivot step for the eligible rows with the column groups through scratch windows, "
            "column groups by structural class (never-fillable groups untested, always-live groups unconditional), "
            "pivot search narrowed to the candidate rows' DPP group "
@@ -527,7 +533,7 @@ const char *hc_trifocal_version(void) {
            "group untested), "
            "structure-agnostic twin kernels for other dH/dx structures, readlane back substitution, pipelined evals over "
            "per-slot prefix tables, 5 waves/SIMD, time slicing at step boundaries with least-attained-service "
-           "issue priority)";
+           "issue priority, a rejected step's retry reuses its first RK4 slope)";
 }
 
 }  // extern "C"

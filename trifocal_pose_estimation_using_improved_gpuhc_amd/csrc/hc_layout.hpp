@@ -46,7 +46,9 @@ static_assert(offsetof(Workspace, tab) == 64, "control block is 64 bytes");
 
 // Time slicing (hc_ring.hpp).  Suspend block of path b (32 x 8 B): words 0..29 = x, word 30 = (t0, dt),
 // word 31 = (stepidx | nsteps << 16, ncorr | succ << 16 | flags << 30); the
-// launcher enables slicing only where these fields fit (slice_fits).
+// launcher enables slicing only where these fields fit (slice_fits).  While its
+// path runs on a slot, words 0..29 hold the first RK4 slope of the path's
+// current step (retry reuse, hc_track_body.inc).
 constexpr int SUSP_WORDS = 32;
 // Steps per time slice: SLICE_Q while at most one suspended path per path slot
 // waits (the launch's end, where the rotation's granularity sets the tail;
@@ -104,7 +106,9 @@ struct KArgs {
     int slice_q;
     int ring_test;                  // tests only (hc_trifocal_set_ring_test): pusher delay in ticks, else 0
     unsigned ring_cap;
-    unsigned *rq;                   // ring counters, one 256-B line each: [0] head, [64] tail, [128] avail, [192] meta
+    int retry_reuse;                // a rejected step's retry takes its first RK4 slope from the suspend block
+                                    // (hc_track_body.inc; off: tests only, hc_trifocal_set_retry_reuse)
+    unsigned *rq;                  // ring counters, one 256-B line each: [0] head, [64] tail, [128] avail, [192] meta
     unsigned long long *susp;       // suspend blocks, SUSP_WORDS per path id
     unsigned long long *ring;       // ring_tag(epoch, ticket) << 32 | path id
     // grouped abort mode (hcGroupedAbortArgs): the scene and the found flag of

@@ -293,8 +293,9 @@ __device__ __forceinline__ bool group_live(uint32_t pmw, uint32_t gb) {
 // [0] executed elements, [1] completed sparse solves, [2] dense solves (path
 // solves); wave-level: [3] sparse wave-solves, [4] live column groups, [5] rare
 // pivot steps; [6..8] stages whose right-hand side ran the mixed / dH/dt-only /
-// H-only evaluation, [9] stages that rebuilt the prefix tables (k_track)
-constexpr int DIAG_LUWORK_WORDS = 10;
+// H-only evaluation, [9] stages that rebuilt the prefix tables (k_track),
+// [10] path-level stage 0s taken from the kept slope of a rejected step (retry reuse)
+constexpr int DIAG_LUWORK_WORDS = 11;
 __device__ unsigned long long g_diag_luwork[DIAG_LUWORK_WORDS];
 struct LuWork { unsigned long long acc, mask, groups, rare, excl; };   // mask: lanes whose work counts (active
                                                                       // path slots); excl: lanes that update by l = 0

@@ -59,6 +59,13 @@ __device__ unsigned long long g_diag_phase[13];
 #ifndef HC_ABORT_PRIO_DIV
 #define HC_ABORT_PRIO_DIV 16
 #endif
+// Retry reuse (hc_track_body.inc): 1: a half about to retry a rejected step with
+// its kept first slope is not suspended at that boundary (the suspension would
+// overwrite the slope); 0: it is suspended like any other and recomputes the
+// slope after its resume
+#ifndef HC_RETRY_HOLD
+#define HC_RETRY_HOLD 1
+#endif
 // Whether tracking launches that fill at most half of the path slots go to
 // k_track_small (launch_track, hc_kernels.hip); 0: never
 #ifndef HC_SMALL_LAUNCH

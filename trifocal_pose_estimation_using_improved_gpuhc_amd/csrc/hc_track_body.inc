@@ -75,6 +75,16 @@
     float t0 = 0.0f, t_step = 0.0f, dt = 0.01f, h2 = 0.0f, scale = 0.0f;
     bool end_zone = false, check = true, isSucc = false, isInf = false;
     cf x = cmk(0.0f, 0.0f), xl = x, sols = x;
+    // Retry reuse (sliced tracking launches): a rejected step's retry starts from
+    // the same x, t and sample as the step it repeats, so its stage 0 would solve
+    // the same system for the same slope k1.  Every stage 0 leaves k1 in words
+    // 0..29 of the path's own suspend block, which is unused while the path runs;
+    // k1v: the block holds the k1 of the step that starts next.  Set by a
+    // rejection and consumed by the PH_BEGIN that follows it before any other
+    // stage runs, so it is not parked with the slot state; a new path and a
+    // resume clear it.
+    constexpr bool REUSE = !ABORT && !ARCH;
+    bool k1v = false;
 
 #ifdef HC_DIAG_PHASES
     uint64_t dg[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -207,6 +217,7 @@
                     end_zone = (w3 >> 30) & 1u; check = (w3 >> 31) & 1u; isSucc = false; isInf = false;
                     t_step = 0.0f;
                     piece = 0;
+                    k1v = false;   // the block held x: a k1 kept before the suspension is gone
                     ph = PH_BEGIN;
                 } else if (nb >= a.num_paths) {
                     ph = PH_IDLE;
@@ -257,6 +268,7 @@
                         t0 = 0.0f; t_step = 0.0f; dt = 0.01f;                 // :80
                         end_zone = false; check = !ARCH || a.truncate != 0; isSucc = false; isInf = false;
                         succ = 0; nsteps = 0; ncorr = 0; stepidx = 0; piece = 0;
+                        k1v = false;
                         ph = PH_BEGIN;
                     }
                 }
@@ -289,7 +301,10 @@
                 // (every path stays suspendable: long paths keeping their slots
                 // measured 5-20 % slower, DESIGN.md section 3.6; that A/B switch
                 // and the issue-priority ones below are in commit 02bc69d)
-                if (!ABORT && !done && a.slice_q > 0 && piece >= a.slice_q) {
+                // (a half about to retry with a kept k1 is not suspended, the block
+                // would be overwritten with x: it runs the retry first and is
+                // suspendable at the next boundary.  HC_RETRY_HOLD, hc_track.hpp)
+                if (!ABORT && !done && a.slice_q > 0 && piece >= a.slice_q && !(REUSE && HC_RETRY_HOLD && k1v)) {
                     // time slice used up: suspend for a new path (its ticket
                     // claimed here), else swap with a suspended path, else
                     // keep running
@@ -339,7 +354,30 @@
                     s = 0;
                     nsteps++;
                     piece++;
+                    if constexpr (REUSE) {
+                        if (k1v) {
+                            // The retry of a rejected step: stage 0 is taken from the kept k1,
+                            // with the s == 0 update of the stage machine below, op for op
+                            // (dt enters only here, k1 does not depend on it).  The k1 was
+                            // stored by these lanes several stages ago; the wait for
+                            // every store of the wave to be acknowledged orders this load
+                            // after it (same address, same device-coherent level).
+                            drain_stores();
+                            const cf k1 = rl ? ld_cf_rlx(reinterpret_cast<const cf *>(a.susp + (size_t)b * SUSP_WORDS + r))
+                                             : cmk(0.0f, 0.0f);
+                            sols = cadd(sols, cscale(cscale(k1, dt), (float)(1.0 / 6.0)));
+                            scale += h2;
+                            coef <<= 1;
+                            x = cadd(x, cscale(k1, scale));
+                            t0 += h2;
+                            s = 1;
+#ifdef HC_DIAG_LUWORK
+                            if (r == 0) atomicAdd(&g_diag_luwork[10], 1ull);
+#endif
+                        }
+                    }
                 }
+                k1v = false;   // used, or lost to the end of the path or to a suspension
                 ph = suspend ? PH_DEQ : done ? PH_FINISH : PH_STAGE;
             }
             if (__ballot(ph == PH_FINISH || ph == PH_DEQ || ph == PH_BEGIN) == 0ull) break;
@@ -552,6 +590,7 @@
             end_zone = q.flags & 1; check = q.flags & 2; isSucc = q.flags & 4; isInf = q.flags & 8;
             piece = q.flags >> 4;
             qpos = q.pad;
+            k1v = false;   // (never set across a stage)
             x = rl ? S.x[r] : cmk(0.0f, 0.0f);
             xl = rl ? S.xl[r] : cmk(0.0f, 0.0f);
             sols = rl ? S.sols[r] : cmk(0.0f, 0.0f);
@@ -582,6 +621,11 @@
                     coef <<= sc;
                     x = cadd(x, cscale(k, scale));
                     t0 += (float)sc * h2;
+                    if constexpr (REUSE) {
+                        // keep k1 for a retry of this step (PH_BEGIN)
+                        if (s == 0 && rl && a.slice_q > 0 && a.retry_reuse)
+                            st_cf_rlx(reinterpret_cast<cf *>(a.susp + (size_t)b * SUSP_WORDS + r), k);
+                    }
                 } else {                                                     // :209-210
                     sols = cadd(sols, cdivs(cscale(cscale(k, dt), 1.0f), 6.0f));
                     x = sols;
@@ -609,6 +653,8 @@
                         sols = xl;
                         succ = 0;
                         t0 = t_step;
+                        // the retry starts where this step started: its k1 is this step's
+                        if constexpr (REUSE) k1v = a.slice_q > 0 && a.retry_reuse;
                     } else {                                                 // :266-275
                         succ++;
                         xl = x;
