@@ -5,7 +5,9 @@
 # (HC_LU_*, HC_EV_*, HC_HX_GROUPED, HC_AB_*, HC_CGESV4, HC_SLICE_Q, HC_PRIO_*)
 # were removed from the product sources in round 3; they live in commit 136b029.
 # Round 6's scheduling switches (HC_SLICE_HOLD, HC_PRIO_LAS, HC_PRIO_STEPW,
-# HC_PRIO_REM) live in commit 02bc69d.
+# HC_PRIO_REM) live in commit 02bc69d.  The switches settled in rounds 5 to 7 and
+# v10.8 (HC_ABORT_GTAB with the LDS staging of the term tables, HC_LU_LATB with the
+# paired always-live groups, HC_RETRY_HOLD, HC_SMALL_LAUNCH) live in commit 12ddb46.
 set -e
 cd "$(dirname "$0")/../trifocal_pose_estimation_using_improved_gpuhc_amd/csrc"
 N=$1; shift

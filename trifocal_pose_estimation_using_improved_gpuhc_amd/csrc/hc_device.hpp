@@ -107,14 +107,6 @@ constexpr int DPP_ROW_MIRROR = 0x140;
 constexpr int DPP_ROW_HALF_MIRROR = 0x141;
 constexpr int DPP_ROW_SHL1 = 0x101, DPP_ROW_SHL2 = 0x102, DPP_ROW_SHL4 = 0x104, DPP_ROW_SHL8 = 0x108;
 
-__device__ __forceinline__ int half_min_i(int v) {
-    v = min(v, dpp_i<DPP_QP_1032>(v));
-    v = min(v, dpp_i<DPP_QP_2301>(v));
-    v = min(v, dpp_i<DPP_ROW_HALF_MIRROR>(v));
-    v = min(v, dpp_i<DPP_ROW_MIRROR>(v));
-    v = min(v, swz_xor16_i(v));
-    return v;
-}
 // sum over each 32-lane half, result in every lane of the half
 __device__ __forceinline__ int half_sum_i(int v) {
     v += dpp_i<DPP_QP_1032>(v);
@@ -133,7 +125,6 @@ __device__ __forceinline__ int wave_sum_i(int v) {
     v += __shfl_xor(v, 1);
     return __builtin_amdgcn_readfirstlane(v);
 }
-__device__ __forceinline__ int bperm_i(int v, int src_lane) { return __builtin_amdgcn_ds_bpermute(src_lane << 2, v); }
 // lane 0 of each 32-lane half to the whole half (address from lane_fresh)
 __device__ __forceinline__ int bcast_half0(int v) { return __builtin_amdgcn_ds_bpermute((lane_fresh() & 32) << 2, v); }
 // broadcast relative lane L (compile-time) of each 32-lane half to the whole half

@@ -229,8 +229,7 @@ __device__ __forceinline__ void eval_hx(cf (&rA)[NV], const uint32_t *s_hx, cons
 // (EvalTables::pre): (c * p[a]) * p[b] into tp and d[a]*p[b] + d[b]*p[a] into
 // qp, with the operations of the term loops they replace (:57-148).  The two
 // halves build their own slots' tables in the same instructions.
-template <typename PW>
-__device__ __forceinline__ void build_prefix_rounds(SlotLDS &S, int r, const PW *pre) {
+__device__ __forceinline__ void build_prefix_rounds(SlotLDS &S, int r, const uint2 *pre) {
     char *sb = reinterpret_cast<char *>(&S);
     wave_lds_sync();
 #pragma unroll
@@ -256,8 +255,7 @@ __device__ __forceinline__ void build_prefix_rounds(SlotLDS &S, int r, const PW 
 // 0 also p[32]; p[33] = 1; ..._TrunPaths.cu:181 via the p(t) helper of
 // dev-eval-indxing-..._LimUnroll_L2Cache.cuh:40-54) and d[r] from the slot's
 // sample (global memory, L2-resident); sp: the start params (LDS).
-template <typename PW>
-__device__ __forceinline__ void build_prefixes(SlotLDS &S, int r, const PW *pre, const cf *target, const cf *diff,
+__device__ __forceinline__ void build_prefixes(SlotLDS &S, int r, const uint2 *pre, const cf *target, const cf *diff,
                                                const cf *sp, float t0) {
     cf *stg = S.ent;
     const float omt = (float)(1.0 - (double)t0);
@@ -349,8 +347,8 @@ __device__ __forceinline__ RhsMasks rhs_masks(const EvalTables *T) {
 
 template <int KIND>
 struct RhsOps { pf2 t, q, xu, xv, xw; };
-template <int KIND, typename TW>
-__device__ __forceinline__ RhsOps<KIND> rhs_ops(const char *sb, const TW &w) {
+template <int KIND>
+__device__ __forceinline__ RhsOps<KIND> rhs_ops(const char *sb, const uint2 &w) {
     RhsOps<KIND> o;
     if constexpr (KIND != RHS_HT) o.t = ldp(sb, w.x & 0xFFFFu);     // (c * p[a]) * p[b]
     if constexpr (KIND != RHS_H) o.q = ldp(sb, w.x >> 16);          // d[a]*p[b] + d[b]*p[a]
@@ -360,11 +358,11 @@ __device__ __forceinline__ RhsOps<KIND> rhs_ops(const char *sb, const TW &w) {
     return o;
 }
 
-template <int KIND, typename TW>
-__device__ __forceinline__ cf eval_rhs(const TW *s_ht, const SlotLDS &S, int r, bool ht_half, const RhsMasks &mk) {
+template <int KIND>
+__device__ __forceinline__ cf eval_rhs(const uint2 *s_ht, const SlotLDS &S, int r, bool ht_half, const RhsMasks &mk) {
     const char *sb = reinterpret_cast<const char *>(&S);
     constexpr bool SUB = KIND == RHS_HT;
-    TW w[HT_TERMS];
+    uint2 w[HT_TERMS];
 #pragma unroll
     for (int j = 0; j < EV_WAHEAD; j++) w[j] = s_ht[j * 32 + r];
     RhsOps<KIND> o[EV_AHEAD + 1];

@@ -109,7 +109,7 @@ struct TrackLaunch {
 // (mode, small-launch decision) -> the kernel whose LU is specialised to this
 // problem's dH/dx structure and its structure-agnostic twin.
 // Term tables read from the workspace (L1/L2).  Tracking: 96 VGPRs, 31 KB
-// LDS per workgroup -> 5 waves/SIMD.  Abort mode: HC_ABORT_MINW, HC_ABORT_GTAB
+// LDS per workgroup -> 5 waves/SIMD.  Abort mode: HC_ABORT_MINW
 // (hc_track.hpp).  The device compiler emits the instantiations in the order
 // this function first names them, after the plain kernels: a
 // new kernel goes at the end of a row, and the small-launch pair stays last.
@@ -117,10 +117,10 @@ struct TrackKernels { const void *lus, *any; };
 static TrackKernels track_kernels(TrackMode mode, bool small) {
     static const void *const by_mode[2][6] = {
         {(const void *)k_track_gated<true>, (const void *)k_track_grouped<true>,
-         (const void *)k_track<true, HC_ABORT_MINW, HC_ABORT_GTAB>, (const void *)k_track<false, 5, true, true>,
+         (const void *)k_track<true, HC_ABORT_MINW, true>, (const void *)k_track<false, 5, true, true>,
          (const void *)k_track<false, 5, true, true>, (const void *)k_track<false, 5, true>},
         {(const void *)k_track_gated<false>, (const void *)k_track_grouped<false>,
-         (const void *)k_track<true, HC_ABORT_MINW, HC_ABORT_GTAB, false, false>,
+         (const void *)k_track<true, HC_ABORT_MINW, true, false, false>,
          (const void *)k_track<false, 5, true, true, false>, (const void *)k_track<false, 5, true, true, false>,
          (const void *)k_track<false, 5, true, false, false>}};
     if (small) return {(const void *)k_track_small<true>, (const void *)k_track_small<false>};
@@ -132,7 +132,7 @@ static TrackKernels track_kernels(TrackMode mode, bool small) {
 // slot of the small kernel at once (or when the testing hook forces it)
 static bool small_launch(TrackMode mode, long long paths) {
     const int small_mode = g_small_launch.load(std::memory_order_relaxed);
-    if (!HC_SMALL_LAUNCH || mode != TrackMode::Track || small_mode < 0) return false;
+    if (mode != TrackMode::Track || small_mode < 0) return false;
     const long long slots = 2ll * WAVES_PER_WG * resident_wgs(track_kernels(mode, false).lus);   // two paths per wave
     const long long small_slots = 2ll * WAVES_PER_WG * resident_wgs(track_kernels(mode, true).lus);
     return small_mode > 0 || (slots > 0 && 2 * paths <= slots && paths <= small_slots);
@@ -489,8 +489,8 @@ unsigned hc_lu_struct_pattern(int row) { return row >= 0 && row < hc::NV ? hc::L
 unsigned hc_lu_candidates(int step) { return step >= 0 && step < hc::NV ? hc::LU_BOUND.cand[step] : 0u; }
 int hc_lu_search_span(int step) { return step >= 0 && step < hc::NV ? hc::lu_search_span(step) : -1; }
 int hc_lu_group_class(int step, int group) {
-    if (step < 0 || step >= hc::NV - 1 || group < 0 || group >= hc::LuChunks<2>::count(step)) return -1;
-    return hc::lu_group_class<2>(step, group);
+    if (step < 0 || step >= hc::NV - 1 || group < 0 || group >= hc::LuChunks::count(step)) return -1;
+    return hc::lu_group_class(step, group);
 }
 
 hcStatus hc_trifocal_ring_check_test(void *workspace, size_t workspace_bytes, unsigned head, unsigned tail,

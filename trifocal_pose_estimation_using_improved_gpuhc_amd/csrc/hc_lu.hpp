@@ -29,8 +29,15 @@
 //    lane writes the group of its row (ds_write_b128; the pivot lane to the
 //    buffer, the others to their own scratch window) and reads the pivot
 //    row's group back (broadcast ds_read_b128) and updates, 2 v_pk_fma_f32 per
-//    element.  The abort kernel's latency mode also writes the pivot row's
-//    1/pivot, rhs and rowid from every lane (no exec region at all).
+//    element.  The latency mode (LAT > 0: the abort and small-launch kernels)
+//    makes one LDS round trip per step instead: every lane writes 1/pivot,
+//    rhs, rowid and every column group the fill-in bound leaves alive, none
+//    of them tested ("Batched latency mode" below).  Their structure-agnostic
+//    twins test the groups as above, and write 1/pivot, rhs and rowid from
+//    every lane (no exec region for the broadcast).
+//
+// A column group is LU_CHUNK = 2 columns everywhere (the scratch windows are
+// 16 B); only a group's length N (1 for a leading single column) is generic.
 //
 // Structural sparsity.  The trifocal Jacobian is sparse (170 of 900 entries
 // carry terms) and partial-pivot elimination fills it in only partly: on
@@ -70,8 +77,8 @@ struct alignas(16) LUBuf {
 static_assert(sizeof(LUBuf) == sizeof(SlotLDS::lu), "LUBuf is SlotLDS::lu");
 static_assert(offsetof(SlotLDS, lu) % 16 == 0, "SlotLDS::lu must be 16-B aligned");
 
-// columns per skippable group (the template parameter CH below): 2, where the
-// LDS stores of dead columns are what a wider group costs
+// columns per skippable group: 2, where the LDS stores of dead columns are
+// what a wider group costs, and what the 16-B scratch windows hold
 // (profiles/r3u_ab_oo_rz_gs_chunk2.jsonl: 33.55 -> 31.78 ms per config-2
 // launch).  The abort kernel used groups of 4 in two loops until round 5, for
 // its lone-wave latency; groups of 2 in the eligible rows' region are as fast
@@ -185,16 +192,15 @@ __device__ __forceinline__ pf2 pcdiv_apply(pf2 b, pf2 piv, const PivF &f) {
 }
 
 // Column groups of step I: a leading single column when I+1 is odd, then
-// groups of CH (even) columns.  The pivot lanes write, and the update reads,
+// groups of LU_CHUNK (even) columns.  The pivot lanes write, and the update reads,
 // exactly these groups.
-template <int CH>
 struct LuChunks {
     static constexpr int single(int I) { return ((I + 1) & 1) && (I + 1 < NV) ? 1 : 0; }
-    static constexpr int start(int I, int k) { return k < single(I) ? I + 1 : I + 1 + single(I) + (k - single(I)) * CH; }
+    static constexpr int start(int I, int k) { return k < single(I) ? I + 1 : I + 1 + single(I) + (k - single(I)) * LU_CHUNK; }
     static constexpr int len(int I, int k) {
-        return k < single(I) ? 1 : ((NV - start(I, k)) < CH ? (NV - start(I, k)) : CH);
+        return k < single(I) ? 1 : ((NV - start(I, k)) < LU_CHUNK ? (NV - start(I, k)) : LU_CHUNK);
     }
-    static constexpr int count(int I) { return single(I) + (NV - (I + 1 + single(I)) + CH - 1) / CH; }
+    static constexpr int count(int I) { return single(I) + (NV - (I + 1 + single(I)) + LU_CHUNK - 1) / LU_CHUNK; }
     static constexpr uint32_t mask(int I, int k) { return ((1u << len(I, k)) - 1u) << start(I, k); }
 };
 
@@ -241,9 +247,8 @@ constexpr LuBound lu_struct_bound() {
 }
 constexpr LuBound LU_BOUND = lu_struct_bound();
 enum : int { GRP_TESTED = 0, GRP_DEAD = 1, GRP_ALWAYS = 2 };
-template <int CH>
 constexpr int lu_group_class(int I, int K) {
-    return (LU_BOUND.s[I] & LuChunks<CH>::mask(I, K)) == 0u ? GRP_DEAD
+    return (LU_BOUND.s[I] & LuChunks::mask(I, K)) == 0u ? GRP_DEAD
            : ((LU_ALWAYS[I] >> K) & 1u)                     ? GRP_ALWAYS
                                                               : GRP_TESTED;
 }
@@ -260,28 +265,26 @@ constexpr int lu_search_span(int I) {
     while (!((c >> hi) & 1u)) hi--;
     return (lo >> 2) == (hi >> 2) ? 1 : (lo >> 3) == (hi >> 3) ? 2 : (lo >> 4) == (hi >> 4) ? 3 : 4;
 }
-template <int CH>
 constexpr bool lu_classes_consistent() {   // no measured-always group is provably dead
     for (int i = 0; i < NV - 1; i++)
-        for (int k = 0; k < LuChunks<CH>::count(i); k++)
-            if (((LU_ALWAYS[i] >> k) & 1u) && (LU_BOUND.s[i] & LuChunks<CH>::mask(i, k)) == 0u) return false;
+        for (int k = 0; k < LuChunks::count(i); k++)
+            if (((LU_ALWAYS[i] >> k) & 1u) && (LU_BOUND.s[i] & LuChunks::mask(i, k)) == 0u) return false;
     return true;
 }
-static_assert(lu_classes_consistent<2>(), "LU_ALWAYS names a provably dead group");
+static_assert(lu_classes_consistent(), "LU_ALWAYS names a provably dead group");
 
 // Group tests on one bit: gbits = pmw | pmw >> 1 | pmw >> 2 | pmw >> 3, so bit J
 // says "some column of J..J+3 may be non-zero" and a group test is s_bitcmp1
 // + s_cbranch (the compiler keeps an s_cmp after a multi-bit s_and).
-template <int CH>
 __device__ __forceinline__ uint32_t group_bits(uint32_t pmw) {
     uint32_t t = pmw;
 #pragma unroll
-    for (int k = 1; k < CH; k++) t |= pmw >> k;
+    for (int k = 1; k < LU_CHUNK; k++) t |= pmw >> k;
     return t;
 }
-template <int I, int K, int CH>
+template <int I, int K>
 __device__ __forceinline__ bool group_live(uint32_t pmw, uint32_t gb) {
-    using C = LuChunks<CH>;
+    using C = LuChunks;
     constexpr int J = C::start(I, K), N = C::len(I, K);
     if constexpr (N == 1) return (pmw >> J) & 1u;
     else return (gb >> J) & 1u;
@@ -329,13 +332,13 @@ __device__ unsigned long long g_diag_live[NV][LIVE_SOLVES + 1];
 // pivot row's stores and the update each tested every group before: 2.2 %
 // faster, profiles/r4o_ab_fused_group_tests.jsonl); the pivot lanes write the
 // group, the rows below read it back and take a_j -= l * u_j
-template <int I, int K, int CH>
+template <int I, int K>
 __device__ __forceinline__ void lu_store_update(cf (&rA)[NV], const cf &l, uint32_t pmw, uint32_t gb, LUBuf &L,
                                                 bool is_piv, bool below HC_LU_WORK_ARG) {
-    using C = LuChunks<CH>;
+    using C = LuChunks;
     if constexpr (K < C::count(I)) {
         constexpr int J = C::start(I, K), N = C::len(I, K);
-        if (__builtin_expect(group_live<I, K, CH>(pmw, gb), 1)) {
+        if (__builtin_expect(group_live<I, K>(pmw, gb), 1)) {
             if (is_piv) {
                 if constexpr (N == 1) {
                     L.row[J] = rA[J];
@@ -365,7 +368,7 @@ __device__ __forceinline__ void lu_store_update(cf (&rA)[NV], const cf &l, uint3
             }
         }
         __builtin_amdgcn_sched_barrier(0);
-        lu_store_update<I, K + 1, CH>(rA, l, pmw, gb, L, is_piv, below HC_LU_WORK_PASS);
+        lu_store_update<I, K + 1>(rA, l, pmw, gb, L, is_piv, below HC_LU_WORK_PASS);
     }
 }
 
@@ -385,42 +388,14 @@ __device__ __forceinline__ void lu_store_update(cf (&rA)[NV], const cf &l, uint3
 // -5 %; a variant whose pivot row also went through a window, its address
 // exchanged with 1/pivot, issued fewer instructions and ran 1 % slower,
 // profiles/r5h_ab_lu_windows.jsonl.)
-template <int I, int K, int CH, bool STRUCT, bool PAIRS = false>
+template <int I, int K, bool STRUCT>
 __device__ __forceinline__ void lu_group_elig(cf (&rA)[NV], const pf2 &l, uint32_t pmw, uint32_t gb, cf *wrow,
                                               const LUBuf &L HC_LU_WORK_ARG) {
-    using C = LuChunks<CH>;
-    constexpr bool PAIR = PAIRS && STRUCT && K + 1 < C::count(I) && lu_group_class<CH>(I, K) == GRP_ALWAYS &&
-                          lu_group_class<CH>(I, K + 1) == GRP_ALWAYS && C::len(I, K) == 2 && C::len(I, K + 1) == 2;
-    if constexpr (PAIR) {
-        // latency mode (the abort kernel): two always-live groups, both stores,
-        // both reads, one wait (profiles/r5lp_ttfp_lat_pairs.jsonl: time to the
-        // first pose -1.6 %; the tracking kernel measured 0.7 % slower with it,
-        // three more VGPR spills: profiles/r5st_ab_lu_group_classes.jsonl, pr1)
-        constexpr int J = C::start(I, K), J2 = C::start(I, K + 1);
-        st4(&wrow[J], rA[J], rA[J + 1]);
-        st4(&wrow[J2], rA[J2], rA[J2 + 1]);
-        wave_lds_sync();
-        HC_LU_WORK(4);
-        HC_DIAG_LIVE_HIT(I, K);
-        HC_DIAG_LIVE_HIT(I, K + 1);
-#ifdef HC_DIAG_LUWORK
-        lu_work_acc.groups += 2;
-#endif
-        cf u[4];
-        ld4(&L.row[J], u[0], u[1]);
-        ld4(&L.row[J2], u[2], u[3]);
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const int c = q < 2 ? J + q : J2 + q - 2;
-            const pf2 v = pcmsub(pf2{rA[c].x, rA[c].y}, l, pf2{u[q].x, u[q].y});
-            rA[c] = cmk(v.x, v.y);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        lu_group_elig<I, K + 2, CH, STRUCT, PAIRS>(rA, l, pmw, gb, wrow, L HC_LU_WORK_PASS);
-    } else if constexpr (K < C::count(I)) {
+    using C = LuChunks;
+    if constexpr (K < C::count(I)) {
         constexpr int J = C::start(I, K), N = C::len(I, K);
-        constexpr int CLS = STRUCT ? lu_group_class<CH>(I, K) : GRP_TESTED;
-        if (CLS != GRP_DEAD && (CLS == GRP_ALWAYS || __builtin_expect(group_live<I, K, CH>(pmw, gb), 1))) {
+        constexpr int CLS = STRUCT ? lu_group_class(I, K) : GRP_TESTED;
+        if (CLS != GRP_DEAD && (CLS == GRP_ALWAYS || __builtin_expect(group_live<I, K>(pmw, gb), 1))) {
             if constexpr (N == 1) {
                 wrow[J] = rA[J];
             } else {
@@ -447,7 +422,7 @@ __device__ __forceinline__ void lu_group_elig(cf (&rA)[NV], const pf2 &l, uint32
             }
         }
         __builtin_amdgcn_sched_barrier(0);
-        lu_group_elig<I, K + 1, CH, STRUCT, PAIRS>(rA, l, pmw, gb, wrow, L HC_LU_WORK_PASS);
+        lu_group_elig<I, K + 1, STRUCT>(rA, l, pmw, gb, wrow, L HC_LU_WORK_PASS);
     }
 }
 
@@ -459,53 +434,51 @@ __device__ __forceinline__ void lu_group_elig(cf (&rA)[NV], const pf2 &l, uint32
 // makes ONE LDS round trip instead of one per live group: every lane writes
 // 1/pivot, rhs, rowid and all those groups (the pivot lane into the buffer,
 // the others into their scratch windows), then every lane reads them back
-// together, then the eligible rows update.
-#ifndef HC_LU_LATB
-#define HC_LU_LATB 1
-#endif
-template <int CH>
+// together, then the eligible rows update.  Taken whenever LAT > 0 && STRUCT
+// && !DENSE (lu_step_body); before it, this mode paired always-live groups
+// under one wait (profiles/r5lp_ttfp_lat_pairs.jsonl; the code is in 12ddb46).
 struct LatCols {   // the columns of step I's live-able groups, packed in group order
     static constexpr int off(int I, int K) {
         int n = 0;
         for (int k = 0; k < K; k++)
-            if (lu_group_class<CH>(I, k) != GRP_DEAD) n += LuChunks<CH>::len(I, k);
+            if (lu_group_class(I, k) != GRP_DEAD) n += LuChunks::len(I, k);
         return n;
     }
-    static constexpr int total(int I) { return off(I, LuChunks<CH>::count(I)); }
+    static constexpr int total(int I) { return off(I, LuChunks::count(I)); }
 };
-template <int I, int K, int CH>
+template <int I, int K>
 __device__ __forceinline__ void lat_store(const cf (&rA)[NV], cf *wrow) {
-    using C = LuChunks<CH>;
+    using C = LuChunks;
     if constexpr (K < C::count(I)) {
-        if constexpr (lu_group_class<CH>(I, K) != GRP_DEAD) {
+        if constexpr (lu_group_class(I, K) != GRP_DEAD) {
             constexpr int J = C::start(I, K), N = C::len(I, K);
             if constexpr (N == 1) wrow[J] = rA[J];
             else st4(&wrow[J], rA[J], rA[J + 1]);
         }
-        lat_store<I, K + 1, CH>(rA, wrow);
+        lat_store<I, K + 1>(rA, wrow);
     }
 }
 // the groups whose packed columns start in [LO, HI) (a batch: its reads are
 // issued together, its updates follow)
-template <int I, int K, int CH, int LO, int HI, int M>
+template <int I, int K, int LO, int HI, int M>
 __device__ __forceinline__ void lat_load(cf (&u)[M], const LUBuf &L) {
-    using C = LuChunks<CH>;
+    using C = LuChunks;
     if constexpr (K < C::count(I)) {
-        constexpr int O = LatCols<CH>::off(I, K);
-        if constexpr (lu_group_class<CH>(I, K) != GRP_DEAD && O >= LO && O < HI) {
+        constexpr int O = LatCols::off(I, K);
+        if constexpr (lu_group_class(I, K) != GRP_DEAD && O >= LO && O < HI) {
             constexpr int J = C::start(I, K), N = C::len(I, K);
             if constexpr (N == 1) u[O - LO] = L.row[J];
             else ld4(&L.row[J], u[O - LO], u[O - LO + 1]);
         }
-        lat_load<I, K + 1, CH, LO, HI>(u, L);
+        lat_load<I, K + 1, LO, HI>(u, L);
     }
 }
-template <int I, int K, int CH, int LO, int HI, int M>
+template <int I, int K, int LO, int HI, int M>
 __device__ __forceinline__ void lat_fma(cf (&rA)[NV], const pf2 &l, const cf (&u)[M]) {
-    using C = LuChunks<CH>;
+    using C = LuChunks;
     if constexpr (K < C::count(I)) {
-        constexpr int O = LatCols<CH>::off(I, K);
-        if constexpr (lu_group_class<CH>(I, K) != GRP_DEAD && O >= LO && O < HI) {
+        constexpr int O = LatCols::off(I, K);
+        if constexpr (lu_group_class(I, K) != GRP_DEAD && O >= LO && O < HI) {
             constexpr int J = C::start(I, K), N = C::len(I, K);
 #pragma unroll
             for (int q = 0; q < N; q++) {
@@ -513,7 +486,7 @@ __device__ __forceinline__ void lat_fma(cf (&rA)[NV], const pf2 &l, const cf (&u
                 rA[J + q] = cmk(v.x, v.y);
             }
         }
-        lat_fma<I, K + 1, CH, LO, HI>(rA, l, u);
+        lat_fma<I, K + 1, LO, HI>(rA, l, u);
     }
 }
 // columns read in the step's first batch (with 1/pivot and rhs); the rest
@@ -522,15 +495,15 @@ __device__ __forceinline__ void lat_fma(cf (&rA)[NV], const pf2 &l, const cf (&u
 #ifndef HC_LU_LATB_COLS
 #define HC_LU_LATB_COLS 8
 #endif
-template <int I, int LO, int CH, int B>
+template <int I, int LO, int B>
 __device__ __forceinline__ void lat_batches(cf (&rA)[NV], const pf2 &l, const LUBuf &L) {
-    constexpr int T = LatCols<CH>::total(I);
+    constexpr int T = LatCols::total(I);
     if constexpr (LO < T) {
         constexpr int HI = LO + B;
         cf u[B + 1];
-        lat_load<I, 0, CH, LO, HI>(u, L);
-        lat_fma<I, 0, CH, LO, HI>(rA, l, u);
-        lat_batches<I, HI, CH, B>(rA, l, L);
+        lat_load<I, 0, LO, HI>(u, L);
+        lat_fma<I, 0, LO, HI>(rA, l, u);
+        lat_batches<I, HI, B>(rA, l, L);
     }
 }
 
@@ -539,16 +512,16 @@ __device__ __forceinline__ void lat_batches(cf (&rA)[NV], const pf2 &l, const LU
 // finite or that met a pivot outside the fast reciprocal range): every column
 // group and the IEEE reciprocal.  The sparse solve carries no dense tests: it
 // reports such a solve, and the caller solves the system again densely.
-template <int I, bool DENSE, int CH, int LAT, bool STRUCT>
+template <int I, bool DENSE, int LAT, bool STRUCT>
 __device__ __forceinline__ void lu_step_body(cf (&rA)[NV], cf &rB, int &rowid, uint32_t &pat, PivF &my, LUBuf &L,
                                              cf *scr, bool is_piv, int pl0, int pl1, pf2 reg_s, pf2 oo_s,
                                              bool elig HC_LU_WORK_ARG) {
-    if constexpr (HC_LU_LATB && LAT > 0 && STRUCT && CH == 2 && !DENSE) {
+    if constexpr (LAT > 0 && STRUCT && !DENSE) {
         HC_ISA_MARK_I("lu_store", I);
         cf *wrow = is_piv ? L.row : scr;
         wrow[I] = cmk(reg_s.x, reg_s.y);
         st4(&wrow[30], rB, cmk(__int_as_float(rowid), 0.0f));
-        lat_store<I, 0, CH>(rA, wrow);
+        lat_store<I, 0>(rA, wrow);
         wave_lds_sync();
         HC_ISA_MARK_I("lu_rcp", I);
         // (the pivot lane reading an exact zero from a zero slot instead, so that
@@ -558,7 +531,7 @@ __device__ __forceinline__ void lu_step_body(cf (&rA)[NV], cf &rB, int &rowid, u
         cf sB0, pr;
         ld4(&L.row[30], sB0, pr);
         cf u[LAT + 1];
-        lat_load<I, 0, CH, 0, LAT>(u, L);
+        lat_load<I, 0, 0, LAT>(u, L);
         const int piv_pos = __float_as_int(pr.x);
         rowid = is_piv ? I : (rowid == I ? piv_pos : rowid);   // :70-82
         my.oo.x = is_piv ? oo_s.x : my.oo.x;
@@ -571,8 +544,8 @@ __device__ __forceinline__ void lu_step_body(cf (&rA)[NV], cf &rB, int &rowid, u
             const pf2 lp = {is_piv ? 0.0f : lq.x, is_piv ? 0.0f : lq.y};
             const pf2 bp = pcmsub(pf2{rB.x, rB.y}, lp, pf2{sB0.x, sB0.y});
             rB = cmk(bp.x, bp.y);
-            lat_fma<I, 0, CH, 0, LAT>(rA, lp, u);
-            lat_batches<I, LAT, CH, LAT>(rA, lp, L);
+            lat_fma<I, 0, 0, LAT>(rA, lp, u);
+            lat_batches<I, LAT, LAT>(rA, lp, L);
         }
         return;
     }
@@ -584,13 +557,14 @@ __device__ __forceinline__ void lu_step_body(cf (&rA)[NV], cf &rB, int &rowid, u
         const uint32_t pp1 = (uint32_t)__builtin_amdgcn_readlane((int)pat, pl1);
         pmw = (pp0 | pp1) & FULL;
     }
-    const uint32_t gb = group_bits<CH>(pmw);
+    const uint32_t gb = group_bits(pmw);
     HC_ISA_MARK_I("lu_store", I);
-    // latency mode (LAT, the abort kernel): every lane writes, the pivot lane to
+    // latency mode without the problem's structure (LAT, !STRUCT: the twins of the
+    // abort and small-launch kernels): every lane writes, the pivot lane to
     // the buffer, the others to their scratch windows -- no exec region, at the
     // price of LDS bandwidth (profiles/r5m_ab_lu_x.jsonl: lone sample -2 %,
     // loaded launch +0.8 %)
-    constexpr bool X1 = LAT > 0 && CH == 2 && !DENSE;
+    constexpr bool X1 = LAT > 0 && !DENSE;
     cf *wrow = nullptr;
     if constexpr (X1) {
         wrow = is_piv ? L.row : scr;
@@ -629,7 +603,7 @@ __device__ __forceinline__ void lu_step_body(cf (&rA)[NV], cf &rB, int &rowid, u
     // fill-in pattern (branch-free) and the rank-1 update.  Fill-in: a row
     // below whose column I may be non-zero takes the pivot patterns (both
     // halves': a superset of its own pivot row's).
-    if constexpr (CH == 2 && !DENSE) {
+    if constexpr (!DENSE) {
         // the multiplier, right-hand side and fill-in pattern in the eligible
         // rows' region too (the pivot lane's multiplier is zeroed: its rhs and
         // row stay, up to the sign of zeros), one exec region per step
@@ -650,7 +624,7 @@ __device__ __forceinline__ void lu_step_body(cf (&rA)[NV], cf &rB, int &rowid, u
             const pf2 bp = pcmsub(pf2{rB.x, rB.y}, lp, pf2{sB0.x, sB0.y});
             rB = cmk(bp.x, bp.y);
             pat |= (uint32_t)__builtin_amdgcn_sbfe((int)pat, I, 1) & pmw;
-            lu_group_elig<I, 0, CH, STRUCT, (LAT > 0)>(rA, lp, pmw, gb, wrow, L HC_LU_WORK_PASS);
+            lu_group_elig<I, 0, STRUCT>(rA, lp, pmw, gb, wrow, L HC_LU_WORK_PASS);
         }
         return;
     }
@@ -667,13 +641,13 @@ __device__ __forceinline__ void lu_step_body(cf (&rA)[NV], cf &rB, int &rowid, u
     // the dense re-solve: one test per group for the pivot lane's store and the
     // update of the rows below (round 4; the dense steps may hold inf and NaN,
     // so the pivot row cannot take a zero multiplier there)
-    lu_store_update<I, 0, CH>(rA, cmk(lp.x, lp.y), pmw, gb, L, is_piv, below HC_LU_WORK_PASS);
+    lu_store_update<I, 0>(rA, cmk(lp.x, lp.y), pmw, gb, L, is_piv, below HC_LU_WORK_PASS);
 }
 
 // One pivot step: the pivot search, then lu_step_body.  !DENSE: a pivot
 // outside the fast reciprocal range sets `redo` (the solve goes on with
 // garbage, the caller discards it and solves densely).
-template <int I, bool DENSE, int CH, int LAT, bool STRUCT>
+template <int I, bool DENSE, int LAT, bool STRUCT>
 __device__ __forceinline__ void lu_forward(cf (&rA)[NV], cf &rB, int &rowid, uint32_t &pat, int lane, int r, int hb,
                                            bool row_lane, PivF &my, LUBuf &L, cf *scr, bool &redo,
                                            unsigned long long elig_m HC_LU_WORK_ARG) {
@@ -781,10 +755,10 @@ __device__ __forceinline__ void lu_forward(cf (&rA)[NV], cf &rB, int &rowid, uin
             pl1 = 32 + __builtin_ctz(mhi);
         }
         HC_ISA_MARK_I("lu_pattern", I);
-        lu_step_body<I, DENSE, CH, LAT, STRUCT>(rA, rB, rowid, pat, my, L, scr, is_piv, pl0, pl1, reg_s, oo_s,
-                                                elig HC_LU_WORK_PASS);
-        lu_forward<I + 1, DENSE, CH, LAT, STRUCT>(rA, rB, rowid, pat, lane, r, hb, row_lane, my, L, scr, redo,
-                                                  elig_m & ~piv_m HC_LU_WORK_PASS);
+        lu_step_body<I, DENSE, LAT, STRUCT>(rA, rB, rowid, pat, my, L, scr, is_piv, pl0, pl1, reg_s, oo_s,
+                                            elig HC_LU_WORK_PASS);
+        lu_forward<I + 1, DENSE, LAT, STRUCT>(rA, rB, rowid, pat, lane, r, hb, row_lane, my, L, scr, redo,
+                                              elig_m & ~piv_m HC_LU_WORK_PASS);
     }
 }
 
@@ -841,13 +815,12 @@ __device__ __forceinline__ void lu_backward(const cf (&rA)[NV], cf &rB, int rowi
 // rows (row r writes column group J at scratch[2r + J]); the caller's data
 // there is lost.
 constexpr int LU_SCRATCH_CF = 2 * 31 + 32;   // 94: lane r's window scratch[2r .. 2r + 31]
-template <bool DENSE, int CH = LU_CHUNK, int LAT = 0, bool STRUCT = false>
+template <bool DENSE, int LAT = 0, bool STRUCT = false>
 __device__ __forceinline__ cf lu_solve(cf (&rA)[NV], cf rB, int lane, uint32_t pattern, LUBuf &L, cf *scratch,
                                       bool &redo, unsigned long long count_mask = ~0ull);
-template <bool DENSE, int CH, int LAT, bool STRUCT>
+template <bool DENSE, int LAT, bool STRUCT>
 __device__ __forceinline__ cf lu_solve(cf (&rA)[NV], cf rB, int lane, uint32_t pattern, LUBuf &L, cf *scratch,
                                       bool &redo, unsigned long long count_mask) {
-    static_assert(CH == 2, "column groups of 2 (the scratch windows are 16 B)");
     (void)count_mask;   // diagnostic builds (HC_DIAG_LUWORK): lanes whose executed work is counted
     const int r = lane & 31, hb = lane & 32;
     const bool row_lane = r < NV;
@@ -878,8 +851,8 @@ __device__ __forceinline__ cf lu_solve(cf (&rA)[NV], cf rB, int lane, uint32_t p
     PivF my{pf2{0.0f, 0.0f}};
 #ifdef HC_DIAG_LUWORK
     LuWork lu_work_acc{0ull, count_mask, 0ull, 0ull, 0ull};
-    lu_forward<0, DENSE, CH, LAT, STRUCT>(rA, rB, rowid, pat, lane, r, hb, row_lane, my, L, scratch + 2 * r, redo,
-                                          __builtin_amdgcn_ballot_w64(row_lane), lu_work_acc);
+    lu_forward<0, DENSE, LAT, STRUCT>(rA, rB, rowid, pat, lane, r, hb, row_lane, my, L, scratch + 2 * r, redo,
+                                      __builtin_amdgcn_ballot_w64(row_lane), lu_work_acc);
     const unsigned long long solves = (unsigned long long)__builtin_popcountll(count_mask & __builtin_amdgcn_ballot_w64(row_lane)) / NV;
     if (lane == 0 && !DENSE && !redo) {   // sparse solves that completed, and their work
         atomicAdd(&g_diag_luwork[0], lu_work_acc.acc);
@@ -890,8 +863,8 @@ __device__ __forceinline__ cf lu_solve(cf (&rA)[NV], cf rB, int lane, uint32_t p
     }
     if (lane == 0 && DENSE) atomicAdd(&g_diag_luwork[2], solves);   // dense (re-)solves
 #else
-    lu_forward<0, DENSE, CH, LAT, STRUCT>(rA, rB, rowid, pat, lane, r, hb, row_lane, my, L, scratch + 2 * r, redo,
-                                          __builtin_amdgcn_ballot_w64(row_lane));
+    lu_forward<0, DENSE, LAT, STRUCT>(rA, rB, rowid, pat, lane, r, hb, row_lane, my, L, scratch + 2 * r, redo,
+                                      __builtin_amdgcn_ballot_w64(row_lane));
 #endif
 #ifdef HC_DIAG_PHASES
     // diagnostic build: the forward / back-substitution boundary of this wave's

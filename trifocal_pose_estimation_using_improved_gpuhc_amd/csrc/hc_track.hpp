@@ -10,8 +10,6 @@ namespace hc {
 
 // Phases of a path slot (one per half-wave):
 enum : int { PH_DEQ = 0, PH_BEGIN = 1, PH_STAGE = 2, PH_FINISH = 3, PH_IDLE = 4 };
-// the type of EvalTables::hxd (the size of the body's LDS staging area, !GTAB)
-typedef uint32_t T_hxd_t[HX_NSLOT / 2][32];
 
 #ifdef HC_DIAG_TIMES
 // diagnostic build: [0] first wave start, [1] last wave exit (s_memrealtime),
@@ -43,14 +41,11 @@ __device__ unsigned long long g_diag_phase[13];
 #ifndef HC_SMALL_LAT
 #define HC_SMALL_LAT 16
 #endif
-// The abort kernels (k_track<true, ...>, k_track_grouped, k_track_gated): term
-// tables read from the workspace (L1/L2), 4 waves/SIMD (the scoring path needs
-// the registers); the tables moved out of the LDS in round 5, where the other
-// waves' LDS traffic was delaying the earliest hypotheses (time to the first
-// pose -2.8 %, profiles/r5q_ttfp_probe.jsonl)
-#ifndef HC_ABORT_GTAB
-#define HC_ABORT_GTAB true
-#endif
+// The abort kernels (k_track<true, ...>, k_track_grouped, k_track_gated):
+// 4 waves/SIMD (the scoring path needs the registers).  Their term tables left
+// the LDS in round 5, where the other waves' LDS traffic was delaying the
+// earliest hypotheses (time to the first pose -2.8 %,
+// profiles/r5q_ttfp_probe.jsonl); no kernel stages them there any more
 #ifndef HC_ABORT_MINW
 #define HC_ABORT_MINW 4
 #endif
@@ -59,24 +54,13 @@ __device__ unsigned long long g_diag_phase[13];
 #ifndef HC_ABORT_PRIO_DIV
 #define HC_ABORT_PRIO_DIV 16
 #endif
-// Retry reuse (hc_track_body.inc): 1: a half about to retry a rejected step with
-// its kept first slope is not suspended at that boundary (the suspension would
-// overwrite the slope); 0: it is suspended like any other and recomputes the
-// slope after its resume
-#ifndef HC_RETRY_HOLD
-#define HC_RETRY_HOLD 1
-#endif
-// Whether tracking launches that fill at most half of the path slots go to
-// k_track_small (launch_track, hc_kernels.hip); 0: never
-#ifndef HC_SMALL_LAUNCH
-#define HC_SMALL_LAUNCH 1
-#endif
 
 // kernel_GPUHC_trifocal_pose_PH_CodeOpt_TrunPaths (..._TrunPaths.cu:45-290) and,
 // with ABORT, ..._TrunPaths_TrunRANSAC (..._TrunRANSAC.cu:45-327).
-// MINW: waves per SIMD the register allocation targets.  GTAB: the term tables
-// are read from the workspace (global, L1/L2-resident) instead of being staged
-// in LDS, which leaves 27.6 KB LDS per workgroup (5 workgroups per CU).
+// MINW: waves per SIMD the register allocation targets.  The term tables are
+// read from the workspace (global, L1/L2-resident), which leaves 27.6 KB LDS
+// per workgroup (5 workgroups per CU); GTAB once chose between that and a
+// staging copy in LDS, and is always true.
 // ARCH: the archived ablation semantics (KArgs::truncate / explicit_rk read at
 // run time); a separate instantiation so the headline kernel carries neither
 // switch and the two show up under their own names in a kernel trace.
@@ -89,13 +73,15 @@ __device__ unsigned long long g_diag_phase[13];
 // equations permuted) tracks, through the structure-agnostic LU.
 template <bool ABORT, int MINW, bool GTAB, bool ARCH = false, bool LUS = true>
 __global__ void __launch_bounds__(WG_THREADS, MINW) k_track(KArgs a) {
+    // GTAB remains only for the kernel's name (traces, scripts/isa_phases.py),
+    // until a version that moves the build id anyway
+    static_assert(GTAB, "the term tables are read from the workspace");
     constexpr bool GROUPED = false, GATED = false;   // (k_track_grouped, k_track_gated below)
     // LU (hc_lu.hpp): the abort kernel's time to the first pose is a lone
     // path's latency, so it runs the latency mode (one LDS round trip per pivot
     // step, in batches of HC_LU_LATB_COLS columns); the tracking kernel the
     // throughput mode (profiles/r6x_ab_track_latency_lu.jsonl: the latency mode
     // is 9 % slower per config-2 launch there)
-    constexpr int LUCH = LU_CHUNK;
     constexpr int LULAT = ABORT ? HC_LU_LATB_COLS : 0;
 #include "hc_track_body.inc"
 }
@@ -107,23 +93,21 @@ __global__ void __launch_bounds__(WG_THREADS, MINW) k_track(KArgs a) {
 // HC_SMALL_MINW waves/SIMD and HC_SMALL_LAT columns per LU batch (above).
 template <bool LUS>
 __global__ void __launch_bounds__(WG_THREADS, HC_SMALL_MINW) k_track_small(KArgs a) {
-    constexpr bool ABORT = false, GTAB = true, ARCH = false, GROUPED = false, GATED = false;
-    constexpr int LUCH = LU_CHUNK;
+    constexpr bool ABORT = false, ARCH = false, GROUPED = false, GATED = false;
     constexpr int LULAT = HC_SMALL_LAT;
 #include "hc_track_body.inc"
 }
 
 // Grouped (multi-triplet) abort launches (hcGroupedAbortArgs): the abort
-// instantiation's body and configuration (k_track<true, HC_ABORT_MINW,
-// HC_ABORT_GTAB>) with GROUPED on: the scoring set, K and the found flag are
-// those of the path's own triplet, looked up from the slot's sample where they
-// are used (nothing of a group is carried across the stage loop).  A kernel of
-// its own rather than one more template parameter of k_track, so the existing
+// instantiation's body and configuration (k_track<true, HC_ABORT_MINW, true>)
+// with GROUPED on: the scoring set, K and the found flag are those of the
+// path's own triplet, looked up from the slot's sample where they are used
+// (nothing of a group is carried across the stage loop).  A kernel of its own
+// rather than one more template parameter of k_track, so the existing
 // instantiations keep their code and their names in kernel traces.
 template <bool LUS>
 __global__ void __launch_bounds__(WG_THREADS, HC_ABORT_MINW) k_track_grouped(KArgs a) {
-    constexpr bool ABORT = true, GTAB = HC_ABORT_GTAB, ARCH = false, GROUPED = true, GATED = false;
-    constexpr int LUCH = LU_CHUNK;
+    constexpr bool ABORT = true, ARCH = false, GROUPED = true, GATED = false;
     constexpr int LULAT = HC_LU_LATB_COLS;
 #include "hc_track_body.inc"
 }
@@ -135,8 +119,7 @@ __global__ void __launch_bounds__(WG_THREADS, HC_ABORT_MINW) k_track_grouped(KAr
 // of its own, so the grouped instantiations keep their code.
 template <bool LUS>
 __global__ void __launch_bounds__(WG_THREADS, HC_ABORT_MINW) k_track_gated(KArgs a) {
-    constexpr bool ABORT = true, GTAB = HC_ABORT_GTAB, ARCH = false, GROUPED = true, GATED = true;
-    constexpr int LUCH = LU_CHUNK;
+    constexpr bool ABORT = true, ARCH = false, GROUPED = true, GATED = true;
     constexpr int LULAT = HC_LU_LATB_COLS;
 #include "hc_track_body.inc"
 }

@@ -1,6 +1,6 @@
 // The body of the tracker kernels k_track, k_track_small, k_track_grouped and k_track_gated (hc_track.hpp),
-// included inside each: ABORT, GROUPED, GATED, GTAB, ARCH, LUS, LUCH and LULAT are
-// their template parameters or constants, `a` their argument block.  GATED
+// included inside each: ABORT, GROUPED, GATED, ARCH, LUS and LULAT are their
+// template parameters or constants, `a` their argument block.  GATED
 // (k_track_gated) replaces the scoring block of PH_FINISH and nothing else.
 // Included textually on purpose (DESIGN.md §3.2): a change here is a codegen
 // change of all twelve instantiations.  The other names it takes from its
@@ -10,15 +10,12 @@
 //   hc_ring.hpp    ld_rlx, ld_cf_rlx, st_u64_h, ld_u64_h, pack2, drain_stores,
 //                  ring_push, ring_pop, ring_pop_paired, ring_wait_ticks
 //   hc_score.hpp   score_half, JointCounts, score_joint_half
-//   hc_track.hpp   PH_*, T_hxd_t, HC_ABORT_PRIO_DIV, the HC_DIAG_* globals
+//   hc_track.hpp   PH_*, HC_ABORT_PRIO_DIV, the HC_DIAG_* globals
 //   hc_device.hpp, hc_slot.hpp, hc_eval.hpp, hc_lu.hpp, hc_pose_device.hpp
 //                  the arithmetic, SlotLDS, the evaluations, lu_solve, scenes
 // kernel_GPUHC_trifocal_pose_PH_CodeOpt_TrunPaths (..._TrunPaths.cu:45-290) and,
 // with ABORT, ..._TrunPaths_TrunRANSAC (..._TrunRANSAC.cu:45-327).
     constexpr bool LUSTRUCT = LUS;
-    constexpr int TAB_BYTES =
-        GTAB ? 16 : (int)(sizeof(uint2) * HT_TERMS * 32 + sizeof(uint32_t) * HX_SLOT_CAP * 32 + sizeof(T_hxd_t));
-    __shared__ __attribute__((aligned(16))) char s_tab[TAB_BYTES];
     __shared__ cf s_sp[NPP];
     __shared__ SlotLDS s_slot[2 * WAVES_PER_WG];
     Workspace *ws = a.ws;
@@ -27,16 +24,10 @@
     if ((T->lu_struct == 1u) != LUSTRUCT) return;   // the other instantiation tracks this table
     // time slicing: this launch's ring epoch (bumped by k_prep_tables)
     const unsigned epoch = (!ABORT && a.slice_q > 0) ? ld_rlx(&a.rq[RQ_EPOCH]) : 0u;
-    const uint2 *s_ht = GTAB ? T->ht : reinterpret_cast<const uint2 *>(s_tab);
-    const uint32_t *s_hx = GTAB ? T->hx : reinterpret_cast<const uint32_t *>(s_ht + HT_TERMS * 32);
-    const uint32_t *s_hxd = GTAB ? &T->hxd[0][0] : s_hx + HX_SLOT_CAP * 32;
-    if constexpr (!GTAB) {
-        uint2 *t_ht = reinterpret_cast<uint2 *>(s_tab);
-        uint32_t *t_hx = reinterpret_cast<uint32_t *>(t_ht + HT_TERMS * 32), *t_hxd = t_hx + HX_SLOT_CAP * 32;
-        for (int i = threadIdx.x; i < HX_SLOT_CAP * 32; i += WG_THREADS) t_hx[i] = T->hx[i];   // padded table
-        for (int i = threadIdx.x; i < HT_TERMS * 32; i += WG_THREADS) t_ht[i] = T->ht[i];
-        for (int i = threadIdx.x; i < HX_NSLOT / 2 * 32; i += WG_THREADS) t_hxd[i] = (&T->hxd[0][0])[i];
-    }
+    // the term tables, read from the workspace (L1/L2-resident)
+    const uint2 *s_ht = T->ht;
+    const uint32_t *s_hx = T->hx;
+    const uint32_t *s_hxd = &T->hxd[0][0];
     if (threadIdx.x < NPP) s_sp[threadIdx.x] = a.start_params[threadIdx.x];
     {
         float *z = reinterpret_cast<float *>(s_slot);
@@ -303,8 +294,10 @@
                 // and the issue-priority ones below are in commit 02bc69d)
                 // (a half about to retry with a kept k1 is not suspended, the block
                 // would be overwritten with x: it runs the retry first and is
-                // suspendable at the next boundary.  HC_RETRY_HOLD, hc_track.hpp)
-                if (!ABORT && !done && a.slice_q > 0 && piece >= a.slice_q && !(REUSE && HC_RETRY_HOLD && k1v)) {
+                // suspendable at the next boundary.  Suspending it like any other and
+                // recomputing the slope after the resume measured 0.06-0.17 ms slower
+                // per config-2 launch: DESIGN.md, retry reuse with plain invalidation)
+                if (!ABORT && !done && a.slice_q > 0 && piece >= a.slice_q && !(REUSE && k1v)) {
                     // time slice used up: suspend for a new path (its ticket
                     // claimed here), else swap with a suspended path, else
                     // keep running
@@ -534,9 +527,9 @@
         // (a dense re-solve evaluates dH/dx again)
         static_assert(ENT_CAP >= LU_SCRATCH_CF && offsetof(SlotLDS, ent) % 16 == 0, "LU scratch in SlotLDS::ent");
 #ifdef HC_DIAG_LUWORK
-        cf k = lu_solve<false, LUCH, LULAT, LUSTRUCT>(rA, rB, lane_v, row_pat, LB, S.ent, redo, __ballot(act));   // :188 / :224
+        cf k = lu_solve<false, LULAT, LUSTRUCT>(rA, rB, lane_v, row_pat, LB, S.ent, redo, __ballot(act));   // :188 / :224
 #else
-        cf k = lu_solve<false, LUCH, LULAT, LUSTRUCT>(rA, rB, lane_v, row_pat, LB, S.ent, redo);                  // :188 / :224
+        cf k = lu_solve<false, LULAT, LUSTRUCT>(rA, rB, lane_v, row_pat, LB, S.ent, redo);                  // :188 / :224
 #endif
         HC_ISA_MARK("ctl_redo");
         if (__builtin_expect(redo, 0)) {
@@ -567,9 +560,9 @@
             gather_hx(rA, &s_rowc[0][0], S, r_r);
             wave_lds_sync();
 #ifdef HC_DIAG_LUWORK
-            k = lu_solve<true, LUCH>(rA, rb, lane_v, row_pat, LB, S.ent, redo, __ballot(act_r));
+            k = lu_solve<true>(rA, rb, lane_v, row_pat, LB, S.ent, redo, __ballot(act_r));
 #else
-            k = lu_solve<true, LUCH>(rA, rb, lane_v, row_pat, LB, S.ent, redo);
+            k = lu_solve<true>(rA, rb, lane_v, row_pat, LB, S.ent, redo);
 #endif
         }
         wave_lds_sync();
