@@ -1,6 +1,8 @@
 """CPU tests of the C-ABI boundary and the native host data layer.
 
 * the library exports exactly the entry points include/*.h declare;
+* the binding's signature table agrees with the prototypes, and its struct
+  mirrors with the layouts the C compiler gives the headers;
 * argument validation returns the documented hcStatus codes without touching
   a device (no compute call is made here);
 * the host layer (readers, RANSAC sample generation, sample split, solution
@@ -21,22 +23,118 @@ from conftest import ROOT
 INCLUDE = os.path.join(ROOT, "include")
 
 
-def _declared_c_functions(header):
-    """Function names declared in a C header (outside comments)."""
+def _prototypes(header):
+    """{name: (return type, [parameter, ...])} of the functions a C header
+    declares (outside comments); `(void)` is no parameter."""
     src = open(os.path.join(INCLUDE, header)).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     src = re.sub(r"//[^\n]*", "", src)
-    names = re.findall(r"^[A-Za-z_][\w\s\*]*?\b(hc_\w+)\s*\(", src, flags=re.M)
-    return set(names)
+    out = {}
+    for ret, name, params in re.findall(r"^([A-Za-z_][\w\s\*]*?)\b(hc_\w+)\s*\(([^()]*)\)", src, flags=re.M):
+        params = [" ".join(p.split()) for p in params.split(",")]
+        out[name] = (" ".join(ret.split()), [] if params == ["void"] else params)
+    return out
+
+
+def _declared_c_functions(header):
+    """Function names declared in a C header (outside comments)."""
+    return set(_prototypes(header))
+
+
+def _headers():
+    return [h for h in sorted(os.listdir(INCLUDE)) if h.endswith(".h")]
 
 
 def _all_declared():
     """Every function the public headers declare (include/*.h)."""
     names = set()
-    for h in sorted(os.listdir(INCLUDE)):
-        if h.endswith(".h"):
-            names |= _declared_c_functions(h)
+    for h in _headers():
+        names |= _declared_c_functions(h)
     return names
+
+
+# C scalar type of a prototype -> the ctypes class the signature table must give it
+_SCALARS = {"int": C.c_int, "unsigned": C.c_uint, "size_t": C.c_size_t, "double": C.c_double,
+            "uint64_t": C.c_uint64}
+_RETURNS = {"void": None, "hcStatus": C.c_int, "int": C.c_int, "unsigned": C.c_uint, "size_t": C.c_size_t,
+            "const char *": C.c_char_p}
+
+
+def _is_pointer_class(t):
+    return t in (C.c_void_p, C.c_char_p) or (isinstance(t, type) and issubclass(t, C._Pointer))
+
+
+def test_signature_table_matches_the_prototypes():
+    """Every entry of _abi.SIGNATURES against its prototype in include/*.h: the
+    same set of names, the parameter count, pointer (`*` or hcStream) against
+    scalar for each parameter -- a scalar also by its type --, and the return
+    type's class."""
+    from trifocal_pose_estimation_using_improved_gpuhc_amd import _abi
+    protos = {}
+    for h in _headers():
+        for name, p in _prototypes(h).items():
+            assert protos.setdefault(name, p) == p, f"{name} is declared twice, differently"
+    assert len(protos) == 50
+    assert {s.name for s in _abi.SIGNATURES} == set(protos)
+    assert len(_abi.SIGNATURES) == len(protos), "a name is listed twice"
+    for s in _abi.SIGNATURES:
+        ret, params = protos[s.name]
+        assert ret in _RETURNS, f"{s.name}: return type {ret!r}"
+        assert s.restype is _RETURNS[ret], f"{s.name}: returns {ret!r}, bound as {s.restype}"
+        assert len(s.argtypes) == len(params), f"{s.name}: {len(params)} parameters, {len(s.argtypes)} argtypes"
+        for k, (p, t) in enumerate(zip(params, s.argtypes)):
+            if "*" in p or p.startswith("hcStream "):
+                assert _is_pointer_class(t), f"{s.name} parameter {k} ({p}) is a pointer, bound as {t}"
+            else:
+                ctype = " ".join(w for w in p.split()[:-1] if w != "const")
+                assert ctype in _SCALARS, f"{s.name} parameter {k}: type {ctype!r}"
+                assert t is _SCALARS[ctype], f"{s.name} parameter {k} ({p}) is bound as {t}"
+    # what lib() bound is the table
+    L = _abi.lib()
+    for s in _abi.SIGNATURES:
+        fn = getattr(L, s.name)
+        assert fn.restype is s.restype and tuple(fn.argtypes) == tuple(s.argtypes), s.name
+
+
+def _c_compiler():
+    import shutil
+    cc = next((c for c in ("cc", "gcc", "clang", "/opt/rocm/llvm/bin/clang", "/opt/rocm/lib/llvm/bin/clang")
+               if shutil.which(c)), None)
+    assert cc, "no C compiler found"
+    return cc
+
+
+def test_struct_mirrors_match_the_headers_by_the_c_compiler(tmp_path):
+    """sizeof and every field's offsetof of the mirrored structs, from the
+    headers through the host C compiler, equal the ctypes classes' and the two
+    numpy dtypes' (tracker.PATH_STATS_DTYPE, multi.GROUP_DTYPE)."""
+    from trifocal_pose_estimation_using_improved_gpuhc_amd import _abi, multi, tracker
+    structs = [_abi.hcTrackSettings, _abi.hcTrackArgs, _abi.hcAbortArgs, _abi.hcTripletGroup,
+               _abi.hcGroupedAbortArgs, _abi.hcJointGate, _abi.hcIpcHandle, _abi.hcPoseSelection,
+               _abi.hcTrifocalSelection]
+    # [(C struct, field names, size, field offsets)] as Python has them
+    mirrors = [(s.__name__, [f[0] for f in s._fields_], C.sizeof(s), [getattr(s, f[0]).offset for f in s._fields_])
+               for s in structs]
+    mirrors += [(name, list(dt.names), dt.itemsize, [dt.fields[f][1] for f in dt.names])
+                for name, dt in (("hcPathStats", tracker.PATH_STATS_DTYPE), ("hcTripletGroup", multi.GROUP_DTYPE))]
+    lines = ['#include <stddef.h>', '#include <stdio.h>', '#include "hc_trifocal.h"', '#include "hc_pose.h"',
+             'int main(void) {']
+    for name, fields, _, _ in mirrors:
+        args = "".join(f", offsetof({name}, {f})" for f in fields)
+        lines.append(f'    printf("{"%zu " * (1 + len(fields))}\\n", sizeof({name}){args});')
+    lines += ['    return 0;', '}', '']
+    src = tmp_path / "layout.c"
+    src.write_text("\n".join(lines))
+    exe = tmp_path / "layout"
+    subprocess.run([_c_compiler(), "-I", INCLUDE, "-o", str(exe), str(src)], check=True, timeout=120)
+    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True, timeout=30).stdout.splitlines()
+    assert len(out) == len(mirrors) == 11
+    for (name, fields, size, offsets), line in zip(mirrors, out):
+        got = [int(v) for v in line.split()]
+        assert got[0] == size, f"sizeof({name}): C {got[0]}, Python {size}"
+        assert got[1:] == offsets, f"{name}: C offsets {dict(zip(fields, got[1:]))}, Python {offsets}"
+    # the nine structs' sizes at ABI version 2
+    assert [m[2] for m in mirrors[:9]] == [12, 104, 56, 24, 56, 16, 64, 136, 136]
 
 
 def test_headers_declare_the_bound_symbols():

@@ -1,13 +1,22 @@
-"""ctypes binding of the C-ABI in include/hc_trifocal.h and include/hc_host.h.
+"""ctypes binding of the C-ABI in include/*.h.
 
 The native library (lib/libhc_trifocal.so, HIP for gfx950) is the product: this
 module only marshals pointers.  It raises if the library is missing -- there is
 no CPU fallback anywhere in the product path.
+
+The boundary is described once: the ctypes mirrors of the argument structs and
+SIGNATURES, one (name, restype, argtypes, optional) entry per declared function.
+lib() binds the table, DECLARED_SYMBOLS is its names, and tests/test_abi_host.py
+holds both against the headers (layouts through the C compiler, signatures
+against the prototypes).  Callers go through two helpers: ptr(x), the c_void_p
+of a tensor, array or stream, and call(name, *args), which raises HCError on a
+status other than HC_SUCCESS.
 """
 from __future__ import annotations
 
 import ctypes as C
 import os
+from collections import namedtuple
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 # HC_TRIFOCAL_LIB: an alternative build of the same library (A/B experiments,
@@ -115,11 +124,86 @@ class hcIpcHandle(C.Structure):
     _fields_ = [("reserved", C.c_ubyte * 64)]
 
 
+# One entry per function of include/*.h: restype and argtypes as the prototype
+# reads (None for void; c_void_p for device and host buffers and for hcStream,
+# POINTER(struct) for the argument structs, c_char_p for paths).  optional: a
+# build from before the symbol existed, loaded through HC_TRIFOCAL_LIB for an
+# A/B run, may lack it; it is then left unbound and call() says so.  The product
+# library exports all of them (tests/test_abi_host.py, which also checks every
+# entry against its prototype).
+Sig = namedtuple("Sig", "name restype argtypes optional", defaults=(False,))
+
+_i, _u, _z, _p, _s, _ST = C.c_int, C.c_uint, C.c_size_t, C.c_void_p, C.c_char_p, C.c_int   # _ST: hcStatus
+_TA = C.POINTER(hcTrackArgs)
+_GA = C.POINTER(hcGroupedAbortArgs)
+_WS = (_p, _z, _p)                                           # workspace, workspace_bytes, stream
+_SUPPORT = (_i, _p, _p, _i, _p, _p, _i, _p, _p, _p)          # the four pose-support calls
+
+SIGNATURES = (
+    # include/hc_trifocal.h
+    Sig("hc_trifocal_workspace_size", _z, ()),
+    Sig("hc_trifocal_workspace_size_for", _z, (_i,)),
+    Sig("hc_trifocal_workspace_size_for_steps", _z, (_i, _i)),
+    Sig("hc_trifocal_2op1p_30x30_track", _ST, (_TA, *_WS)),
+    Sig("hc_trifocal_2op1p_30x30_track_abort", _ST, (_TA, C.POINTER(hcAbortArgs), *_WS)),
+    Sig("hc_trifocal_2op1p_30x30_track_abort_grouped", _ST, (_TA, _GA, *_WS), True),
+    Sig("hc_trifocal_2op1p_30x30_track_abort_gated", _ST, (_TA, _GA, C.POINTER(hcJointGate), *_WS), True),
+    Sig("hc_shared_flag_create", _ST, (C.POINTER(_p), C.POINTER(hcIpcHandle)), True),
+    Sig("hc_shared_flag_memory_kind", _i, (_p,), True),
+    Sig("hc_shared_flag_open", _ST, (C.POINTER(hcIpcHandle), C.POINTER(_p)), True),
+    Sig("hc_shared_flag_reset", _ST, (_p, _p), True),
+    Sig("hc_shared_flag_close", _ST, (_p, _i), True),
+    Sig("hc_trifocal_2op1p_30x30_track_ph_codeopt", _ST, (_TA, *_WS)),
+    Sig("hc_trifocal_2op1p_30x30_track_ph", _ST, (_TA, *_WS)),
+    Sig("hc_trifocal_workspace_status", _ST, (_p,)),
+    Sig("hc_trifocal_read_timings", _ST, (_p, C.POINTER(C.c_double))),
+    Sig("hc_trifocal_read_timestamps", _ST, (_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                             C.POINTER(C.c_double))),
+    Sig("hc_cgesv_30x30_batched", _ST, (_i, _p, _p, _p, _p)),
+    Sig("hc_trifocal_eval_batched", _ST, (_i, _p, _p, _p, _p, _p, _p, _p, *_WS)),
+    Sig("hc_last_error_string", _s, ()),
+    Sig("hc_trifocal_version", _s, ()),
+    Sig("hc_trifocal_abi_version", _i, ()),
+    # include/hc_trifocal_testing.h (test hooks)
+    Sig("hc_trifocal_set_ring_test", None, (_i,)),
+    Sig("hc_trifocal_set_small_launch", None, (_i,), True),
+    Sig("hc_trifocal_set_retry_reuse", None, (_i,), True),
+    Sig("hc_trifocal_ring_check_test", _ST, (_p, _z, _u, _u, _u, _p), True),
+    Sig("hc_lu_struct_pattern", _u, (_i,), True),
+    Sig("hc_lu_group_class", _i, (_i, _i), True),
+    Sig("hc_lu_candidates", _u, (_i,), True),
+    Sig("hc_lu_search_span", _i, (_i,), True),
+    # include/hc_pose.h
+    Sig("hc_trifocal_pose_support", _ST, _SUPPORT),
+    Sig("hc_trifocal_pose_support_grouped", _ST, _SUPPORT, True),
+    Sig("hc_pose_merge", None, (_i, _p, _p, _i, C.POINTER(hcPoseSelection))),
+    Sig("hc_trifocal_pose_support_joint", _ST, _SUPPORT),
+    Sig("hc_trifocal_pose_support_joint_grouped", _ST, _SUPPORT),
+    Sig("hc_trifocal_pose_inlier_mask", _ST, (_p, _i, _p, _p, _p, _p)),
+    Sig("hc_pose_merge_joint", None, (_i, _p, _p, C.POINTER(hcTrifocalSelection))),
+    Sig("hc_pose_residuals", _i, (_p,) * 7),
+    # include/hc_host.h
+    Sig("hc_read_start_sols", _i, (_s, _p)),
+    Sig("hc_read_start_params", _i, (_s, _p)),
+    Sig("hc_read_int_table", _i, (_s, _p, _i)),
+    Sig("hc_read_float_table", _i, (_s, _p, _i)),
+    Sig("hc_count_triplet_edgels", _i, (_s,)),
+    Sig("hc_read_triplet_edgels", _i, (_s, _p, _p, _i)),
+    Sig("hc_split_samples", None, (_i, _i, _p)),
+    Sig("hc_prepare_target_params", None, (_u, _i, _p, _p, _p, _i, _p, _p, _p, _p)),
+    Sig("hc_count_solutions", None, (_i, _p, _p, _p, _p)),
+    Sig("hc_write_converged_sols", _i, (_s, _i, _p, _p)),
+    Sig("hc_add_pixel_noise", None, (_i, _p, _p, C.c_double, C.c_uint64, _p)),
+    Sig("hc_write_triplet_edgels", _i, (_s, _i, _p, _p)),
+)
+DECLARED_SYMBOLS = tuple(s.name for s in SIGNATURES)
+
 _lib = None
 
 
 def lib() -> C.CDLL:
-    """Load the native library (raises HCError if it has not been built)."""
+    """Load the native library (raises HCError if it has not been built) and
+    bind every entry of SIGNATURES it exports."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
@@ -129,111 +213,15 @@ def lib() -> C.CDLL:
         # instead of pulling a second HIP/HSA runtime from /opt/rocm.
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
-        L.hc_trifocal_abi_version.restype = C.c_int
+        for s in SIGNATURES:
+            fn = getattr(L, s.name, None)
+            if fn is None:
+                if s.optional:
+                    continue
+                raise HCError(f"{LIB_PATH} does not export {s.name}")
+            fn.restype, fn.argtypes = s.restype, list(s.argtypes)
         if L.hc_trifocal_abi_version() != ABI_VERSION:
             raise HCError(f"{LIB_PATH}: ABI {L.hc_trifocal_abi_version()}, this binding expects {ABI_VERSION}")
-        L.hc_trifocal_set_ring_test.restype = None
-        L.hc_trifocal_set_ring_test.argtypes = [C.c_int]
-        if hasattr(L, "hc_trifocal_set_small_launch"):   # (test hook, round 6)
-            L.hc_trifocal_set_small_launch.restype = None
-            L.hc_trifocal_set_small_launch.argtypes = [C.c_int]
-        if hasattr(L, "hc_trifocal_set_retry_reuse"):   # (test hook; absent from builds before v10.8)
-            L.hc_trifocal_set_retry_reuse.restype = None
-            L.hc_trifocal_set_retry_reuse.argtypes = [C.c_int]
-        if hasattr(L, "hc_trifocal_ring_check_test"):   # (test hook, round 6)
-            L.hc_trifocal_ring_check_test.restype = C.c_int
-            L.hc_trifocal_ring_check_test.argtypes = [C.c_void_p, C.c_size_t, C.c_uint, C.c_uint, C.c_uint, C.c_void_p]
-        if hasattr(L, "hc_lu_group_class"):   # (test hooks; absent from builds before round 5's LU classes)
-            L.hc_lu_struct_pattern.restype = C.c_uint
-            L.hc_lu_struct_pattern.argtypes = [C.c_int]
-            L.hc_lu_group_class.restype = C.c_int
-            L.hc_lu_group_class.argtypes = [C.c_int, C.c_int]
-        if hasattr(L, "hc_lu_search_span"):
-            L.hc_lu_candidates.restype = C.c_uint
-            L.hc_lu_candidates.argtypes = [C.c_int]
-            L.hc_lu_search_span.restype = C.c_int
-            L.hc_lu_search_span.argtypes = [C.c_int]
-        L.hc_trifocal_workspace_size.restype = C.c_size_t
-        L.hc_trifocal_workspace_size_for.restype = C.c_size_t
-        L.hc_trifocal_workspace_size_for.argtypes = [C.c_int]
-        L.hc_trifocal_workspace_size_for_steps.restype = C.c_size_t
-        L.hc_trifocal_workspace_size_for_steps.argtypes = [C.c_int, C.c_int]
-        L.hc_trifocal_version.restype = C.c_char_p
-        L.hc_last_error_string.restype = C.c_char_p
-        for fn in ("hc_trifocal_2op1p_30x30_track", "hc_trifocal_2op1p_30x30_track_abort",
-                   "hc_trifocal_2op1p_30x30_track_ph_codeopt", "hc_trifocal_2op1p_30x30_track_ph",
-                   "hc_trifocal_workspace_status", "hc_trifocal_read_timings", "hc_trifocal_read_timestamps", "hc_cgesv_30x30_batched", "hc_trifocal_eval_batched"):
-            getattr(L, fn).restype = C.c_int
-        L.hc_trifocal_2op1p_30x30_track.argtypes = [C.POINTER(hcTrackArgs), C.c_void_p, C.c_size_t, C.c_void_p]
-        L.hc_trifocal_2op1p_30x30_track_ph_codeopt.argtypes = [C.POINTER(hcTrackArgs), C.c_void_p, C.c_size_t,
-                                                               C.c_void_p]
-        L.hc_trifocal_2op1p_30x30_track_ph.argtypes = [C.POINTER(hcTrackArgs), C.c_void_p, C.c_size_t, C.c_void_p]
-        L.hc_trifocal_2op1p_30x30_track_abort.argtypes = [C.POINTER(hcTrackArgs), C.POINTER(hcAbortArgs),
-                                                          C.c_void_p, C.c_size_t, C.c_void_p]
-        L.hc_trifocal_read_timings.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
-        L.hc_trifocal_workspace_status.argtypes = [C.c_void_p]
-        L.hc_trifocal_read_timestamps.restype = C.c_int
-        L.hc_trifocal_read_timestamps.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
-                                                  C.POINTER(C.c_double)]
-        L.hc_cgesv_30x30_batched.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.hc_trifocal_eval_batched.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
-                                               C.c_void_p]
-        L.hc_trifocal_pose_support.restype = C.c_int
-        L.hc_trifocal_pose_support.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
-                                               C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        # grouped (multi-triplet) launches (bound where present, as below)
-        if hasattr(L, "hc_trifocal_2op1p_30x30_track_abort_grouped"):
-            L.hc_trifocal_2op1p_30x30_track_abort_grouped.restype = C.c_int
-            L.hc_trifocal_2op1p_30x30_track_abort_grouped.argtypes = [C.POINTER(hcTrackArgs),
-                                                                      C.POINTER(hcGroupedAbortArgs), C.c_void_p,
-                                                                      C.c_size_t, C.c_void_p]
-            L.hc_trifocal_pose_support_grouped.restype = C.c_int
-            L.hc_trifocal_pose_support_grouped.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
-                                                           C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        # the gated abort launch (bound where present: A/B runs load earlier builds)
-        if hasattr(L, "hc_trifocal_2op1p_30x30_track_abort_gated"):
-            L.hc_trifocal_2op1p_30x30_track_abort_gated.restype = C.c_int
-            L.hc_trifocal_2op1p_30x30_track_abort_gated.argtypes = [C.POINTER(hcTrackArgs),
-                                                                    C.POINTER(hcGroupedAbortArgs),
-                                                                    C.POINTER(hcJointGate), C.c_void_p, C.c_size_t,
-                                                                    C.c_void_p]
-        L.hc_pose_merge.restype = None
-        L.hc_pose_merge.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(hcPoseSelection)]
-        L.hc_trifocal_pose_support_joint.restype = C.c_int
-        L.hc_trifocal_pose_support_joint.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
-                                                     C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.hc_trifocal_pose_support_joint_grouped.restype = C.c_int
-        L.hc_trifocal_pose_support_joint_grouped.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
-                                                             C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.hc_trifocal_pose_inlier_mask.restype = C.c_int
-        L.hc_trifocal_pose_inlier_mask.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.hc_pose_merge_joint.restype = None
-        L.hc_pose_merge_joint.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.POINTER(hcTrifocalSelection)]
-        L.hc_pose_residuals.restype = C.c_int
-        L.hc_pose_residuals.argtypes = [C.c_void_p] * 6 + [C.c_void_p]
-        L.hc_add_pixel_noise.restype = None
-        L.hc_add_pixel_noise.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_uint64, C.c_void_p]
-        L.hc_write_triplet_edgels.restype = C.c_int
-        L.hc_write_triplet_edgels.argtypes = [C.c_char_p, C.c_int, C.c_void_p, C.c_void_p]
-        L.hc_write_converged_sols.restype = C.c_int
-        L.hc_write_converged_sols.argtypes = [C.c_char_p, C.c_int, C.c_void_p, C.c_void_p]
-        L.hc_prepare_target_params.argtypes = [C.c_uint, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
-                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        for fn in ("hc_read_start_sols", "hc_read_start_params", "hc_read_int_table", "hc_read_float_table",
-                   "hc_count_triplet_edgels", "hc_read_triplet_edgels"):
-            getattr(L, fn).restype = C.c_int
-        # (bound only where present: A/B runs load earlier builds through HC_TRIFOCAL_LIB;
-        # the product library exports them, tests/test_abi_host.py)
-        if hasattr(L, "hc_shared_flag_create"):
-            for fn in ("hc_shared_flag_create", "hc_shared_flag_open", "hc_shared_flag_reset", "hc_shared_flag_close"):
-                getattr(L, fn).restype = C.c_int
-            L.hc_shared_flag_create.argtypes = [C.POINTER(C.c_void_p), C.POINTER(hcIpcHandle)]
-            L.hc_shared_flag_open.argtypes = [C.POINTER(hcIpcHandle), C.POINTER(C.c_void_p)]
-            L.hc_shared_flag_reset.argtypes = [C.c_void_p, C.c_void_p]
-            L.hc_shared_flag_close.argtypes = [C.c_void_p, C.c_int]
-            L.hc_shared_flag_memory_kind.restype = C.c_int
-            L.hc_shared_flag_memory_kind.argtypes = [C.c_void_p]
         _lib = L
     return _lib
 
@@ -244,26 +232,26 @@ def check(status: int, what: str) -> None:
         raise HCError(f"{what} failed: {HC_STATUS.get(status, status)} ({detail})")
 
 
-# Exported symbols that include/*.h declare (tests check the library exports all of them).
-DECLARED_SYMBOLS = (
-    "hc_trifocal_workspace_size", "hc_trifocal_workspace_size_for", "hc_trifocal_workspace_size_for_steps", "hc_trifocal_2op1p_30x30_track", "hc_trifocal_2op1p_30x30_track_abort",
-    "hc_trifocal_2op1p_30x30_track_ph_codeopt", "hc_trifocal_2op1p_30x30_track_ph",
-    "hc_trifocal_workspace_status", "hc_trifocal_read_timings", "hc_trifocal_read_timestamps", "hc_cgesv_30x30_batched", "hc_trifocal_eval_batched", "hc_trifocal_version",
-    "hc_last_error_string", "hc_trifocal_abi_version", "hc_trifocal_set_ring_test",
-    "hc_trifocal_ring_check_test", "hc_trifocal_set_small_launch", "hc_trifocal_set_retry_reuse",
-    "hc_lu_struct_pattern", "hc_lu_group_class", "hc_lu_candidates", "hc_lu_search_span",
-    "hc_shared_flag_create", "hc_shared_flag_open", "hc_shared_flag_reset", "hc_shared_flag_close",
-    "hc_shared_flag_memory_kind",
-    "hc_read_start_sols", "hc_read_start_params", "hc_read_int_table", "hc_read_float_table",
-    "hc_count_triplet_edgels", "hc_read_triplet_edgels", "hc_split_samples", "hc_prepare_target_params",
-    "hc_count_solutions",
-    "hc_trifocal_2op1p_30x30_track_abort_grouped", "hc_trifocal_pose_support_grouped",
-    "hc_trifocal_pose_support", "hc_pose_merge", "hc_pose_residuals", "hc_write_converged_sols",
-    "hc_add_pixel_noise", "hc_write_triplet_edgels",
-    "hc_trifocal_pose_support_joint", "hc_trifocal_pose_support_joint_grouped", "hc_trifocal_pose_inlier_mask",
-    "hc_pose_merge_joint",
-    "hc_trifocal_2op1p_30x30_track_abort_gated",
-)
+def call(name: str, *args) -> None:
+    """Call the hcStatus-returning entry point `name`; a status other than
+    HC_SUCCESS raises HCError, and so does a symbol the loaded build lacks."""
+    fn = getattr(lib(), name, None)
+    if fn is None:
+        raise HCError(f"{LIB_PATH} does not export {name}")
+    check(fn(*args), name)
+
+
+def ptr(x):
+    """The c_void_p of a buffer or stream: a torch tensor's device (or host)
+    address, a numpy array's (the pointer keeps the array alive), a torch
+    stream's hipStream_t; None is NULL."""
+    if x is None:
+        return C.c_void_p()
+    if hasattr(x, "data_ptr"):
+        return C.c_void_p(x.data_ptr())
+    if hasattr(x, "cuda_stream"):
+        return C.c_void_p(x.cuda_stream)
+    return x.ctypes.data_as(C.c_void_p)
 
 
 def _fatbin_digest(path: str) -> str | None:

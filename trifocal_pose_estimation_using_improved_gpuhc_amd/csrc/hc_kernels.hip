@@ -52,12 +52,32 @@ static size_t ws_bytes_needed() { return (sizeof(Workspace) + 255) & ~(size_t)25
 // this launch's ring (256-B aligned) and may overwrite cleared entries past
 // it: k_prep_tables keeps that span as the dirty range (RQ_DLO, RQ_DHI) and
 // re-zeroes it when a later launch's ring covers it.
-static size_t ring_bytes(unsigned long long cap) { return ((size_t)cap * sizeof(unsigned long long) + 255) & ~(size_t)255; }
-static size_t ws_bytes_for(long long paths, int max_steps) {
+struct SliceLayout {
+    size_t rq, ring, susp;                // byte offsets from the workspace's base
+    size_t total;                         // workspace bytes that hold all of it (hc_trifocal_workspace_size_for_steps)
+    unsigned long long ring_cap;          // ring entries
+    size_t susp_entry0, susp_entry1;      // the suspend blocks' span in ring-entry units (PrepArgs)
+};
+static SliceLayout slice_layout(long long paths, int max_steps) {
     if (paths < 0) paths = 0;
     if (max_steps < 0) max_steps = 0;
-    return ws_bytes_needed() + RQ_WORDS * sizeof(unsigned) + ring_bytes(ring_entries(paths, max_steps)) +
-           (size_t)paths * SUSP_WORDS * sizeof(unsigned long long);
+    SliceLayout a;
+    a.ring_cap = ring_entries(paths, max_steps);
+    const size_t ring_bytes = ((size_t)a.ring_cap * sizeof(unsigned long long) + 255) & ~(size_t)255;
+    a.rq = ws_bytes_needed();
+    a.ring = a.rq + RQ_WORDS * sizeof(unsigned);
+    a.susp = a.ring + ring_bytes;
+    a.total = a.susp + (size_t)paths * SUSP_WORDS * sizeof(unsigned long long);
+    a.susp_entry0 = ring_bytes / 8;
+    a.susp_entry1 = a.susp_entry0 + (size_t)paths * SUSP_WORDS;
+    return a;
+}
+// Time slicing when the workspace has room for the area and the step counters
+// fit the suspend block (slice_fits); KArgs::ring_cap and PrepArgs::susp_entry1
+// are 32-bit words, so only where the ring and the suspend blocks' span fit them.
+static bool sliced_launch(bool abort_mode, const hcTrackSettings &st, const SliceLayout &a, size_t wsb) {
+    return !abort_mode && SLICE_Q > 0 && wsb >= a.total && a.ring_cap < 0xFFFFFF00ull &&
+           a.susp_entry1 < (size_t)UINT_MAX && slice_fits(st.max_steps, st.max_corrections, st.delta_t_inc_steps);
 }
 // tests only (hc_trifocal_set_ring_test, include/hc_trifocal_testing.h): pusher
 // delay of every 16th ring ticket; read by every launch of every thread
@@ -214,19 +234,13 @@ static hcStatus launch_track(const hcTrackArgs *t, const TrackLaunch &l, void *w
         k.found_flag = ab->found_trifocal_sols;
         k.batch_index = ab->trifocal_sols_batch_index;
     }
-    // time slicing when the workspace has room for it (hc_trifocal_workspace_size_for) and
-    // the step counters fit the suspend block
-    // (the suspend blocks' span in ring-entry units, PrepArgs::susp_entry1, is a
-    // 32-bit word: slicing only where it fits)
-    const size_t susp_end = ring_bytes(ring_entries(paths, t->settings.max_steps)) / 8 + (size_t)paths * SUSP_WORDS;
-    if (!abort_mode && SLICE_Q > 0 && wsb >= ws_bytes_for(paths, t->settings.max_steps) &&
-        ring_entries(paths, t->settings.max_steps) < 0xFFFFFF00ull && susp_end < (size_t)UINT_MAX &&
-        slice_fits(t->settings.max_steps, t->settings.max_corrections, t->settings.delta_t_inc_steps)) {
-        char *base = (char *)workspace + ws_bytes_needed();
-        k.ring_cap = (unsigned)ring_entries(paths, t->settings.max_steps);
-        k.rq = (unsigned *)base;
-        k.ring = (unsigned long long *)(base + RQ_WORDS * sizeof(unsigned));
-        k.susp = (unsigned long long *)(base + RQ_WORDS * sizeof(unsigned) + ring_bytes(k.ring_cap));
+    const SliceLayout area = slice_layout(paths, t->settings.max_steps);
+    const bool sliced = sliced_launch(abort_mode, t->settings, area, wsb);
+    if (sliced) {
+        k.ring_cap = (unsigned)area.ring_cap;
+        k.rq = (unsigned *)((char *)workspace + area.rq);
+        k.ring = (unsigned long long *)((char *)workspace + area.ring);
+        k.susp = (unsigned long long *)((char *)workspace + area.susp);
         k.slice_q = SLICE_Q;
         k.ring_test = g_ring_test.load(std::memory_order_relaxed);
         k.retry_reuse = g_retry_reuse.load(std::memory_order_relaxed);   // (the slope is kept in the suspend block)
@@ -235,8 +249,8 @@ static hcStatus launch_track(const hcTrackArgs *t, const TrackLaunch &l, void *w
     // (a grouped launch's flags are the caller's group_found words: Workspace::found stays 0, unused)
     PrepArgs pa{t->unified_index, ws, ab ? ab->found_trifocal_sols : nullptr, ab ? ab->peer_found : nullptr,
                 k.rq, k.ring, k.ring_cap,
-                k.rq ? (unsigned)(ring_bytes(k.ring_cap) / 8) : 0u,
-                k.rq ? (unsigned)susp_end : 0u};
+                sliced ? (unsigned)area.susp_entry0 : 0u,
+                sliced ? (unsigned)area.susp_entry1 : 0u};
     hipLaunchKernelGGL(k_prep_tables, dim3(1), dim3(PREP_THREADS), 0, s, pa);
     if (launch_status(HC_ERROR_LAUNCH) != HC_SUCCESS) return HC_ERROR_LAUNCH;
     // the twin is enqueued after the specialised kernel: exactly one of the two
@@ -309,7 +323,7 @@ size_t hc_trifocal_workspace_size_for(int sub_ransac_iters) {
 }
 
 size_t hc_trifocal_workspace_size_for_steps(int sub_ransac_iters, int max_steps) {
-    return hc::ws_bytes_for(sub_ransac_iters > 0 ? (long long)sub_ransac_iters * hc::NTRK : 0, max_steps);
+    return hc::slice_layout(sub_ransac_iters > 0 ? (long long)sub_ransac_iters * hc::NTRK : 0, max_steps).total;
 }
 
 hcStatus hc_trifocal_2op1p_30x30_track(const hcTrackArgs *args, void *workspace, size_t workspace_bytes,
@@ -495,10 +509,10 @@ int hc_lu_group_class(int step, int group) {
 
 hcStatus hc_trifocal_ring_check_test(void *workspace, size_t workspace_bytes, unsigned head, unsigned tail,
                                      unsigned avail, hcStream stream) {
-    if (!workspace || workspace_bytes < hc::ws_bytes_needed() + hc::RQ_WORDS * sizeof(unsigned))
-        return HC_ERROR_WORKSPACE;
+    const hc::SliceLayout area = hc::slice_layout(0, 0);   // the counters' place does not depend on the launch
+    if (!workspace || workspace_bytes < area.ring) return HC_ERROR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    unsigned *rq = (unsigned *)((char *)workspace + hc::ws_bytes_needed());
+    unsigned *rq = (unsigned *)((char *)workspace + area.rq);
     const unsigned v[3] = {head, tail, avail};
     const int at[3] = {hc::RQ_HEAD, hc::RQ_TAIL, hc::RQ_AVAIL};
     (void)hipGetLastError();

@@ -14,6 +14,8 @@ pose_support_joint_grouped, inlier_mask, merge_joint below).
 
 The four pose-support calls (per view / joint, one triplet / grouped) share one
 launcher and one synchronous wrapper (_launch, _run), parameterised by a _Rule.
+Every native call goes through the signature table of _abi: buffers and streams
+are passed as _abi.ptr(x), hcStatus entry points are called by _abi.call(name, ...).
 """
 from __future__ import annotations
 
@@ -28,11 +30,6 @@ from .problem import RansacData
 
 SEL_BYTES = _abi.POSE_SELECTION_BYTES
 JOINT_SEL_BYTES = _abi.TRIFOCAL_SELECTION_BYTES
-
-
-def _stream_handle(stream, device):
-    s = stream if stream is not None else torch.cuda.current_stream(device)
-    return C.c_void_p(s.cuda_stream)
 
 
 def _struct_from_raw(cls, nbytes, raw):
@@ -105,10 +102,10 @@ def _launch(rule, tracks, converge, scene, inliers, selections, flags, stream) -
             if not t.is_cuda or not t.is_contiguous():
                 raise _abi.HCError(f"{name}: buffers must be contiguous device tensors")
         scene_args = (int(scene[0].shape[0]), *scene)
-    args = [C.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor) else a
+    args = [_abi.ptr(a) if isinstance(a, torch.Tensor) else a
             for a in (n, tracks, converge, *scene_args, flags, inliers, selections)]
-    _abi.check(getattr(_abi.lib(), "hc_trifocal_" + name)(*args, _stream_handle(stream, tracks.device)),
-               "hc_trifocal_" + name)
+    _abi.call("hc_trifocal_" + name, *args,
+              _abi.ptr(stream if stream is not None else torch.cuda.current_stream(tracks.device)))
 
 
 def _run(rule, tracks, converge, scene, flags=0):
@@ -198,7 +195,7 @@ def merge(parts: list, path_offsets: list, quirks: bool = False) -> dict:
         arr[i] = p if isinstance(p, _abi.hcPoseSelection) else selection_struct(p)
     offs = np.ascontiguousarray(path_offsets, np.int32)
     out = _abi.hcPoseSelection()
-    _abi.lib().hc_pose_merge(n, C.cast(arr, C.c_void_p), C.c_void_p(offs.ctypes.data),
+    _abi.lib().hc_pose_merge(n, C.cast(arr, C.c_void_p), _abi.ptr(offs),
                              _abi.HC_POSE_REFERENCE_QUIRKS if quirks else 0, C.byref(out))
     return selection_dict(out)
 
@@ -221,10 +218,8 @@ def inlier_mask(selection, edgels: torch.Tensor, K: torch.Tensor, packed: bool =
     if selection.numel() * selection.element_size() < JOINT_SEL_BYTES:
         raise _abi.HCError("inlier_mask: selection is smaller than hcTrifocalSelection")
     words = torch.empty((E + 63) // 64, dtype=torch.int64, device=dev)
-    _abi.check(_abi.lib().hc_trifocal_pose_inlier_mask(C.c_void_p(selection.data_ptr()), E,
-                                                       C.c_void_p(edgels.data_ptr()), C.c_void_p(K.data_ptr()),
-                                                       C.c_void_p(words.data_ptr()), _stream_handle(stream, dev)),
-               "hc_trifocal_pose_inlier_mask")
+    _abi.call("hc_trifocal_pose_inlier_mask", _abi.ptr(selection), E, _abi.ptr(edgels), _abi.ptr(K), _abi.ptr(words),
+              _abi.ptr(stream if stream is not None else torch.cuda.current_stream(dev)))
     if stream is not None:
         stream.synchronize()
     else:
@@ -245,7 +240,7 @@ def merge_joint(parts: list, path_offsets: list) -> dict:
         arr[i] = joint_selection_from_dict(p) if isinstance(p, dict) else joint_selection_struct(p)
     offs = np.ascontiguousarray(path_offsets if n else [0], np.int32)
     out = _abi.hcTrifocalSelection()
-    _abi.lib().hc_pose_merge_joint(n, C.cast(arr, C.c_void_p), C.c_void_p(offs.ctypes.data), C.byref(out))
+    _abi.lib().hc_pose_merge_joint(n, C.cast(arr, C.c_void_p), _abi.ptr(offs), C.byref(out))
     return joint_selection_dict(out)
 
 
@@ -254,7 +249,7 @@ def residuals(data: RansacData, sel: dict):
     out = np.zeros(4, np.float32)
     a = [np.ascontiguousarray(v, np.float32) for v in (data.pose21, data.pose31, sel["R21"], sel["t21"],
                                                         sel["R31"], sel["t31"])]
-    ok = _abi.lib().hc_pose_residuals(*[C.c_void_p(v.ctypes.data) for v in a], C.c_void_p(out.ctypes.data))
+    ok = _abi.lib().hc_pose_residuals(*[_abi.ptr(v) for v in a], _abi.ptr(out))
     return out, bool(ok)
 
 

@@ -7,7 +7,6 @@ layout: <root>/problems/<problem>/... and <root>/RANSAC_Data/<problem>/<dataset>
 """
 from __future__ import annotations
 
-import ctypes as C
 import os
 from dataclasses import dataclass
 
@@ -18,10 +17,6 @@ from . import _abi
 PROBLEM = "trifocal_2op1p_30x30"
 REPO_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DATA_ROOT = os.path.join(REPO_ROOT, "data")
-
-
-def _p(a: np.ndarray):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 def read_settings(path: str) -> dict:
@@ -80,13 +75,13 @@ def load_problem(root: str = DATA_ROOT, problem: str = PROBLEM) -> Problem:
     sp = np.zeros((34, 2), np.float32)
     dx = np.zeros(36000, np.int32)
     dt = np.zeros(2880, np.int32)
-    if L.hc_read_start_sols(os.path.join(d, "start_sols.txt").encode(), _p(ss)) != 312 * 30:
+    if L.hc_read_start_sols(os.path.join(d, "start_sols.txt").encode(), _abi.ptr(ss)) != 312 * 30:
         raise _abi.HCError("start solutions not loaded")
-    if L.hc_read_start_params(os.path.join(d, "start_params.txt").encode(), _p(sp)) != 33:
+    if L.hc_read_start_params(os.path.join(d, "start_params.txt").encode(), _abi.ptr(sp)) != 33:
         raise _abi.HCError("start parameters not loaded")
-    if L.hc_read_int_table(os.path.join(d, "dHdx_indx.txt").encode(), _p(dx), dx.size) != dx.size:
+    if L.hc_read_int_table(os.path.join(d, "dHdx_indx.txt").encode(), _abi.ptr(dx), dx.size) != dx.size:
         raise _abi.HCError("dH/dx evaluation indices not loaded")
-    if L.hc_read_int_table(os.path.join(d, "dHdt_indx.txt").encode(), _p(dt), dt.size) != dt.size:
+    if L.hc_read_int_table(os.path.join(d, "dHdt_indx.txt").encode(), _abi.ptr(dt), dt.size) != dt.size:
         raise _abi.HCError("dH/dt evaluation indices not loaded")
     return Problem(ss, sp, dx, dt, read_settings(os.path.join(d, "gpuhc_settings.yaml")))
 
@@ -105,22 +100,23 @@ def load_ransac_data(index: int = 0, root: str = DATA_ROOT, problem: str = PROBL
         raise _abi.HCError(f"no triplet edgels in {f!r}")
     loc = np.zeros((E, 6), np.float32)
     tan = np.zeros((E, 6), np.float32)
-    if L.hc_read_triplet_edgels(f, _p(loc), _p(tan), E) != E:
+    if L.hc_read_triplet_edgels(f, _abi.ptr(loc), _abi.ptr(tan), E) != E:
         raise _abi.HCError("triplet edgels not loaded")
     K = np.zeros(9, np.float32)
-    if L.hc_read_float_table(os.path.join(d, "Intrinsic_Matrix.txt").encode(), _p(K), 9) != 9:
+    if L.hc_read_float_table(os.path.join(d, "Intrinsic_Matrix.txt").encode(), _abi.ptr(K), 9) != 9:
         raise _abi.HCError("intrinsic matrix not loaded")
     poses = []
     for v in ("21", "31"):
         P = np.zeros(12, np.float32)
-        L.hc_read_float_table(os.path.join(d, f"GT_Poses{v}", f"GT_Poses{v}_{index:03d}.txt").encode(), _p(P), 12)
+        L.hc_read_float_table(os.path.join(d, f"GT_Poses{v}", f"GT_Poses{v}_{index:03d}.txt").encode(), _abi.ptr(P),
+                              12)
         poses.append(P)
     return RansacData(loc, tan, K, poses[0], poses[1])
 
 
 def split_samples(num_samples: int, num_gpus: int) -> np.ndarray:
     sub = np.zeros(num_gpus, np.int32)
-    _abi.lib().hc_split_samples(C.c_int(num_samples), C.c_int(num_gpus), _p(sub))
+    _abi.lib().hc_split_samples(num_samples, num_gpus, _abi.ptr(sub))
     return sub
 
 
@@ -132,9 +128,9 @@ def prepare_target_params(problem: Problem, data: RansacData, seed: int, num_sam
     tgt = np.zeros((num_samples, 34, 2), np.float32)
     dif = np.zeros((num_samples, 34, 2), np.float32)
     picked = np.zeros((num_samples, 3), np.int32)
-    _abi.lib().hc_prepare_target_params(C.c_uint(seed), C.c_int(num_gpus), _p(sub), _p(data.locations),
-                                        _p(data.tangents), C.c_int(data.locations.shape[0]),
-                                        _p(problem.start_params), _p(tgt), _p(dif), _p(picked))
+    p = _abi.ptr
+    _abi.lib().hc_prepare_target_params(seed, num_gpus, p(sub), p(data.locations), p(data.tangents),
+                                        data.locations.shape[0], p(problem.start_params), p(tgt), p(dif), p(picked))
     return tgt, dif, picked
 
 
@@ -142,7 +138,6 @@ def count_solutions(tracks: np.ndarray, conv: np.ndarray, inf: np.ndarray):
     """(converged, real, infinity) like Evaluations::Evaluate_RANSAC_HC_Sols."""
     out = np.zeros(3, np.int32)
     tr = np.ascontiguousarray(tracks, np.float32)
-    n = conv.shape[0] // 312
-    _abi.lib().hc_count_solutions(C.c_int(n), _p(tr), _p(np.ascontiguousarray(conv, np.uint8)),
-                                  _p(np.ascontiguousarray(inf, np.uint8)), _p(out))
+    cv, nf = np.ascontiguousarray(conv, np.uint8), np.ascontiguousarray(inf, np.uint8)
+    _abi.lib().hc_count_solutions(conv.shape[0] // 312, _abi.ptr(tr), _abi.ptr(cv), _abi.ptr(nf), _abi.ptr(out))
     return tuple(int(v) for v in out)

@@ -191,7 +191,7 @@ class SharedFlag:
         if int(agree.item()) == 1:
             self.ptr = p.value
         elif p.value:
-            self._L.hc_shared_flag_close(C.c_void_p(p.value), 1 if self.opened else 0)
+            self._L.hc_shared_flag_close(p, 1 if self.opened else 0)
             self.error = self.error or "another rank could not map the flag"
         self._group = group
         self._owner = owner
@@ -203,17 +203,17 @@ class SharedFlag:
         otherwise set the flag after the reset), then the owner resets and
         synchronises, and a barrier on both sides orders the reset after every
         rank's previous launches and before any rank's next one."""
-        import ctypes as C
-
         import torch
         import torch.distributed as dist
+
+        from . import _abi
         if self.ptr is None:
             return
         s = stream if stream is not None else torch.cuda.current_stream()
         torch.cuda.synchronize(s.device)
         dist.barrier(group=self._group)
         if self._rank == self._owner:
-            st = self._L.hc_shared_flag_reset(C.c_void_p(self.ptr), C.c_void_p(s.cuda_stream))
+            st = self._L.hc_shared_flag_reset(self.ptr, _abi.ptr(s))
             if st != 0:
                 raise RuntimeError(f"hc_shared_flag_reset failed: {st}")
             s.synchronize()
@@ -223,22 +223,19 @@ class SharedFlag:
     def memory_kind(self):
         """The owner's allocation (include/hc_trifocal.h hc_shared_flag_memory_kind):
         'uncached', 'fine-grained', 'coarse-grained', or None on a mapping rank."""
-        import ctypes as C
         if self.ptr is None or self._rank != self._owner:
             return None
-        k = self._L.hc_shared_flag_memory_kind(C.c_void_p(self.ptr))
+        k = self._L.hc_shared_flag_memory_kind(self.ptr)
         return {2: "uncached", 1: "fine-grained", 0: "coarse-grained"}.get(k)
 
     def close(self) -> None:
         """Collective: the mapping ranks unmap before the owner frees."""
-        import ctypes as C
-
         import torch.distributed as dist
         if self.ptr is None:
             return
         if self.opened:
-            self._L.hc_shared_flag_close(C.c_void_p(self.ptr), 1)
+            self._L.hc_shared_flag_close(self.ptr, 1)
         dist.barrier(group=self._group)
         if not self.opened:
-            self._L.hc_shared_flag_close(C.c_void_p(self.ptr), 0)
+            self._L.hc_shared_flag_close(self.ptr, 0)
         self.ptr = None

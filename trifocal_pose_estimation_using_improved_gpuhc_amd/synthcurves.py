@@ -13,7 +13,6 @@ so `load_ransac_data(index, dataset=name)` and `magmaHC-main -s <name>` read the
 """
 from __future__ import annotations
 
-import ctypes as C
 import os
 import shutil
 
@@ -29,8 +28,8 @@ def add_pixel_noise(locations: np.ndarray, K: np.ndarray, sigma_px: float, seed:
     loc = np.ascontiguousarray(locations, np.float32)
     Kc = np.ascontiguousarray(K, np.float32)
     out = np.empty_like(loc)
-    _abi.lib().hc_add_pixel_noise(loc.shape[0], C.c_void_p(loc.ctypes.data), C.c_void_p(Kc.ctypes.data),
-                                  float(sigma_px), int(seed) & 0xFFFFFFFFFFFFFFFF, C.c_void_p(out.ctypes.data))
+    _abi.lib().hc_add_pixel_noise(loc.shape[0], _abi.ptr(loc), _abi.ptr(Kc), float(sigma_px),
+                                  int(seed) & 0xFFFFFFFFFFFFFFFF, _abi.ptr(out))
     return out
 
 
@@ -43,8 +42,7 @@ def noisy(data: RansacData, sigma_px: float, seed: int = DEFAULT_SEED) -> Ransac
 def write_triplet_edgels(path: str, locations: np.ndarray, tangents: np.ndarray) -> None:
     loc = np.ascontiguousarray(locations, np.float32)
     tan = np.ascontiguousarray(tangents, np.float32)
-    if _abi.lib().hc_write_triplet_edgels(path.encode(), loc.shape[0], C.c_void_p(loc.ctypes.data),
-                                          C.c_void_p(tan.ctypes.data)) != loc.shape[0]:
+    if _abi.lib().hc_write_triplet_edgels(path.encode(), loc.shape[0], _abi.ptr(loc), _abi.ptr(tan)) != loc.shape[0]:
         raise _abi.HCError(f"cannot write {path}")
 
 

@@ -17,8 +17,11 @@ from .problem import Problem, RansacData
 PATH_STATS_DTYPE = np.dtype([("steps", "<i4"), ("corrections", "<i4"), ("inliers21", "<i4"), ("inliers31", "<i4")])
 
 
-def _ptr(t: torch.Tensor | None):
-    return None if t is None else C.c_void_p(t.data_ptr())
+# (abort, truncate, explicit_rk) -> the entry point (TrackMode of csrc/hc_kernels.hip)
+_TRACK_ENTRY = {(True, True, False): "hc_trifocal_2op1p_30x30_track_abort",
+                (False, True, False): "hc_trifocal_2op1p_30x30_track",
+                (False, False, False): "hc_trifocal_2op1p_30x30_track_ph_codeopt",
+                (False, False, True): "hc_trifocal_2op1p_30x30_track_ph"}
 
 
 def _require_gpu(device) -> torch.device:
@@ -204,17 +207,14 @@ class DeviceTracker:
         g.group_found_ticks = r.found_ticks.data_ptr()
         g.inflight_stop = 1 if inflight_stop else 0
         s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        name, blocks = "hc_trifocal_2op1p_30x30_track_abort_grouped", [C.byref(a), C.byref(g)]
         if ratio is not None:
             jg = _abi.hcJointGate()
             jg.min_joint_ratio = ratio
             jg.joint_inliers = r.joint_inliers.data_ptr()
-            _abi.check(self.L.hc_trifocal_2op1p_30x30_track_abort_gated(
-                C.byref(a), C.byref(g), C.byref(jg), C.c_void_p(ws_t.data_ptr()), self.ws_bytes,
-                C.c_void_p(s.cuda_stream)), "hc_trifocal_2op1p_30x30_track_abort_gated")
-            return
-        _abi.check(self.L.hc_trifocal_2op1p_30x30_track_abort_grouped(
-            C.byref(a), C.byref(g), C.c_void_p(ws_t.data_ptr()), self.ws_bytes, C.c_void_p(s.cuda_stream)),
-            "hc_trifocal_2op1p_30x30_track_abort_grouped")
+            name = "hc_trifocal_2op1p_30x30_track_abort_gated"
+            blocks.append(C.byref(jg))
+        _abi.call(name, *blocks, _abi.ptr(ws_t), self.ws_bytes, _abi.ptr(s))
 
     def track_grouped(self, batch, inflight_stop: bool = False, stats: bool = True, found=None,
                       gate=None) -> TrackResult:
@@ -278,12 +278,11 @@ class DeviceTracker:
         wsb = ws_t.numel() if (time_slicing and not abort) else self.ws_bytes
         a = self._track_args(r, target, diff, sample_offset, num_samples)
         s = stream if stream is not None else torch.cuda.current_stream(self.device)
-        hs = C.c_void_p(s.cuda_stream)
-        ws = C.c_void_p(ws_t.data_ptr())
         if abort and not truncate:
             raise _abi.HCError("abort mode always truncates paths (..._TrunRANSAC.cu)")
         if explicit_rk and truncate:
             raise _abi.HCError("the archived ..._PH kernel has no path truncation: pass truncate=False")
+        blocks = [C.byref(a)]   # hcTrackArgs, then the mode's own argument block
         if abort:
             if self.edgels is None:
                 raise _abi.HCError("abort mode needs set_ransac_data() first")
@@ -295,17 +294,9 @@ class DeviceTracker:
             ab.trifocal_sols_batch_index = r.batch_index[sample_offset * 312:].data_ptr()
             ab.inflight_stop = 1 if inflight_stop else 0
             ab.peer_found = None if peer_found is None else peer_found.ptr
-            _abi.check(self.L.hc_trifocal_2op1p_30x30_track_abort(C.byref(a), C.byref(ab), ws, wsb, hs),
-                       "hc_trifocal_2op1p_30x30_track_abort")
-        elif explicit_rk:
-            _abi.check(self.L.hc_trifocal_2op1p_30x30_track_ph(C.byref(a), ws, wsb, hs),
-                       "hc_trifocal_2op1p_30x30_track_ph")
-        elif not truncate:
-            _abi.check(self.L.hc_trifocal_2op1p_30x30_track_ph_codeopt(C.byref(a), ws, wsb, hs),
-                       "hc_trifocal_2op1p_30x30_track_ph_codeopt")
-        else:
-            _abi.check(self.L.hc_trifocal_2op1p_30x30_track(C.byref(a), ws, wsb, hs),
-                       "hc_trifocal_2op1p_30x30_track")
+            blocks.append(C.byref(ab))
+        _abi.call(_TRACK_ENTRY[bool(abort), bool(truncate), bool(explicit_rk)], *blocks, _abi.ptr(ws_t), wsb,
+                  _abi.ptr(s))
 
     def new_workspace(self, num_samples: int = 0) -> torch.Tensor:
         """A workspace; with num_samples > 0, large enough for time slicing of
@@ -345,14 +336,13 @@ class DeviceTracker:
         entry never came or the ring overflowed; the lost path's outputs are
         not written; diagnostics in the control block's ring_fail words)."""
         ws = workspace if workspace is not None else self.workspace
-        _abi.check(self.L.hc_trifocal_workspace_status(C.c_void_p(ws.data_ptr())), "hc_trifocal_workspace_status")
+        _abi.call("hc_trifocal_workspace_status", _abi.ptr(ws))
 
     def read_timestamps(self, workspace: torch.Tensor | None = None):
         """(start_ticks, found_ticks, tick_hz) of the last launch on workspace."""
         a, b, hz = C.c_uint64(0), C.c_uint64(0), C.c_double(0.0)
         ws = workspace if workspace is not None else self.workspace
-        _abi.check(self.L.hc_trifocal_read_timestamps(C.c_void_p(ws.data_ptr()), C.byref(a), C.byref(b), C.byref(hz)),
-                   "hc_trifocal_read_timestamps")
+        _abi.call("hc_trifocal_read_timestamps", _abi.ptr(ws), C.byref(a), C.byref(b), C.byref(hz))
         return a.value, b.value, hz.value
 
     def track(self, target: np.ndarray, diff: np.ndarray, abort: bool = False, stats: bool = True,
@@ -371,22 +361,19 @@ class DeviceTracker:
 
     def first_found_seconds(self) -> float:
         v = C.c_double(0.0)
-        _abi.check(self.L.hc_trifocal_read_timings(C.c_void_p(self.workspace.data_ptr()), C.byref(v)),
-                   "hc_trifocal_read_timings")
+        _abi.call("hc_trifocal_read_timings", _abi.ptr(self.workspace), C.byref(v))
         return v.value
 
 
 def cgesv_batched(A: np.ndarray, b: np.ndarray, device="cuda:0") -> np.ndarray:
     """Batched tracker-LU solve of n 30x30 complex systems (A row-major (n,30,30,2))."""
     dev = _require_gpu(device)
-    L = _abi.lib()
     At = torch.from_numpy(np.ascontiguousarray(A, np.float32)).to(dev)
     bt = torch.from_numpy(np.ascontiguousarray(b, np.float32)).to(dev)
     xt = torch.empty_like(bt)
     n = At.shape[0]
-    _abi.check(L.hc_cgesv_30x30_batched(n, _ptr(At), _ptr(bt), _ptr(xt),
-                                        C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
-               "hc_cgesv_30x30_batched")
+    _abi.call("hc_cgesv_30x30_batched", n, _abi.ptr(At), _abi.ptr(bt), _abi.ptr(xt),
+              _abi.ptr(torch.cuda.current_stream(dev)))
     torch.cuda.synchronize(dev)
     return xt.cpu().numpy()
 
@@ -394,7 +381,6 @@ def cgesv_batched(A: np.ndarray, b: np.ndarray, device="cuda:0") -> np.ndarray:
 def eval_batched(unified: np.ndarray, x: np.ndarray, p: np.ndarray, d: np.ndarray, device="cuda:0"):
     """Batched dH/dx, dH/dt, H at (x, p) with the tracker's compacted tables."""
     dev = _require_gpu(device)
-    L = _abi.lib()
     n = x.shape[0]
     U = torch.from_numpy(np.ascontiguousarray(unified, np.int32)).to(dev)
     X = torch.from_numpy(np.ascontiguousarray(x, np.float32)).to(dev)
@@ -403,10 +389,9 @@ def eval_batched(unified: np.ndarray, x: np.ndarray, p: np.ndarray, d: np.ndarra
     HX = torch.empty((n, 30, 30, 2), dtype=torch.float32, device=dev)
     HT = torch.empty((n, 30, 2), dtype=torch.float32, device=dev)
     H = torch.empty((n, 30, 2), dtype=torch.float32, device=dev)
-    wsb = int(L.hc_trifocal_workspace_size())
+    wsb = int(_abi.lib().hc_trifocal_workspace_size())
     ws = torch.zeros(wsb, dtype=torch.uint8, device=dev)
-    _abi.check(L.hc_trifocal_eval_batched(n, _ptr(U), _ptr(X), _ptr(P), _ptr(D), _ptr(HX), _ptr(HT), _ptr(H),
-                                          _ptr(ws), wsb, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
-               "hc_trifocal_eval_batched")
+    _abi.call("hc_trifocal_eval_batched", n, *(_abi.ptr(t) for t in (U, X, P, D, HX, HT, H, ws)), wsb,
+              _abi.ptr(torch.cuda.current_stream(dev)))
     torch.cuda.synchronize(dev)
     return HX.cpu().numpy(), HT.cpu().numpy(), H.cpu().numpy()
