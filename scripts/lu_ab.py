@@ -20,7 +20,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def child(n):
     sys.path.insert(0, ROOT)
-    import ctypes as C
     import hashlib
 
     import numpy as np
@@ -40,22 +39,22 @@ def child(n):
     P[:, 33] = (1.0, 0.0)
     D = dif[s]
     L = _abi.lib()
-    p = lambda a: C.c_void_p(a.data_ptr())  # noqa: E731
-    U = torch.from_numpy(problem.unified_index).to(dev)
+    p = _abi.ptr
+    U =torch.from_numpy(problem.unified_index).to(dev)
     Xt, Pt, Dt = (torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (X, P, D))
     HX = torch.empty((n, 30, 30, 2), dtype=torch.float32, device=dev)
     HT = torch.empty((n, 30, 2), dtype=torch.float32, device=dev)
     H = torch.empty((n, 30, 2), dtype=torch.float32, device=dev)
     wsb = int(L.hc_trifocal_workspace_size())
     ws = torch.zeros(wsb, dtype=torch.uint8, device=dev)
-    st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    _abi.check(L.hc_trifocal_eval_batched(n, p(U), p(Xt), p(Pt), p(Dt), p(HX), p(HT), p(H), p(ws), wsb, st), "eval")
+    st = p(torch.cuda.current_stream(dev))
+    _abi.call("hc_trifocal_eval_batched", n, p(U), p(Xt), p(Pt), p(Dt), p(HX), p(HT), p(H), p(ws), wsb, st)
     Xs = torch.empty_like(HT)
     ms = []
     for i in range(8):
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record()
-        _abi.check(L.hc_cgesv_30x30_batched(n, p(HX), p(HT), p(Xs), st), "cgesv")
+        _abi.call("hc_cgesv_30x30_batched", n, p(HX), p(HT), p(Xs), st)
         b.record()
         torch.cuda.synchronize()
         if i:

@@ -19,7 +19,6 @@ import os
 import sys
 import time
 
-import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -53,8 +52,9 @@ def main():
         tgt, dif, _ = prepare_target_params(problem, data, seed, 100)
     scaled = "--scaled" in argv
     if scaled:
-        tgt = np.stack([tgt[0]] + [(tgt[0] * np.float32(s)).astype(np.float32) for s in (2.0 ** 40, 2.0 ** 70)])
-        dif = (tgt - problem.start_params[None]).astype(np.float32)
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        from checks import scaled_samples
+        tgt, dif = scaled_samples(problem, tgt[0], (0, 40, 70))
     tr = DeviceTracker(problem, dev)
     r = tr.allocate(tgt.shape[0])
     tr.reset_tracks(r)

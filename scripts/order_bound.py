@@ -58,7 +58,7 @@ def main():
     for rnd in range(2):
         for name, o in orders.items():
             ot = None if o is None else torch.from_numpy(o.astype(np.int32)).to(dev)
-            assert L.hc_ab_set_path_order(None if ot is None else C.c_void_p(ot.data_ptr())) == 0
+            assert L.hc_ab_set_path_order(_abi.ptr(ot)) == 0
             ms = []
             kspan = (C.c_ulonglong * 4)()
             for i in range(8):

@@ -9,7 +9,7 @@ import time
 import torch
 
 sys.path.insert(0, ".")
-from trifocal_pose_estimation_using_improved_gpuhc_amd import load_problem, load_ransac_data, prepare_target_params  # noqa: E402
+from trifocal_pose_estimation_using_improved_gpuhc_amd import _abi, load_problem, load_ransac_data, prepare_target_params  # noqa: E402
 from trifocal_pose_estimation_using_improved_gpuhc_amd.tracker import DeviceTracker  # noqa: E402
 
 dev = torch.device("cuda:0")
@@ -40,8 +40,7 @@ for sliced in (True, False):
         run(K)
         torch.cuda.synchronize(dev)
         el = time.perf_counter() - t0
-        import ctypes
-        st = [int(tr.L.hc_trifocal_workspace_status(ctypes.c_void_p(w.data_ptr()))) for w in wss]
+        st = [int(tr.L.hc_trifocal_workspace_status(_abi.ptr(w))) for w in wss]
         rec = {"sliced": sliced, "streams": ns, "batches": K, "ms_per_batch": round(el / K * 1e3, 3), "status": st}
         print(json.dumps(rec), flush=True)
         out.write(json.dumps(rec) + "\n")

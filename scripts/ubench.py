@@ -5,7 +5,6 @@ Times the batched 30x30 LU kernel, the batched evaluation kernel and one
 tracking launch, each with HIP events, and prints per-unit costs so the
 tracker's time can be attributed (eval vs LU vs control).
 """
-import ctypes as C
 import json
 import os
 import sys
@@ -37,15 +36,15 @@ def timeit(fn, reps=5):
 def main():
     L = _abi.lib()
     dev = torch.device("cuda:0")
-    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    p = _abi.ptr
+    st = p(torch.cuda.current_stream())
     out = {}
     n = 1 << 18
     g = torch.Generator(device=dev).manual_seed(0)
     A = torch.randn((n, 30, 30, 2), generator=g, device=dev)
     b = torch.randn((n, 30, 2), generator=g, device=dev)
     x = torch.empty_like(b)
-    ms = timeit(lambda: _abi.check(L.hc_cgesv_30x30_batched(n, C.c_void_p(A.data_ptr()), C.c_void_p(b.data_ptr()),
-                                                             C.c_void_p(x.data_ptr()), st), "cgesv"))
+    ms = timeit(lambda: _abi.call("hc_cgesv_30x30_batched", n, p(A), p(b), p(x), st))
     out["cgesv_ms"] = ms
     out["cgesv_ns_per_solve"] = ms * 1e6 / n
     problem = load_problem()
@@ -60,10 +59,8 @@ def main():
     H = torch.empty((n, 30, 2), device=dev)
     wsb = int(L.hc_trifocal_workspace_size())
     ws = torch.zeros(wsb, dtype=torch.uint8, device=dev)
-    ms = timeit(lambda: _abi.check(L.hc_trifocal_eval_batched(
-        n, C.c_void_p(U.data_ptr()), C.c_void_p(X.data_ptr()), C.c_void_p(P.data_ptr()), C.c_void_p(D.data_ptr()),
-        C.c_void_p(HX.data_ptr()), C.c_void_p(HT.data_ptr()), C.c_void_p(H.data_ptr()), C.c_void_p(ws.data_ptr()),
-        wsb, st), "eval"))
+    ms = timeit(lambda: _abi.call("hc_trifocal_eval_batched", n, p(U), p(X), p(P), p(D), p(HX), p(HT), p(H), p(ws),
+                                  wsb, st))
     out["eval_ms"] = ms
     out["eval_ns_per_point"] = ms * 1e6 / n
     tr = DeviceTracker(problem, dev)

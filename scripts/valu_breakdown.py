@@ -9,7 +9,6 @@ counters (SQ_INSTS_VALU, ...) can be attributed per unit of work (GPU only):
     rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVES -- python scripts/valu_breakdown.py
 """
 import argparse
-import ctypes as C
 import os
 import sys
 
@@ -46,11 +45,11 @@ HT = torch.empty((n, 30, 2), dtype=torch.float32, device=dev)
 H = torch.empty((n, 30, 2), dtype=torch.float32, device=dev)
 wsb = int(L.hc_trifocal_workspace_size())
 ws = torch.zeros(wsb, dtype=torch.uint8, device=dev)
-st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-p = lambda a: C.c_void_p(a.data_ptr())  # noqa: E731
-_abi.check(L.hc_trifocal_eval_batched(n, p(U), p(Xt), p(Pt), p(Dt), p(HX), p(HT), p(H), p(ws), wsb, st), "eval")
+p = _abi.ptr
+st = p(torch.cuda.current_stream(dev))
+_abi.call("hc_trifocal_eval_batched", n, p(U), p(Xt), p(Pt), p(Dt), p(HX), p(HT), p(H), p(ws), wsb, st)
 Xs = torch.empty_like(HT)
-_abi.check(L.hc_cgesv_30x30_batched(n, p(HX), p(HT), p(Xs), st), "cgesv")
+_abi.call("hc_cgesv_30x30_batched", n, p(HX), p(HT), p(Xs), st)
 tr = DeviceTracker(problem, dev)
 r = tr.allocate(100)
 tr.reset_tracks(r)

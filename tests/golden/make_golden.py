@@ -30,27 +30,14 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.dirname(HERE)]
 
+from checks import track_hash  # noqa: E402  (tests/checks.py: the tests hash with the same function)
 from oracle import oracle as O  # noqa: E402
 
 DATA = os.path.join(ROOT, "data")
 PROB = os.path.join(DATA, "problems", "trifocal_2op1p_30x30")
 RANS = os.path.join(DATA, "RANSAC_Data", "trifocal_2op1p_30x30", "Synthetic")
-
-
-def track_hash(tracks):
-    """Per-path 64-bit polynomial hash of x[0..29] with +0/-0 and NaN canonicalised."""
-    a = np.ascontiguousarray(tracks[:, :30, :], np.float32).copy()
-    a[a == 0] = 0.0
-    a[np.isnan(a)] = np.float32(np.nan)
-    w = a.reshape(a.shape[0], -1).view(np.uint32).astype(np.uint64)
-    h = np.zeros(a.shape[0], np.uint64)
-    P = np.uint64(1099511628211)
-    with np.errstate(over="ignore"):
-        for k in range(w.shape[1]):
-            h = (h * P) ^ w[:, k]
-    return h
 
 
 def pose_fixture(tr, conv, loc, K):

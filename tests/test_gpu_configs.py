@@ -14,31 +14,28 @@
   largest   config 4's whole workload (8000 samples) in one tracking launch
             on one GPU: the golden prefix, oracle paths across the launch.
 """
-import os
-
 import numpy as np
 import pytest
 
+from checks import (assert_matches_golden, assert_matches_oracle, assert_same_run, assert_untouched, found_ids, golden,
+                    noisy_data, ring_counters, tracked)
 from conftest import same
 from residual import RESIDUAL_TOL, max_relative_residual, real_converged
 
 pytestmark = pytest.mark.gpu
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-NOISE_SEED = 20250215   # synthcurves.DEFAULT_SEED: the bench's first config-5 trial
-
 
 @pytest.fixture(scope="module")
-def noisy1px(problem, ransac0):
-    from trifocal_pose_estimation_using_improved_gpuhc_amd import prepare_target_params, synthcurves
-    nd = synthcurves.noisy(ransac0, 1.0, NOISE_SEED)
+def noisy1px(problem):
+    from trifocal_pose_estimation_using_improved_gpuhc_amd import prepare_target_params
+    nd = noisy_data()
     tgt, dif, picked = prepare_target_params(problem, nd, seed=0, num_samples=100)
     return nd, tgt, dif, picked
 
 
 def test_noisy_samples_match_golden(noisy1px):
     """The native noise generator + Prepare_Target_Params reproduce the fixture's inputs."""
-    g = np.load(os.path.join(GOLDEN, "gpuhc_noisy1px_N100.npz"))
+    g = golden("gpuhc_noisy1px_N100")
     _, tgt, dif, picked = noisy1px
     assert np.array_equal(picked, g["picked"])
     assert np.array_equal(tgt, g["target"]) and np.array_equal(dif, g["diff"])
@@ -48,34 +45,23 @@ def test_noisy_tracker_matches_oracle_small(problem, oracle, tracker, noisy1px):
     """Config 5 inputs, 2 samples (624 paths), value for value against the oracle."""
     _, tgt, dif, _ = noisy1px
     r = tracker.track(tgt[:2], dif[:2]).host()
-    tr, conv, inf, st = oracle.gpuhc_track(problem.start_sols, problem.start_params, tgt[:2], dif[:2],
-                                           problem.unified_index)
-    assert (r["converge"] == conv).all() and (r["infinity"] == inf).all()
-    assert (r["stats"]["steps"] == st["steps"]).all() and (r["stats"]["corrections"] == st["corrections"]).all()
-    bad = ~same(r["tracks"][:, :30], tr[:, :30]).all(axis=(1, 2))
-    assert not bad.any(), f"{bad.sum()} tracks differ"
+    assert_matches_oracle(r, oracle.gpuhc_track(problem.start_sols, problem.start_params, tgt[:2], dif[:2],
+                                                problem.unified_index))
 
 
 def test_noisy_tracker_and_pose_match_golden_N100(tracker, noisy1px):
     """Config 5, 100 samples: every flag / count / track hash equals the oracle's
     golden run; the device pose support over the HIP tracks selects the golden
     paths with the golden inlier counts, and its GT verdict is the golden one."""
-    import sys
-
     from trifocal_pose_estimation_using_improved_gpuhc_amd import count_solutions, pose
-    sys.path.insert(0, GOLDEN)
-    from make_golden import track_hash
-    g = np.load(os.path.join(GOLDEN, "gpuhc_noisy1px_N100.npz"))
+    g = golden("gpuhc_noisy1px_N100")
     nd, tgt, dif, _ = noisy1px
     res = tracker.track(tgt, dif)
     r = res.host()
-    assert (r["converge"] == g["conv"]).all() and (r["infinity"] == g["inf"]).all()
-    assert (r["stats"]["steps"] == g["steps"]).all() and (r["stats"]["corrections"] == g["corrections"]).all()
-    h = track_hash(r["tracks"])
-    assert (h == g["hash"]).all(), f"{(h != g['hash']).sum()} track hashes differ"
+    assert_matches_golden(r, g)
     assert tuple(g["counts"]) == count_solutions(r["tracks"], r["converge"], r["infinity"])
     import torch
-    E = torch.from_numpy(np.ascontiguousarray(nd.locations)).to(tracker.device)
+    E = torch.from_numpy(np.array(nd.locations)).to(tracker.device)
     inl, sel = pose.pose_support(res.tracks, res.converge, E, tracker.K)
     assert sel["num_candidates"] == int(g["num_candidates"])
     assert [sel["path21"], sel["path31"]] == g["path"].tolist()
@@ -103,35 +89,27 @@ def test_largest_launch_config4_workload_on_one_gpu(problem, oracle, tracker, ra
     are one sequence, so the first 100 samples equal the N = 100 golden run;
     700 paths drawn across the launch equal the oracle's tracks of the same
     batch ids; every suspended path was resumed."""
-    import sys
-
     import torch
 
     from trifocal_pose_estimation_using_improved_gpuhc_amd import prepare_target_params
-    sys.path.insert(0, GOLDEN)
-    from make_golden import track_hash
     N = 8000
     tgt, dif, _ = prepare_target_params(problem, ransac0, seed=0, num_samples=N)
     r = tracker.track(tgt, dif)
-    off = int(tracker.L.hc_trifocal_workspace_size())
-    rq = np.frombuffer(tracker.workspace[off:off + 768].cpu().numpy().tobytes(), np.uint32)
-    assert rq[64] > 100000 and rq[0] == rq[64] and rq[128] == 0, "sliced, and every suspended path resumed"
+    head, tail, avail = ring_counters(tracker)
+    assert tail > 100000 and head == tail and avail == 0, "sliced, and every suspended path resumed"
     st = r.stats.cpu().numpy().view(np.int32).reshape(-1, 4)
     assert (st[:, 0] >= 1).all() and (st[:, 0] <= tracker.settings.max_steps + 1).all()
-    g = np.load(os.path.join(GOLDEN, "gpuhc_N100_seed0.npz"))
-    n0 = 100 * 312
-    assert np.array_equal(r.converge[:n0].cpu().numpy(), g["conv"])
-    assert np.array_equal(r.infinity[:n0].cpu().numpy(), g["inf"])
-    assert np.array_equal(st[:n0, 0], g["steps"]) and np.array_equal(st[:n0, 1], g["corrections"])
-    assert (track_hash(r.tracks[:n0].cpu().numpy()) == g["hash"]).all()
+
+    def rows(sel):   # the host dict of some rows (all 2 496 000 tracks are 619 MB)
+        at = torch.from_numpy(np.arange(N * 312)[sel]).to(r.tracks.device)
+        return dict(tracks=r.tracks[at].cpu().numpy(), converge=r.converge[at].cpu().numpy(),
+                    infinity=r.infinity[at].cpu().numpy(), stats=dict(steps=st[sel, 0], corrections=st[sel, 1]))
+
+    assert_matches_golden(rows(slice(0, 100 * 312)), golden("gpuhc_N100_seed0"))
     ids = np.sort(np.random.default_rng(7).choice(N * 312, 700, replace=False))
-    idx = torch.from_numpy(ids).to(r.tracks.device)
     o_tr, o_conv, o_inf, o_st = oracle.gpuhc_track_subset(ids, problem.start_sols, problem.start_params, tgt, dif,
                                                           problem.unified_index)
-    assert np.array_equal(r.converge[idx].cpu().numpy(), o_conv[ids])
-    assert np.array_equal(r.infinity[idx].cpu().numpy(), o_inf[ids])
-    assert np.array_equal(st[ids, 0], o_st["steps"][ids]) and np.array_equal(st[ids, 1], o_st["corrections"][ids])
-    assert same(r.tracks[idx].cpu().numpy()[:, :30], o_tr[ids, :30]).all()
+    assert_same_run(rows(ids), o_tr[ids], o_conv[ids], o_inf[ids], o_st["steps"][ids], o_st["corrections"][ids])
 
 
 @pytest.mark.parametrize("inflight_stop", [0, 1])
@@ -149,26 +127,17 @@ def test_abort_config3_N1000(problem, oracle, tracker, ransac0, inflight_stop):
     tgt, dif, _ = prepare_target_params(problem, ransac0, seed=0, num_samples=N)
     r = tracker.track(tgt, dif, abort=True, inflight_stop=bool(inflight_stop)).host()
     assert r["found"]
-    found = np.nonzero(r["batch_index"] >= 0)[0]
-    assert len(found) > 0 and (r["batch_index"][found] == found).all()
+    found = found_ids(r)
     st = r["stats"]
-    tracked = st["steps"] > 0
-    assert tracked[found].all() and (r["converge"][found] == 1).all()
-    check = np.nonzero(tracked)[0]
-    tr, conv, inf, ost = oracle.gpuhc_track_subset(check, problem.start_sols, problem.start_params, tgt, dif,
-                                                   problem.unified_index)
-    assert (r["converge"][check] == conv[check]).all() and (r["infinity"][check] == inf[check]).all()
-    assert (st["steps"][check] == ost["steps"][check]).all()
-    assert (st["corrections"][check] == ost["corrections"][check]).all()
-    assert same(r["tracks"][check, :30], tr[check, :30]).all()
+    trk = tracked(r)
+    assert len(found) > 0 and trk[found].all() and (r["converge"][found] == 1).all()
+    check = np.nonzero(trk)[0]
+    assert_matches_oracle(r, oracle.gpuhc_track_subset(check, problem.start_sols, problem.start_params, tgt, dif,
+                                                       problem.unified_index), where=check)
     for b in found:
         ok, i21, i31 = oracle.score_hypothesis(r["tracks"][b], ransac0.locations, ransac0.K)
         assert ok == 1 and (st["inliers21"][b], st["inliers31"][b]) == (i21, i31)
-    skipped = ~tracked
-    assert skipped.any()
-    assert (r["converge"][skipped] == 0).all() and (st["corrections"][skipped] == 0).all()
-    start = np.tile(problem.start_sols[None, :, :30], (N, 1, 1, 1)).reshape(-1, 30, 2)
-    assert np.array_equal(r["tracks"][skipped][:, :30], start[skipped])
+    assert_untouched(r, problem.start_sols, ~trk)
     if inflight_stop == 0:
         # nothing is cut short: every tracked path either converged, diverged,
         # was pruned or ran out of steps -- exactly what the oracle reports for it
@@ -188,32 +157,22 @@ def test_heldout_dataset_matches_golden_N100(problem, oracle, tracker, ds):
     golden run (flags, counts, track hashes); the device pose support over the
     HIP tracks selects the golden paths, and its verdict against GT_Poses21/31
     of the same dataset is the golden one."""
-    import sys
-
     import torch
 
     from trifocal_pose_estimation_using_improved_gpuhc_amd import (count_solutions, load_ransac_data, pose,
                                                                    prepare_target_params)
-    sys.path.insert(0, GOLDEN)
-    from make_golden import track_hash
-    g = np.load(os.path.join(GOLDEN, f"gpuhc_ds{ds}_N100_seed0.npz"))
+    g = golden(f"gpuhc_ds{ds}_N100_seed0")
     data = load_ransac_data(int(ds))
     tgt, dif, picked = prepare_target_params(problem, data, seed=0, num_samples=100)
     assert np.array_equal(picked, g["picked"]) and np.array_equal(tgt, g["target"]) and np.array_equal(dif, g["diff"])
     if ds == "050":
         r2 = tracker.track(tgt[:2], dif[:2]).host()
-        tr, conv, inf, st = oracle.gpuhc_track(problem.start_sols, problem.start_params, tgt[:2], dif[:2],
-                                               problem.unified_index)
-        assert (r2["converge"] == conv).all() and (r2["infinity"] == inf).all()
-        assert (r2["stats"]["steps"] == st["steps"]).all()
-        assert same(r2["tracks"][:, :30], tr[:, :30]).all()
+        assert_matches_oracle(r2, oracle.gpuhc_track(problem.start_sols, problem.start_params, tgt[:2], dif[:2],
+                                                     problem.unified_index))
     res = tracker.track(tgt, dif)
     r = res.host()
-    assert (r["converge"] == g["conv"]).all() and (r["infinity"] == g["inf"]).all()
-    assert (r["stats"]["steps"] == g["steps"]).all() and (r["stats"]["corrections"] == g["corrections"]).all()
+    assert_matches_golden(r, g)
     assert same(r["tracks"][:624, :30], g["tracks_s01"][:, :30]).all()
-    h = track_hash(r["tracks"])
-    assert (h == g["hash"]).all(), f"{(h != g['hash']).sum()} track hashes differ"
     assert tuple(g["counts"]) == count_solutions(r["tracks"], r["converge"], r["infinity"])
     E = torch.from_numpy(np.ascontiguousarray(data.locations)).to(tracker.device)
     K = torch.from_numpy(np.ascontiguousarray(data.K)).to(tracker.device)

@@ -16,48 +16,31 @@ clean data path 104 of dataset 000 has E of E joint inliers for any prefix of
 the edgels, the other candidates of 000's first 8 samples at most 195 of 5117,
 and no candidate of dataset 099's 128 samples reaches half its edgels.
 """
-import os
-
 import numpy as np
 import pytest
 
-from conftest import same
+import checks
+from checks import GroupCase, check_group_result, gate_score, noisy_data
 
 pytestmark = pytest.mark.gpu
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 NEVER = 2.0      # a ratio > 1 never passes: every path is tracked and scored
 
 
-class Case:
+def Case(problem, tracker, ds, samples, **kw):
     """A TripletBatch, its device copy, the plain track() of all its samples
     and the grouped joint pose support of those plain tracks (n x 3 counts)."""
-
-    def __init__(self, problem, tracker, ds, samples, interleave=False, edgel_counts=None, plain=None):
-        from trifocal_pose_estimation_using_improved_gpuhc_amd import pose
-        from trifocal_pose_estimation_using_improved_gpuhc_amd.multi import TripletBatch
-        self.batch = TripletBatch(problem, ds, seeds=0, samples_per_triplet=samples, interleave=interleave,
-                                  edgel_counts=edgel_counts)
-        self.dev = self.batch.to(tracker.device)
-        self.plain_dev = plain if plain is not None else tracker.track(self.batch.target, self.batch.diff)
-        self.plain = self.plain_dev.host()
-        self.counts, _ = pose.pose_support_joint_grouped(self.plain_dev.tracks, self.plain_dev.converge, self.dev)
-        for v in list(self.plain.values()) + [self.counts]:
-            v.setflags(write=False)
-        self.E_of_path = np.repeat(self.batch.edgel_counts[self.batch.sample_group], 312)
+    return GroupCase.on_device(problem, tracker, ds, samples, joint=True, **kw)
 
 
 @pytest.fixture(scope="module")
-def noisy0(ransac0):
-    from trifocal_pose_estimation_using_improved_gpuhc_amd import synthcurves
-    d = synthcurves.noisy(ransac0, 1.0, 20250215)
-    d.locations.setflags(write=False)
-    return d
+def noisy0():
+    return noisy_data()
 
 
 @pytest.fixture(scope="module")
 def golden():
-    return np.load(os.path.join(GOLDEN, "pose_joint_noisy1px_N100.npz"))
+    return checks.golden("pose_joint_noisy1px_N100")
 
 
 @pytest.fixture(scope="module")
@@ -76,63 +59,10 @@ def clean8(problem, tracker, ransac0):   # test 4: the plain tracks shared by ev
     return Case(problem, tracker, [ransac0], 8)
 
 
-def _passes(counts, E, gate):
-    """The gate in double, as the kernel states it (the ratio is a float32)."""
-    return counts.astype(np.float64) >= float(np.float32(gate)) * E.astype(np.float64)
-
-
-def _check_gated(r, case, problem, gate, found, found_ids, all_tracked=(), none_tracked=(), tick_groups=None):
-    """The checks of a gated result r (host dict) of case's batch -- those of
-    an abort-mode result, with the pose-support counts in the oracle's place.
-    found: the expected flags; found_ids: the expected set of batch_index
-    entries (None: derived from the counts alone); all_tracked / none_tracked:
-    groups whose paths must all / must none be tracked; tick_groups: the groups
-    that found in this launch (default: those flagged).  Returns `tracked`."""
-    b, plain, ref = case.batch, case.plain, case.counts
-    n = b.num_samples * 312
-    assert r["found"].tolist() == found
-    ids = np.nonzero(r["batch_index"] >= 0)[0]
-    assert (r["batch_index"][ids] == ids).all()
-    st = r["stats"]
-    ji = r["joint_inliers"]
-    assert ji.shape == (n,) and ji.dtype == np.int32
-    tracked = st["steps"] > 0     # every path of these inputs takes >= 13 steps
-    group_of_path = np.repeat(b.sample_group, 312)
-    tick_groups = [t for t, f in enumerate(found) if f] if tick_groups is None else tick_groups
-    # the passing paths are exactly the tracked paths whose joint count meets the gate
-    scored = tracked & (ref[:, 0] >= 0)
-    expect = np.nonzero(scored & _passes(ref[:, 0], case.E_of_path, gate))[0]
-    assert ids.tolist() == expect.tolist()
-    if found_ids is not None:
-        assert set(ids.tolist()) == set(found_ids)
-    assert set(group_of_path[ids].tolist()) == set(tick_groups)
-    for p in ids:
-        assert tracked[p] and r["converge"][p] == 1 and ji[p] == ref[p, 0]
-    # every tracked path is the plain launch's path of the same batch id, and
-    # carries the pose-support counts of that path
-    assert (r["converge"][tracked] == plain["converge"][tracked]).all()
-    assert (r["infinity"][tracked] == plain["infinity"][tracked]).all()
-    assert (st["steps"][tracked] == plain["stats"]["steps"][tracked]).all()
-    assert (st["corrections"][tracked] == plain["stats"]["corrections"][tracked]).all()
-    assert same(r["tracks"][tracked, :30], plain["tracks"][tracked, :30]).all()
-    assert np.array_equal(ji[tracked], ref[tracked, 0])            # -1 where not scored
-    assert np.array_equal(st["inliers21"][tracked], np.maximum(ref[tracked, 1], 0))
-    assert np.array_equal(st["inliers31"][tracked], np.maximum(ref[tracked, 2], 0))
-    # every other path: conv 0, zero stats, the start solution, no count
-    un = ~tracked
-    assert (r["converge"][un] == 0).all() and (r["infinity"][un] == 0).all()
-    for k in ("steps", "corrections", "inliers21", "inliers31"):
-        assert (st[k][un] == 0).all(), k
-    assert (ji[un] == -1).all()
-    start = np.tile(problem.start_sols[None], (b.num_samples, 1, 1, 1)).reshape(n, 31, 2)
-    assert np.array_equal(r["tracks"][un], start[un])
-    for t in all_tracked:
-        assert tracked[b.path_index(t)].all(), f"group {t}: {(~tracked[b.path_index(t)]).sum()} paths not tracked"
-    for t in none_tracked:
-        assert not tracked[b.path_index(t)].any(), f"group {t}: {tracked[b.path_index(t)].sum()} paths tracked"
-    ticks = r["found_ticks"]
-    assert [t for t in range(b.num_groups) if ticks[t] != 0] == sorted(tick_groups)
-    return tracked
+def _check_gated(r, case, problem, gate, found, expect_ids, **kw):
+    """checks.check_group_result with the pose-support counts against the gate
+    in the oracle's place (expect_ids None: derived from the counts alone)."""
+    return check_group_result(r, case, problem.start_sols, gate_score(gate), found, expect_ids, **kw)
 
 
 def test_counts_nothing_fires(problem, tracker, noisy_case, golden):
@@ -143,11 +73,7 @@ def test_counts_nothing_fires(problem, tracker, noisy_case, golden):
     r = tracker.track_grouped(c.dev, gate=NEVER).host()
     tracked = _check_gated(r, c, problem, NEVER, [0], set(), all_tracked=(0,))
     assert tracked.all() and tracked.shape == (31200,)
-    plain, st = c.plain, r["stats"]
-    assert same(r["tracks"][:, :30], plain["tracks"][:, :30]).all()
-    assert (r["converge"] == plain["converge"]).all() and (r["infinity"] == plain["infinity"]).all()
-    assert (st["steps"] == plain["stats"]["steps"]).all()
-    assert (st["corrections"] == plain["stats"]["corrections"]).all()
+    st = r["stats"]
     assert np.array_equal(r["joint_inliers"], c.counts[:, 0])
     sc = c.counts[:, 0] >= 0
     assert np.array_equal(st["inliers21"][sc], c.counts[sc, 1]) and np.array_equal(st["inliers31"][sc], c.counts[sc, 2])

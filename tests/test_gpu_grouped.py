@@ -17,7 +17,7 @@ abort gate at sample 0 track 104 only, 050 (E = 1000) at sample 2 track 52 only,
 import numpy as np
 import pytest
 
-from conftest import same
+from checks import GroupCase, check_group_result, found_ids, oracle_score
 
 pytestmark = pytest.mark.gpu
 
@@ -28,18 +28,9 @@ def datas():
     return {i: load_ransac_data(i) for i in (0, 1, 10, 50, 99)}
 
 
-class Case:
+def Case(problem, tracker, ds, samples, **kw):
     """A TripletBatch, its device copy and the plain track() of all its samples."""
-
-    def __init__(self, problem, tracker, ds, samples, interleave=False, edgel_counts=None):
-        from trifocal_pose_estimation_using_improved_gpuhc_amd.multi import TripletBatch
-        self.batch = TripletBatch(problem, ds, seeds=0, samples_per_triplet=samples, interleave=interleave,
-                                  edgel_counts=edgel_counts)
-        self.dev = self.batch.to(tracker.device)
-        self.plain_dev = tracker.track(self.batch.target, self.batch.diff)
-        self.plain = self.plain_dev.host()
-        for v in self.plain.values():
-            v.setflags(write=False)
+    return GroupCase.on_device(problem, tracker, ds, samples, **kw)
 
 
 @pytest.fixture(scope="module")
@@ -119,51 +110,9 @@ def test_pose_grouped_interleaved_views_disagree(tracker, mixed_case):
     assert sorted([sels[1]["path21"], sels[1]["path31"]]) == sorted([int(ids[11767]), int(ids[32971])])
 
 
-def _check_abort(r, case, problem, oracle, found, found_ids, all_tracked, none_tracked=(), tick_groups=None):
-    """The checks of an abort-mode result r (host dict) of case's batch.
-    found: the expected flags; found_ids: the expected set of batch_index
-    entries (None: a non-empty set within the finding groups); all_tracked /
-    none_tracked: groups whose paths must all / must none be tracked;
-    tick_groups: the groups that found in this launch (default: those flagged)."""
-    b, plain = case.batch, case.plain
-    n = b.num_samples * 312
-    assert r["found"].tolist() == found
-    ids = np.nonzero(r["batch_index"] >= 0)[0]
-    assert (r["batch_index"][ids] == ids).all()
-    if found_ids is not None:
-        assert set(ids.tolist()) == set(found_ids)
-    else:
-        assert len(ids) > 0
-    st = r["stats"]
-    tracked = st["steps"] > 0
-    group_of_path = np.repeat(b.sample_group, 312)
-    tick_groups = [t for t, f in enumerate(found) if f] if tick_groups is None else tick_groups
-    assert set(group_of_path[ids].tolist()) == set(tick_groups)
-    for p in ids:
-        t = int(group_of_path[p])
-        ok, i21, i31 = oracle.score_hypothesis(r["tracks"][p], b.locations[t], b.Ks[t])
-        assert ok == 1 and (st["inliers21"][p], st["inliers31"][p]) == (i21, i31), p
-        assert tracked[p] and r["converge"][p] == 1
-    # every tracked path is the plain launch's path of the same batch id
-    assert (r["converge"][tracked] == plain["converge"][tracked]).all()
-    assert (r["infinity"][tracked] == plain["infinity"][tracked]).all()
-    assert (st["steps"][tracked] == plain["stats"]["steps"][tracked]).all()
-    assert (st["corrections"][tracked] == plain["stats"]["corrections"][tracked]).all()
-    assert same(r["tracks"][tracked, :30], plain["tracks"][tracked, :30]).all()
-    # every other path: conv 0, zero stats, the start solution
-    un = ~tracked
-    assert (r["converge"][un] == 0).all() and (r["infinity"][un] == 0).all()
-    for k in ("steps", "corrections", "inliers21", "inliers31"):
-        assert (st[k][un] == 0).all(), k
-    start = np.tile(problem.start_sols[None], (b.num_samples, 1, 1, 1)).reshape(n, 31, 2)
-    assert np.array_equal(r["tracks"][un], start[un])
-    for t in all_tracked:
-        assert tracked[b.path_index(t)].all(), f"group {t}: {(~tracked[b.path_index(t)]).sum()} paths not tracked"
-    for t in none_tracked:
-        assert not tracked[b.path_index(t)].any(), f"group {t}: {tracked[b.path_index(t)].sum()} paths tracked"
-    ticks = r["found_ticks"]
-    assert [t for t in range(b.num_groups) if ticks[t] != 0] == sorted(tick_groups)
-    return tracked
+def _check_abort(r, case, problem, oracle, found, expect_ids, all_tracked, **kw):
+    """checks.check_group_result with the oracle's scoring of the found paths."""
+    return check_group_result(r, case, problem.start_sols, oracle_score(oracle), found, expect_ids, all_tracked, **kw)
 
 
 @pytest.mark.parametrize("inflight_stop", [0, 1])
@@ -187,7 +136,7 @@ def test_abort_grouped_single_triplet(problem, oracle, tracker, datas, inflight_
     _check_abort(r, c, problem, oracle, [1], {104}, all_tracked=())
     single = tracker.track(c.batch.target, c.batch.diff, abort=True, inflight_stop=bool(inflight_stop)).host()
     assert single["found"] is True
-    assert set(np.nonzero(single["batch_index"] >= 0)[0].tolist()) == {104}
+    assert set(found_ids(single).tolist()) == {104}
 
 
 def test_abort_grouped_interleaved(problem, oracle, tracker, mixed_case):

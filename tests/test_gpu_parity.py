@@ -4,33 +4,15 @@ Bar: identical values -- the kernel and the oracle implement the sam
 op-level spec, so every float must match exactly, treating +0 == -0 and
 NaN == NaN; converged / infinity flags and step / correction counts identical.
 """
-import contextlib
-import ctypes
-import os
-
 import numpy as np
 import pytest
 
+from checks import (KERNEL_BY_SIZE, SMALL_ALWAYS, SMALL_NEVER, assert_bit_identical, assert_matches_golden,
+                    assert_matches_oracle, assert_untouched, found_ids, golden, golden_passing, launch_mode,
+                    ring_counters, run_cli, scaled_samples, tracked)
 from conftest import same
 
 pytestmark = pytest.mark.gpu
-
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-
-# Tracking launches run the latency-mode kernel (k_track_small) when they fill
-# at most half of the path slots (N <= 16 samples), the throughput kernel
-# (k_track) otherwise; the tests below run each size through both
-# (hc_trifocal_set_small_launch: 0 by size, 1 always small, -1 never).
-KERNEL_BY_SIZE, SMALL_ALWAYS, SMALL_NEVER = 0, 1, -1
-
-
-@contextlib.contextmanager
-def small_launch(L, mode):
-    L.hc_trifocal_set_small_launch(mode)
-    try:
-        yield
-    finally:
-        L.hc_trifocal_set_small_launch(KERNEL_BY_SIZE)
 
 
 def _jacobians_from_path(problem, oracle, tgt, dif, n=64, seed=1):
@@ -63,7 +45,7 @@ def test_eval_matches_oracle(problem, oracle, samples100):
 
 def test_eval_golden_kat(problem):
     from trifocal_pose_estimation_using_improved_gpuhc_amd.tracker import eval_batched
-    g = np.load(os.path.join(GOLDEN, "kat_eval.npz"))
+    g = golden("kat_eval")
     HX, HT, H = eval_batched(problem.unified_index, g["x"][None], g["p"][None], g["d"][None])
     assert same(HX[0], g["Hx"]).all() and same(HT[0], g["Ht"]).all() and same(H[0], g["H"]).all()
 
@@ -145,16 +127,10 @@ def test_tracker_matches_oracle_small(problem, oracle, samples100, tracker, mode
     """Full GPU-HC tracking of 2 samples (624 paths) vs the oracle, value for value."""
     tgt, dif, _ = samples100
     N = 2
-    with small_launch(tracker.L, mode):
+    with launch_mode(tracker.L, mode):
         r = tracker.track(tgt[:N], dif[:N]).host()
-    tr, conv, inf, st = oracle.gpuhc_track(problem.start_sols, problem.start_params, tgt[:N], dif[:N],
-                                           problem.unified_index)
-    assert (r["converge"] == conv).all()
-    assert (r["infinity"] == inf).all()
-    assert (r["stats"]["steps"] == st["steps"]).all()
-    assert (r["stats"]["corrections"] == st["corrections"]).all()
-    bad = ~same(r["tracks"][:, :30], tr[:, :30]).all(axis=(1, 2))
-    assert not bad.any(), f"{bad.sum()} tracks differ, first {np.nonzero(bad)[0][:5]}"
+    assert_matches_oracle(r, oracle.gpuhc_track(problem.start_sols, problem.start_params, tgt[:N], dif[:N],
+                                                problem.unified_index))
     # x[30] is never written by the kernel (reference :282 writes tx < 30 only)
     assert (r["tracks"][:, 30, 0] == 1.0).all()
 
@@ -171,20 +147,12 @@ def test_tracker_dense_resolve_matches_oracle(problem, oracle, samples100, track
     one, so a normal half is re-solved densely beside a scaled half (the redo is
     wave-uniform) and must come out identical.  Bit-exact against the oracle."""
     tgt, dif, _ = samples100
-    T = [tgt[0]]
-    for sc in (2.0 ** 40, 2.0 ** 70):
-        T.append((tgt[0] * np.float32(sc)).astype(np.float32))
-    T = np.stack(T)
-    D = (T - problem.start_params[None]).astype(np.float32)   # prepare_target_params' diff
-    assert np.array_equal(D[0], dif[0])
-    with small_launch(tracker.L, mode):
+    T, D = scaled_samples(problem, tgt[0], (0, 40, 70))
+    assert np.array_equal(T[0], tgt[0]) and np.array_equal(D[0], dif[0])
+    with launch_mode(tracker.L, mode):
         r = tracker.track(T, D).host()
-    tr, conv, inf, st = oracle.gpuhc_track(problem.start_sols, problem.start_params, T, D, problem.unified_index)
-    assert (r["converge"] == conv).all() and (r["infinity"] == inf).all()
-    assert (r["stats"]["steps"] == st["steps"]).all()
-    assert (r["stats"]["corrections"] == st["corrections"]).all()
-    bad = ~same(r["tracks"][:, :30], tr[:, :30]).all(axis=(1, 2))
-    assert not bad.any(), f"{bad.sum()} tracks differ, first {np.nonzero(bad)[0][:5]}"
+    ref = _, conv, inf, _ = oracle.gpuhc_track(problem.start_sols, problem.start_params, T, D, problem.unified_index)
+    assert_matches_oracle(r, ref)
     assert inf[312:].sum() > 600 and conv[:312].sum() > 0   # the scaled samples diverge, sample 0 converges
 
 
@@ -195,37 +163,26 @@ def test_tracker_dense_resolve_abort_mode(problem, oracle, samples100, tracker):
     before any hypothesis can pass, then config 2's sample 0.  Every tracked
     path equals the oracle's abort-off run bit for bit."""
     tgt, dif, _ = samples100
-    T = np.stack([(tgt[0] * np.float32(2.0 ** 40)).astype(np.float32),
-                  (tgt[0] * np.float32(2.0 ** 70)).astype(np.float32), tgt[0]])
-    D = (T - problem.start_params[None]).astype(np.float32)
+    T, D = scaled_samples(problem, tgt[0], (40, 70, 0))
     r = tracker.track(T, D, abort=True).host()
     tracker.workspace_status()
-    tr, conv, inf, st = oracle.gpuhc_track(problem.start_sols, problem.start_params, T, D, problem.unified_index)
-    tracked = r["stats"]["steps"] > 0
-    assert tracked[:624].all(), "the scaled samples' paths must all be tracked"
-    assert (r["converge"][tracked] == conv[tracked]).all() and (r["infinity"][tracked] == inf[tracked]).all()
-    assert (r["stats"]["steps"][tracked] == st["steps"][tracked]).all()
-    assert (r["stats"]["corrections"][tracked] == st["corrections"][tracked]).all()
-    assert same(r["tracks"][tracked][:, :30], tr[tracked][:, :30]).all()
-    assert inf[:624].sum() > 600
+    ref = oracle.gpuhc_track(problem.start_sols, problem.start_params, T, D, problem.unified_index)
+    trk = tracked(r)
+    assert trk[:624].all(), "the scaled samples' paths must all be tracked"
+    assert_matches_oracle(r, ref, where=trk)
+    assert_untouched(r, problem.start_sols, ~trk, allow_empty=True)
+    found_ids(r)
+    assert ref[2][:624].sum() > 600
 
 
 @pytest.mark.parametrize("mode", [KERNEL_BY_SIZE, SMALL_ALWAYS], ids=["throughput_kernel", "latency_kernel"])
 def test_tracker_matches_golden_N100(problem, samples100, tracker, mode):
     """Config 2 (100 samples, abort off): every flag / count / track hash equals the committed golden run."""
-    import sys
-    sys.path.insert(0, GOLDEN)
-    from make_golden import track_hash
-    g = np.load(os.path.join(GOLDEN, "gpuhc_N100_seed0.npz"))
+    g = golden("gpuhc_N100_seed0")
     tgt, dif, _ = samples100
-    with small_launch(tracker.L, mode):
+    with launch_mode(tracker.L, mode):
         r = tracker.track(tgt, dif).host()
-    assert (r["converge"] == g["conv"]).all()
-    assert (r["infinity"] == g["inf"]).all()
-    assert (r["stats"]["steps"] == g["steps"]).all()
-    assert (r["stats"]["corrections"] == g["corrections"]).all()
-    h = track_hash(r["tracks"])
-    assert (h == g["hash"]).all(), f"{(h != g['hash']).sum()} track hashes differ"
+    assert_matches_golden(r, g)
     from trifocal_pose_estimation_using_improved_gpuhc_amd import count_solutions
     assert tuple(g["counts"]) == count_solutions(r["tracks"], r["converge"], r["infinity"])
     # per-path real flags: the input of the prefix pin against the reference's
@@ -244,15 +201,10 @@ def test_time_slicing_is_bit_exact(problem, samples100, tracker):
     tgt, dif, _ = samples100
     a = tracker.track(tgt, dif, time_slicing=False).host()
     b = tracker.track(tgt, dif, time_slicing=True).host()
-    # ring counters after the base workspace (hc_kernels.hip KArgs::rq): [0] head, [64] tail, [128] avail
-    off = int(tracker.L.hc_trifocal_workspace_size())
-    rq = np.frombuffer(tracker.workspace[off:off + 768].cpu().numpy().tobytes(), np.uint32)
-    assert rq[64] > 1000, f"only {rq[64]} suspensions"
-    assert rq[0] == rq[64] and rq[128] == 0, "every suspended path was resumed"
-    assert (a["converge"] == b["converge"]).all() and (a["infinity"] == b["infinity"]).all()
-    assert np.array_equal(a["stats"]["steps"], b["stats"]["steps"])
-    assert np.array_equal(a["stats"]["corrections"], b["stats"]["corrections"])
-    assert np.array_equal(a["tracks"].view(np.uint32), b["tracks"].view(np.uint32))
+    head, tail, avail = ring_counters(tracker)
+    assert tail > 1000, f"only {tail} suspensions"
+    assert head == tail and avail == 0, "every suspended path was resumed"
+    assert_bit_identical(a, b)
 
 
 def test_time_slicing_concurrent_streams(problem, samples100, tracker):
@@ -275,11 +227,8 @@ def test_time_slicing_concurrent_streams(problem, samples100, tracker):
         tracker.launch(t, d, bufs[k], stream=streams[k], workspace=wss[k])
     torch.cuda.synchronize(dev)
     for k in range(4):
-        h = bufs[k].host()
-        assert int(tracker.L.hc_trifocal_workspace_status(ctypes.c_void_p(wss[k].data_ptr()))) == 0
-        assert (h["converge"] == ref["converge"]).all() and (h["infinity"] == ref["infinity"]).all()
-        assert np.array_equal(h["stats"]["steps"], ref["stats"]["steps"])
-        assert np.array_equal(h["tracks"].view(np.uint32), ref["tracks"].view(np.uint32))
+        tracker.workspace_status(wss[k])
+        assert_bit_identical(bufs[k].host(), ref)
 
 
 def test_small_and_large_launches_share_a_workspace(problem, samples100, tracker):
@@ -293,21 +242,14 @@ def test_small_and_large_launches_share_a_workspace(problem, samples100, tracker
     ref = tracker.track(tgt, dif, time_slicing=False).host()
     dev = tracker.device
     t, d = torch.from_numpy(tgt).to(dev), torch.from_numpy(dif).to(dev)
-
-    def check(h, n):
-        sl = slice(0, n * 312)
-        assert (h["converge"] == ref["converge"][sl]).all() and (h["infinity"] == ref["infinity"][sl]).all()
-        assert np.array_equal(h["stats"]["steps"], ref["stats"]["steps"][sl])
-        assert np.array_equal(h["tracks"].view(np.uint32), ref["tracks"][sl].view(np.uint32))
-
     ws = tracker.new_workspace(100)
     for n in (100, 8, 100, 2):
         r = tracker.allocate(n)
         tracker.reset_tracks(r)
         tracker.launch(t, d, r, workspace=ws, num_samples=n)
         torch.cuda.synchronize(dev)
-        assert int(tracker.L.hc_trifocal_workspace_status(ctypes.c_void_p(ws.data_ptr()))) == 0
-        check(r.host(), n)
+        tracker.workspace_status(ws)
+        assert_bit_identical(r.host(), ref, rows=slice(0, n * 312))
     streams = [torch.cuda.Stream(dev) for _ in range(4)]
     bufs = [tracker.allocate(8) for _ in range(4)]
     wss = [tracker.new_workspace(8) for _ in range(4)]
@@ -318,8 +260,8 @@ def test_small_and_large_launches_share_a_workspace(problem, samples100, tracker
         tracker.launch(t, d, bufs[k], stream=streams[k], workspace=wss[k], num_samples=8)
     torch.cuda.synchronize(dev)
     for k in range(4):
-        assert int(tracker.L.hc_trifocal_workspace_status(ctypes.c_void_p(wss[k].data_ptr()))) == 0
-        check(bufs[k].host(), 8)
+        tracker.workspace_status(wss[k])
+        assert_bit_identical(bufs[k].host(), ref, rows=slice(0, 8 * 312))
 
 
 def test_time_slicing_falls_back_when_the_ring_does_not_fit(problem, samples100, tracker):
@@ -338,12 +280,8 @@ def test_time_slicing_falls_back_when_the_ring_does_not_fit(problem, samples100,
     tracker.reset_tracks(r)
     tracker.launch(torch.from_numpy(tgt).to(dev), torch.from_numpy(dif).to(dev), r, workspace=ws)
     torch.cuda.synchronize(dev)
-    off = int(tracker.L.hc_trifocal_workspace_size())
-    rq = np.frombuffer(ws[off:off + 768].cpu().numpy().tobytes(), np.uint32)
-    assert rq[64] == 0, "a launch whose ring does not fit must not slice"
-    h = r.host()
-    assert (h["converge"] == ref["converge"]).all()
-    assert np.array_equal(h["tracks"].view(np.uint32), ref["tracks"].view(np.uint32))
+    assert ring_counters(tracker, ws)[1] == 0, "a launch whose ring does not fit must not slice"
+    assert_bit_identical(r.host(), ref)
 
 
 def test_time_slicing_workspace_reused_across_launch_sizes(problem, samples100, tracker):
@@ -366,9 +304,10 @@ def test_time_slicing_workspace_reused_across_launch_sizes(problem, samples100, 
         tracker.reset_tracks(r)
         tracker.launch(t, d, r, workspace=ws, num_samples=n)
         torch.cuda.synchronize(dev)
-        assert int(tracker.L.hc_trifocal_workspace_status(ctypes.c_void_p(ws.data_ptr()))) == 0
+        tracker.workspace_status(ws)
+        head, tail, _ = ring_counters(tracker, ws)
+        assert tail > 0 and head == tail, "sliced, and every suspended path resumed"
         rq = np.frombuffer(ws[off:off + 1024].cpu().numpy().tobytes(), np.uint32)
-        assert rq[64] > 0 and rq[0] == rq[64], "sliced, and every suspended path resumed"
         # RQ_CLEARED: the largest ring so far (one entry per possible suspension + 4096 spare);
         # after the 50-sample launch its suspend blocks lie inside it: the dirty range [195, 196)
         cap = lambda k: k * 312 * ((tracker.settings.max_steps + 1) // 3 + 1) + 4096  # noqa: E731
@@ -377,11 +316,7 @@ def test_time_slicing_workspace_reused_across_launch_sizes(problem, samples100, 
             assert cap(50) <= rq[195] < rq[196] <= cap(100)
         else:
             assert rq[195] == rq[196] == 0
-        h = r.host()
-        sl = slice(0, n * 312)
-        assert (h["converge"] == ref["converge"][sl]).all() and (h["infinity"] == ref["infinity"][sl]).all()
-        assert np.array_equal(h["stats"]["steps"], ref["stats"]["steps"][sl])
-        assert np.array_equal(h["tracks"].view(np.uint32), ref["tracks"][sl].view(np.uint32))
+        assert_bit_identical(r.host(), ref, rows=slice(0, n * 312))
 
 
 def test_time_slicing_abandoned_tickets_are_pushed_again(problem, samples100, tracker):
@@ -407,41 +342,30 @@ def test_time_slicing_abandoned_tickets_are_pushed_again(problem, samples100, tr
     finally:
         tracker.L.hc_trifocal_set_ring_test(0)
     cb = np.frombuffer(ws[:64].cpu().numpy().tobytes(), np.uint32)
-    assert int(tracker.L.hc_trifocal_workspace_status(ctypes.c_void_p(ws.data_ptr()))) == 0, cb
+    tracker.workspace_status(ws)
     assert cb[12] > 0, "no ticket was abandoned: the test did not reach the re-push"
-    h = r.host()
-    assert (h["converge"] == ref["converge"]).all() and (h["infinity"] == ref["infinity"]).all()
-    assert np.array_equal(h["stats"]["steps"], ref["stats"]["steps"])
-    assert np.array_equal(h["tracks"].view(np.uint32), ref["tracks"].view(np.uint32))
+    assert_bit_identical(r.host(), ref)
 
 
 def test_tracker_abort_mode(problem, samples100, tracker):
     """Config 3 semantics (abort on): the found hypothesis is one of the passing
     hypotheses of the abort-off run; tracked paths equal the abort-off results;
     skipped paths keep the start solution with conv = 0."""
-    import sys
-    sys.path.insert(0, GOLDEN)
-    from make_golden import track_hash
-    g = np.load(os.path.join(GOLDEN, "gpuhc_N100_seed0.npz"))
-    passing = set(int(b) for b, s in zip(g["scored_ids"], g["scored"]) if s[0] == 1)
+    g = golden("gpuhc_N100_seed0")
+    passing = golden_passing(g)
     assert passing, "the golden run must contain a passing hypothesis"
     tgt, dif, _ = samples100
     r = tracker.track(tgt, dif, abort=True).host()
     assert r["found"]
-    found_ids = set(int(b) for b in np.nonzero(r["batch_index"] >= 0)[0])
-    assert found_ids and found_ids <= passing
-    assert all(int(r["batch_index"][b]) == b for b in found_ids)
+    found = set(found_ids(r).tolist())
+    assert found and found <= passing
     st = r["stats"]
-    tracked = st["steps"] > 0
-    assert (r["converge"][tracked] == g["conv"][tracked]).all()
-    assert (track_hash(r["tracks"])[tracked] == g["hash"][tracked]).all()
-    skipped = ~tracked
-    assert (r["converge"][skipped] == 0).all()
-    assert np.array_equal(r["tracks"][skipped][:, :30],
-                          np.tile(problem.start_sols[None, :, :30], (100, 1, 1, 1)).reshape(-1, 30, 2)[skipped])
+    trk = tracked(r)
+    assert_matches_golden(r, g, where=trk)
+    assert_untouched(r, problem.start_sols, ~trk, allow_empty=True)
     # inlier counts of scored paths equal the oracle's scoring
     sc = {int(b): s for b, s in zip(g["scored_ids"], g["scored"])}
-    for b in np.nonzero(tracked & (r["converge"] == 1))[0]:
+    for b in np.nonzero(trk & (r["converge"] == 1))[0]:
         ok, i21, i31 = sc[int(b)]
         if st["inliers21"][b] or st["inliers31"][b] or ok:
             assert (st["inliers21"][b], st["inliers31"][b]) == (i21, i31)
@@ -454,15 +378,11 @@ def test_tracker_abort_chunked(problem, samples100, tracker):
     10 launches, one workspace each.  Found ids (made global) are passing
     hypotheses, tracked paths equal the abort-off golden run, and once a chunk
     has found a pose every later chunk skips all of its paths."""
-    import sys
-
     import torch
 
     from trifocal_pose_estimation_using_improved_gpuhc_amd import sharding
-    sys.path.insert(0, GOLDEN)
-    from make_golden import track_hash
-    g = np.load(os.path.join(GOLDEN, "gpuhc_N100_seed0.npz"))
-    passing = set(int(b) for b, s in zip(g["scored_ids"], g["scored"]) if s[0] == 1)
+    g = golden("gpuhc_N100_seed0")
+    passing = golden_passing(g)
     tgt, dif, _ = samples100
     dev = tracker.device
     t = torch.from_numpy(tgt).to(dev)
@@ -475,15 +395,16 @@ def test_tracker_abort_chunked(problem, samples100, tracker):
     h = r.host()
     assert len(parts) == 10 and h["found"]
     found = set()
-    for off, n in parts:
+    for off, n in parts:   # a chunk launch writes ids within the chunk
         loc = h["batch_index"][off * 312:(off + n) * 312]
+        found_ids(dict(batch_index=loc))
         found |= set(int(b) for b in sharding.global_batch_ids(loc, off, 0))
     assert found and found <= passing
-    tracked = h["stats"]["steps"] > 0
-    assert (h["converge"][tracked] == g["conv"][tracked]).all()
-    assert (track_hash(h["tracks"])[tracked] == g["hash"][tracked]).all()
+    trk = tracked(h)
+    assert_matches_golden(h, g, where=trk)
+    assert_untouched(h, problem.start_sols, ~trk)
     first_chunk = min(b // 312 for b in found) // 10
-    assert not tracked[(first_chunk + 1) * 3120:].any()
+    assert not trk[(first_chunk + 1) * 3120:].any()
     stamps = [tracker.read_timestamps(w)[:2] for w in wss]
     hz = tracker.read_timestamps(wss[0])[2]
     assert sharding.first_found_seconds(stamps, hz) > 0
@@ -493,28 +414,17 @@ def test_tracker_abort_chunked(problem, samples100, tracker):
 def test_cli_config2_matches_golden(tmp_path):
     """bin/magmaHC-main (C++ GPU_HC_Solver over the C-ABI) on config 2: the
     solution statistics it writes equal the golden run's counts."""
-    import shutil
-    import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cli = os.path.join(root, "trifocal_pose_estimation_using_improved_gpuhc_amd", "bin", "magmaHC-main")
-    assert os.path.exists(cli), "CLI not built"
-    shutil.copytree(os.path.join(root, "data"), os.path.join(tmp_path, "data"))
-    out = subprocess.run([cli, "-p", "trifocal_2op1p_30x30", "-d", str(tmp_path)], capture_output=True, text=True,
-                         timeout=300)
-    assert out.returncode == 0, out.stdout + out.stderr
-    g = np.load(os.path.join(GOLDEN, "gpuhc_N100_seed0.npz"))
-    stats = open(os.path.join(tmp_path, "Output_Write_Files", "GPU_Sols_Statistics.txt")).read().split()
-    assert [int(v) for v in stats[:3]] == [int(v) for v in g["counts"]]
-    assert float(open(os.path.join(tmp_path, "Output_Write_Files", "GPU_Timings.txt")).read().split()[0]) > 0
+    _, read = run_cli(tmp_path)
+    stats = read("GPU_Sols_Statistics.txt").split()
+    assert [int(v) for v in stats[:3]] == [int(v) for v in golden("gpuhc_N100_seed0")["counts"]]
+    assert float(read("GPU_Timings.txt").split()[0]) > 0
     # device pose recovery (SURVEY §8 f1): the maximal-support pose matches GT_Poses*_000
-    pr = open(os.path.join(tmp_path, "Output_Write_Files", "GPU_Pose_Results.txt")).read().split()
-    gp = np.load(os.path.join(GOLDEN, "pose_N100_seed0.npz"))
+    pr = read("GPU_Pose_Results.txt").split()
+    gp = golden("pose_N100_seed0")
     assert int(pr[0]) == 1 and [int(pr[5]), int(pr[6])] == gp["path"].tolist() and int(pr[7]) == int(gp["num_candidates"])
     assert max(float(v) for v in pr[1:5]) < 1e-3
     # abort mode (config 3 semantics through the CLI)
-    out = subprocess.run([cli, "-p", "trifocal_2op1p_30x30", "-d", str(tmp_path), "-n", "1000", "--abort"],
-                         capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stdout + out.stderr
+    run_cli(tmp_path, "-n", "1000", "--abort")
 
 
 @pytest.mark.gpu
@@ -524,26 +434,17 @@ def test_cli_four_rounds(tmp_path):
     with srand(ti) (GPU_HC_Solver.cpp:252-306).  Every round writes its timing,
     solution statistics and pose line; every round's counts equal the oracle's
     (tests/golden/cli_rounds_counts.npz)."""
-    import shutil
-    import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cli = os.path.join(root, "trifocal_pose_estimation_using_improved_gpuhc_amd", "bin", "magmaHC-main")
-    shutil.copytree(os.path.join(root, "data"), os.path.join(tmp_path, "data"))
-    out = subprocess.run([cli, "-p", "trifocal_2op1p_30x30", "-d", str(tmp_path), "-t", "4"], capture_output=True,
-                         text=True, timeout=300)
-    assert out.returncode == 0, out.stdout + out.stderr
-    od = os.path.join(tmp_path, "Output_Write_Files")
-    ms = [float(v) for v in open(os.path.join(od, "GPU_Timings.txt")).read().split()]
+    stdout, read = run_cli(tmp_path, "-t", "4")
+    ms = [float(v) for v in read("GPU_Timings.txt").split()]
     assert len(ms) == 4 and min(ms) > 0
-    stats = [ln.split() for ln in open(os.path.join(od, "GPU_Sols_Statistics.txt")).read().splitlines()]
+    stats = [ln.split() for ln in read("GPU_Sols_Statistics.txt").splitlines()]
     assert len(stats) == 4 and all(int(r[0]) > 0 for r in stats)
-    g = np.load(os.path.join(GOLDEN, "gpuhc_N100_seed0.npz"))
-    assert [int(v) for v in stats[0]] == [int(v) for v in g["counts"]]
+    assert [int(v) for v in stats[0]] == [int(v) for v in golden("gpuhc_N100_seed0")["counts"]]
     # every round's counts equal the oracle's run of that round's dataset and draw
-    rounds = np.load(os.path.join(GOLDEN, "cli_rounds_counts.npz"))["counts"]
+    rounds = golden("cli_rounds_counts")["counts"]
     assert [[int(v) for v in r[:3]] for r in stats] == rounds.tolist()
-    assert len(open(os.path.join(od, "GPU_Pose_Results.txt")).read().splitlines()) == 4
-    assert "Running 4 rounds" in out.stdout
+    assert len(read("GPU_Pose_Results.txt").splitlines()) == 4
+    assert "Running 4 rounds" in stdout
 
 
 def test_ph_codeopt_matches_oracle_small(problem, oracle, samples100, tracker):
@@ -552,27 +453,16 @@ def test_ph_codeopt_matches_oracle_small(problem, oracle, samples100, tracker):
     tgt, dif, _ = samples100
     N = 2
     r = tracker.track(tgt[:N], dif[:N], truncate=False).host()
-    tr, conv, inf, st = oracle.gpuhc_track(problem.start_sols, problem.start_params, tgt[:N], dif[:N],
-                                           problem.unified_index, oracle.settings(truncate=False))
-    assert (r["converge"] == conv).all() and (r["infinity"] == inf).all()
-    assert (r["stats"]["steps"] == st["steps"]).all()
-    assert (r["stats"]["corrections"] == st["corrections"]).all()
-    assert same(r["tracks"][:, :30], tr[:, :30]).all()
+    assert_matches_oracle(r, oracle.gpuhc_track(problem.start_sols, problem.start_params, tgt[:N], dif[:N],
+                                                problem.unified_index, oracle.settings(truncate=False)))
 
 
 def test_ph_codeopt_matches_golden_N100(problem, samples100, tracker):
     """Config 2 without path truncation: every flag / count / track hash equals the
     oracle's committed run (tests/golden/gpuhc_phcodeopt_N100_seed0.npz)."""
-    import sys
-    sys.path.insert(0, GOLDEN)
-    from make_golden import track_hash
-    g = np.load(os.path.join(GOLDEN, "gpuhc_phcodeopt_N100_seed0.npz"))
     tgt, dif, _ = samples100
     r = tracker.track(tgt, dif, truncate=False).host()
-    assert (r["converge"] == g["conv"]).all() and (r["infinity"] == g["inf"]).all()
-    assert (r["stats"]["steps"] == g["steps"]).all()
-    assert (r["stats"]["corrections"] == g["corrections"]).all()
-    assert (track_hash(r["tracks"]) == g["hash"]).all()
+    assert_matches_golden(r, golden("gpuhc_phcodeopt_N100_seed0"))
 
 
 def test_ph_matches_oracle_small(problem, oracle, samples100, tracker):
@@ -581,27 +471,17 @@ def test_ph_matches_oracle_small(problem, oracle, samples100, tracker):
     tgt, dif, _ = samples100
     N = 2
     r = tracker.track(tgt[:N], dif[:N], truncate=False, explicit_rk=True).host()
-    tr, conv, inf, st = oracle.gpuhc_track(problem.start_sols, problem.start_params, tgt[:N], dif[:N],
-                                           problem.unified_index, oracle.settings(truncate=False, explicit_rk=True))
-    assert (r["converge"] == conv).all() and (r["infinity"] == inf).all()
-    assert (r["stats"]["steps"] == st["steps"]).all()
-    assert (r["stats"]["corrections"] == st["corrections"]).all()
-    assert same(r["tracks"][:, :30], tr[:, :30]).all()
+    assert_matches_oracle(r, oracle.gpuhc_track(problem.start_sols, problem.start_params, tgt[:N], dif[:N],
+                                                problem.unified_index,
+                                                oracle.settings(truncate=False, explicit_rk=True)))
 
 
 def test_ph_matches_golden_N100(problem, samples100, tracker):
     """Config 2 through the archived ..._PH semantics: every flag / count / track
     hash equals the oracle's committed run (tests/golden/gpuhc_ph_N100_seed0.npz)."""
-    import sys
-    sys.path.insert(0, GOLDEN)
-    from make_golden import track_hash
-    g = np.load(os.path.join(GOLDEN, "gpuhc_ph_N100_seed0.npz"))
     tgt, dif, _ = samples100
     r = tracker.track(tgt, dif, truncate=False, explicit_rk=True).host()
-    assert (r["converge"] == g["conv"]).all() and (r["infinity"] == g["inf"]).all()
-    assert (r["stats"]["steps"] == g["steps"]).all()
-    assert (r["stats"]["corrections"] == g["corrections"]).all()
-    assert (track_hash(r["tracks"]) == g["hash"]).all()
+    assert_matches_golden(r, golden("gpuhc_ph_N100_seed0"))
 
 
 def _row_permuted(problem, perm):
@@ -643,7 +523,6 @@ def test_eval_rejects_tables_without_helpers(problem):
     """Two long dH/dt rows paired as lane ^ 16 partners (neither can help the
     other): the table builder rejects the table (HC_ERROR_TABLE) and the
     kernels leave their outputs untouched."""
-    import ctypes as C
     import torch
     from trifocal_pose_estimation_using_improved_gpuhc_amd import _abi
     perm = np.arange(30)
@@ -660,9 +539,9 @@ def test_eval_rejects_tables_without_helpers(problem):
     H = torch.full((n, 30, 2), 7.0, dtype=torch.float32, device=dev)
     wsb = int(L.hc_trifocal_workspace_size())
     ws = torch.zeros(wsb, dtype=torch.uint8, device=dev)
-    p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
-    _abi.check(L.hc_trifocal_eval_batched(n, p(Ut), p(X), p(P), p(P), p(HX), p(HT), p(H), p(ws), wsb,
-                                          C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "eval")
+    p = _abi.ptr
+    _abi.call("hc_trifocal_eval_batched", n, p(Ut), p(X), p(P), p(P), p(HX), p(HT), p(H), p(ws), wsb,
+              p(torch.cuda.current_stream(dev)))
     torch.cuda.synchronize(dev)
     assert int(L.hc_trifocal_workspace_status(p(ws))) == 5   # HC_ERROR_TABLE
     assert (HX == 7.0).all() and (HT == 7.0).all() and (H == 7.0).all()
@@ -702,24 +581,18 @@ def test_tracker_row_permuted_structure_matches_oracle(problem, oracle, samples1
         tr = DeviceTracker(dataclasses.replace(problem, dHdx_index=dx, dHdt_index=dt), torch.device("cuda:0"))
         tr.set_ransac_data(ransac0)
         for truncate in (True, False):
-            with small_launch(tr.L, mode):
+            with launch_mode(tr.L, mode):
                 r = tr.track(tgt[:N], dif[:N], truncate=truncate).host()
             tr.workspace_status()
-            o_tr, conv, inf, st = oracle.gpuhc_track(problem.start_sols, problem.start_params, tgt[:N], dif[:N], U,
-                                                     oracle.settings(truncate=truncate))
-            assert (r["converge"] == conv).all() and (r["infinity"] == inf).all(), (swap, truncate)
-            assert (r["stats"]["steps"] == st["steps"]).all() and (r["stats"]["corrections"] == st["corrections"]).all()
-            bad = ~same(r["tracks"][:, :30], o_tr[:, :30]).all(axis=(1, 2))
-            assert not bad.any(), f"{swap} truncate={truncate}: {bad.sum()} tracks differ"
+            ref = oracle.gpuhc_track(problem.start_sols, problem.start_params, tgt[:N], dif[:N], U,
+                                     oracle.settings(truncate=truncate))
+            assert_matches_oracle(r, ref)
             if truncate:
-                ref_conv, ref_tracks = conv, o_tr
+                ref_abort_off = ref
         # abort mode: every path it tracked equals the abort-off oracle run
         a = tr.track(tgt[:N], dif[:N], abort=True).host()
         tr.workspace_status()
-        tracked = a["stats"]["steps"] > 0
-        assert tracked.sum() > 0
-        assert (a["converge"][tracked] == ref_conv[tracked]).all()
-        assert same(a["tracks"][tracked][:, :30], ref_tracks[tracked][:, :30]).all()
+        assert_matches_oracle(a, ref_abort_off, where=tracked(a))
     assert not _outside_lu_structure(problem.dHdx_index)
 
 
@@ -729,18 +602,20 @@ def test_ring_check_reports_an_undrained_ring(tracker):
     path that was never resumed: HC_ERROR_DEVICE with ring_fail = (~0, avail,
     tail, head); a drained ring stays silent."""
     import torch
+
+    from trifocal_pose_estimation_using_improved_gpuhc_amd._abi import ptr
     L = tracker.L
     wsb = int(L.hc_trifocal_workspace_size_for(1))
-    hs = ctypes.c_void_p(torch.cuda.current_stream(tracker.device).cuda_stream)
+    hs = ptr(torch.cuda.current_stream(tracker.device))
     for head, tail, avail, bad in ((7, 7, 0, False), (9, 7, 0, True), (7, 7, 1, True)):
         ws = torch.zeros(wsb, dtype=torch.uint8, device=tracker.device)
-        assert int(L.hc_trifocal_ring_check_test(ctypes.c_void_p(ws.data_ptr()), wsb, head, tail, avail, hs)) == 0
+        assert int(L.hc_trifocal_ring_check_test(ptr(ws), wsb, head, tail, avail, hs)) == 0
         torch.cuda.synchronize(tracker.device)
-        st = int(L.hc_trifocal_workspace_status(ctypes.c_void_p(ws.data_ptr())))
+        st = int(L.hc_trifocal_workspace_status(ptr(ws)))
         cb = np.frombuffer(ws[:64].cpu().numpy().tobytes(), np.uint32)
         if bad:
             assert st == 4 and list(cb[8:12]) == [0xFFFFFFFF, avail, tail, head], (st, cb[8:12])
         else:
             assert st == 0 and (cb[8:12] == 0).all()
     small = int(L.hc_trifocal_workspace_size())
-    assert int(L.hc_trifocal_ring_check_test(ctypes.c_void_p(ws.data_ptr()), small, 1, 0, 0, hs)) == 2
+    assert int(L.hc_trifocal_ring_check_test(ptr(ws), small, 1, 0, 0, hs)) == 2

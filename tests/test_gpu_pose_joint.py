@@ -13,16 +13,14 @@ ids of a 624-path buffer whose other paths are not converged; the scene is the
 first E edgels of dataset 000 with sigma = 1 px noise (seed 20250215), so that
 inlier-ness differs per edgel and per view.
 """
-import os
-
 import numpy as np
 import pytest
 
+from checks import golden, noisy_data, run_cli
 from joint_reference import joint_reference, pack_mask
 
 pytestmark = pytest.mark.gpu
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 NPATHS = 624
 SIZES = [1, 63, 64, 65, 200]
 POSE_KEYS = ("R21", "t21", "R31", "t31")
@@ -35,18 +33,15 @@ def _empty_tracks(n):
 
 
 @pytest.fixture(scope="module")
-def noisy0(ransac0):
-    from trifocal_pose_estimation_using_improved_gpuhc_amd import synthcurves
-    d = synthcurves.noisy(ransac0, 1.0, 20250215)
-    d.locations.setflags(write=False)
-    return d
+def noisy0():
+    return noisy_data()
 
 
 @pytest.fixture(scope="module")
 def common(oracle, noisy0):
     """Tracks, ids, and the oracle's per-edgel masks over the first 200 edgels
     (computed once; the reference of a smaller E is their first E columns)."""
-    g = np.load(os.path.join(GOLDEN, "pose_N100_seed0.npz"))
+    g = golden("pose_N100_seed0")
     cand = np.ascontiguousarray(g["cand_tracks"])
     rng = np.random.default_rng(11)
     ids = np.sort(rng.choice(NPATHS, len(cand), replace=False))
@@ -203,9 +198,9 @@ def test_joint_grouped(problem, tracker, common, noisy0, ransac0):
     selection is the single-triplet joint call over that triplet's own rows."""
     import torch
 
-    from trifocal_pose_estimation_using_improved_gpuhc_amd import pose, synthcurves
+    from trifocal_pose_estimation_using_improved_gpuhc_amd import pose
     from trifocal_pose_estimation_using_improved_gpuhc_amd.multi import TripletBatch
-    other = synthcurves.noisy(ransac0, 1.0, 20250216)
+    other = noisy_data(20250216)
     batch = TripletBatch(problem, [noisy0, other, ransac0], seeds=0, samples_per_triplet=[2, 2, 1], interleave=True,
                          edgel_counts=[63, 200, 100])
     assert batch.sample_group.tolist() == [0, 1, 2, 0, 1]
@@ -278,7 +273,7 @@ def test_joint_noisy_golden(tracker, noisy0):
     import torch
 
     from trifocal_pose_estimation_using_improved_gpuhc_amd import pose
-    g = np.load(os.path.join(GOLDEN, "pose_joint_noisy1px_N100.npz"))
+    g = golden("pose_joint_noisy1px_N100")
     ids = g["cand_ids"]
     assert len(ids) == 31
     tr, conv = _empty_tracks(31200)
@@ -302,21 +297,12 @@ def test_cli_joint_option(tmp_path, samples100, tracker):
     """`magmaHC-main --joint` (setting Pose_Selection_Joint) on config 2: the
     solver selects the path the joint call selects on the same launch, for both
     views, prints the joint count and still recovers the GT pose."""
-    import shutil
-    import subprocess
-
     from trifocal_pose_estimation_using_improved_gpuhc_amd import pose
     tgt, dif, _ = samples100
     r = tracker.track(tgt, dif)
     _, sel = pose.pose_support_joint(r.tracks, r.converge, tracker.edgels, tracker.K)
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cli = os.path.join(root, "trifocal_pose_estimation_using_improved_gpuhc_amd", "bin", "magmaHC-main")
-    assert os.path.exists(cli), "CLI not built"
-    shutil.copytree(os.path.join(root, "data"), os.path.join(tmp_path, "data"))
-    out = subprocess.run([cli, "-p", "trifocal_2op1p_30x30", "-d", str(tmp_path), "--joint"], capture_output=True,
-                         text=True, timeout=300)
-    assert out.returncode == 0, out.stdout + out.stderr
-    assert f" - joint selection: path {sel['path']}, {sel['inliers']} edgels within 2 px in both views" in out.stdout
-    pr = open(os.path.join(tmp_path, "Output_Write_Files", "GPU_Pose_Results.txt")).read().split()
+    stdout, read = run_cli(tmp_path, "--joint")
+    assert f" - joint selection: path {sel['path']}, {sel['inliers']} edgels within 2 px in both views" in stdout
+    pr = read("GPU_Pose_Results.txt").split()
     assert int(pr[0]) == 1 and int(pr[5]) == int(pr[6]) == sel["path"] and int(pr[7]) == sel["num_candidates"]
     assert max(float(v) for v in pr[1:5]) < 1e-3

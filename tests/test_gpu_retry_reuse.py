@@ -10,45 +10,16 @@ step and 6 226 rejected steps are retried (6 311 on the held-out dataset 050).
 100 samples is the smallest committed shape with more paths than path slots, so
 suspensions fall between a rejection and its retry.
 """
-import contextlib
-import os
-import sys
-
-import numpy as np
 import pytest
 
-from conftest import same
+from checks import (KERNEL_BY_SIZE, SMALL_NEVER, assert_matches_golden, assert_matches_oracle, assert_same_run, golden,
+                    launch_mode, scaled_samples)
 
 pytestmark = pytest.mark.gpu
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-KERNEL_BY_SIZE, SMALL_NEVER = 0, -1   # hc_trifocal_set_small_launch
 
-
-@contextlib.contextmanager
-def launch_mode(L, small, reuse):
-    """Kernel choice and the retry-reuse switch for the launches inside; the defaults after."""
-    L.hc_trifocal_set_small_launch(small)
-    L.hc_trifocal_set_retry_reuse(1 if reuse else 0)
-    try:
-        yield
-    finally:
-        L.hc_trifocal_set_small_launch(KERNEL_BY_SIZE)
-        L.hc_trifocal_set_retry_reuse(1)
-
-
-def assert_equal_runs(r, tracks, conv, inf, steps, corrections):
-    assert (r["converge"] == conv).all()
-    assert (r["infinity"] == inf).all()
-    assert (r["stats"]["steps"] == steps).all()
-    assert (r["stats"]["corrections"] == corrections).all()
-    bad = ~same(r["tracks"][:, :30], tracks[:, :30]).all(axis=(1, 2))
-    assert not bad.any(), f"{bad.sum()} tracks differ, first {np.nonzero(bad)[0][:5]}"
-
-
-def assert_matches_oracle(r, ref):
-    tr, conv, inf, st = ref
-    assert_equal_runs(r, tr, conv, inf, st["steps"], st["corrections"])
+def assert_equal_runs(r, h):
+    assert_same_run(r, h["tracks"], h["converge"], h["infinity"], h["stats"]["steps"], h["stats"]["corrections"])
 
 
 @pytest.fixture(scope="module")
@@ -70,8 +41,7 @@ def scaled(problem, oracle, samples100):
     """The input of test_gpu_parity's dense re-solve test: sample 0 and its target
     parameters x 2^40 and x 2^70, whose systems go to the dense re-solve."""
     tgt, dif, _ = samples100
-    T = np.stack([tgt[0]] + [(tgt[0] * np.float32(sc)).astype(np.float32) for sc in (2.0 ** 40, 2.0 ** 70)])
-    D = (T - problem.start_params[None]).astype(np.float32)
+    T, D = scaled_samples(problem, tgt[0], (0, 40, 70))
     ref = oracle.gpuhc_track(problem.start_sols, problem.start_params, T, D, problem.unified_index)
     assert ref[2][312:].sum() > 600 and ref[1][:312].sum() > 0   # the scaled samples diverge, sample 0 converges
     return T, D, ref
@@ -95,8 +65,7 @@ def test_switch_off_equals_on(samples100, tracker, throughput_on):
     tgt, dif, _ = samples100
     with launch_mode(tracker.L, SMALL_NEVER, False):
         r = tracker.track(tgt[:2], dif[:2]).host()
-    h = throughput_on
-    assert_equal_runs(r, h["tracks"], h["converge"], h["infinity"], h["stats"]["steps"], h["stats"]["corrections"])
+    assert_equal_runs(r, throughput_on)
 
 
 def test_unsliced_launch_equals_sliced(samples100, tracker, throughput_on):
@@ -105,8 +74,7 @@ def test_unsliced_launch_equals_sliced(samples100, tracker, throughput_on):
     tgt, dif, _ = samples100
     with launch_mode(tracker.L, SMALL_NEVER, True):
         r = tracker.track(tgt[:2], dif[:2], time_slicing=False).host()
-    h = throughput_on
-    assert_equal_runs(r, h["tracks"], h["converge"], h["infinity"], h["stats"]["steps"], h["stats"]["corrections"])
+    assert_equal_runs(r, throughput_on)
 
 
 def test_held_out_dataset_matches_oracle(problem, oracle, tracker):
@@ -122,18 +90,10 @@ def test_held_out_dataset_matches_oracle(problem, oracle, tracker):
 @pytest.mark.parametrize("reuse", [True, False], ids=["on", "off"])
 def test_config2_matches_golden(samples100, tracker, reuse):
     """4a, 4b: config 2 (100 samples, more paths than slots) against the committed golden run."""
-    sys.path.insert(0, GOLDEN)
-    from make_golden import track_hash
-    g = np.load(os.path.join(GOLDEN, "gpuhc_N100_seed0.npz"))
     tgt, dif, _ = samples100
     with launch_mode(tracker.L, KERNEL_BY_SIZE, reuse):
         r = tracker.track(tgt, dif).host()
-    assert (r["converge"] == g["conv"]).all()
-    assert (r["infinity"] == g["inf"]).all()
-    assert (r["stats"]["steps"] == g["steps"]).all()
-    assert (r["stats"]["corrections"] == g["corrections"]).all()
-    h = track_hash(r["tracks"])
-    assert (h == g["hash"]).all(), f"{(h != g['hash']).sum()} track hashes differ"
+    assert_matches_golden(r, golden("gpuhc_N100_seed0"))
 
 
 @pytest.mark.parametrize("reuse", [True, False], ids=["on", "off"])

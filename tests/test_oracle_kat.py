@@ -255,9 +255,7 @@ def test_oracle_reproduces_golden_tracks(problem, oracle, samples100):
 
 
 def test_oracle_cpuhc_reproduces_golden(problem, oracle, samples100):
-    import sys
-    sys.path.insert(0, GOLDEN)
-    from make_golden import track_hash
+    from checks import track_hash
     g = np.load(os.path.join(GOLDEN, "cpuhc_seed0.npz"))
     tgt, dif, _ = samples100
     tr, conv, inf, st, _ = oracle.cpuhc_track(problem.start_sols, problem.start_params, tgt[:2], dif[:2],

@@ -14,8 +14,13 @@ import ctypes as C
 import os
 import subprocess
 
+from types import SimpleNamespace
+
 import numpy as np
 import pytest
+
+from checks import assert_same_run, assert_untouched, found_ids
+from trifocal_pose_estimation_using_improved_gpuhc_amd._abi import ptr as p
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHIM = os.path.join(ROOT, "integration", "build", "libhc_shim_test.so")
@@ -80,6 +85,42 @@ def _lib():
     return L
 
 
+def _reference_layout(problem, tracker, tgt, dif):
+    """The reference's device layout (GPU_HC_Solver.cpp:137-184,335-362): start
+    sols and tracks as 31-complex columns, addressed through per-track pointer
+    arrays (d_startSols_array / d_Track_array), the parameters of tgt's
+    samples and the index tables, unified and separate.  outputs(n): tracks at
+    the start solutions, their pointer array and cleared flags for a launch of
+    n samples; common(o): the launchers' shared argument run."""
+    import torch
+    dev, s = tracker.device, tracker.settings
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+    ss = up(problem.start_sols)
+    lay = SimpleNamespace(ss=ss, sp=up(problem.start_params), tp=up(tgt), dp=up(dif), U=up(problem.unified_index),
+                          hx=up(problem.dHdx_index.reshape(-1)), ht=up(problem.dHdt_index.reshape(-1)),
+                          ssa=torch.tensor([ss.data_ptr() + k * 31 * 8 for k in range(312)], dtype=torch.int64,
+                                           device=dev))
+
+    def outputs(n):
+        o = SimpleNamespace(tracks=ss.unsqueeze(0).expand(n, -1, -1, -1).reshape(n * 312, 31, 2).contiguous(),
+                            conv=torch.zeros(312 * n, dtype=torch.bool, device=dev),
+                            inf=torch.zeros(312 * n, dtype=torch.bool, device=dev))
+        o.tra = torch.tensor([o.tracks.data_ptr() + b * 31 * 8 for b in range(312 * n)], dtype=torch.int64, device=dev)
+        o.host = lambda: dict(tracks=o.tracks.cpu().numpy(), converge=o.conv.cpu().numpy().astype(np.uint8),
+                              infinity=o.inf.cpu().numpy().astype(np.uint8))
+        return o
+
+    lay.outputs = outputs
+    lay.common = lambda o: [C.c_int(s.max_steps), C.c_int(s.max_corrections), C.c_int(s.delta_t_inc_steps),
+                            p(lay.ssa), p(o.tra), p(lay.sp), p(lay.tp), p(lay.dp)]
+    return lay
+
+
+def _assert_same_flags_and_tracks(got, ref, where=None):
+    """The launchers report no step or correction counts."""
+    assert_same_run(got, ref["tracks"], ref["converge"], ref["infinity"], None, None, where)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("abort,truncate,volta,N", [
     (a, t, v, 3) for (a, t) in [(False, True), (True, True), (False, False)] for v in (False, True)] + [
@@ -92,59 +133,41 @@ def test_shim_launchers_match_abi(problem, samples100, tracker, ransac0, abort, 
     dev = tracker.device
     tgt, dif, _ = samples100
     ref = tracker.track(tgt[:N], dif[:N], abort=abort, truncate=truncate).host()
-    # the reference's device layout (GPU_HC_Solver.cpp:137-184,335-362): start sols and
-    # tracks as 31-complex columns, addressed through per-track pointer arrays
-    ss = torch.from_numpy(problem.start_sols).to(dev)
-    tracks = ss.unsqueeze(0).expand(N, -1, -1, -1).reshape(N * 312, 31, 2).contiguous()
-    ssa = torch.tensor([ss.data_ptr() + k * 31 * 8 for k in range(312)], dtype=torch.int64, device=dev)
-    tra = torch.tensor([tracks.data_ptr() + b * 31 * 8 for b in range(312 * N)], dtype=torch.int64, device=dev)
-    sp = torch.from_numpy(problem.start_params).to(dev)
-    tp = torch.from_numpy(np.ascontiguousarray(tgt[:N])).to(dev)
-    dp = torch.from_numpy(np.ascontiguousarray(dif[:N])).to(dev)
-    U = torch.from_numpy(problem.unified_index).to(dev)
-    hx = torch.from_numpy(np.ascontiguousarray(problem.dHdx_index.reshape(-1))).to(dev)
-    ht = torch.from_numpy(np.ascontiguousarray(problem.dHdt_index.reshape(-1))).to(dev)
-    conv = torch.zeros(312 * N, dtype=torch.bool, device=dev)
-    inf = torch.zeros(312 * N, dtype=torch.bool, device=dev)
+    lay = _reference_layout(problem, tracker, tgt[:N], dif[:N])
+    o = lay.outputs(N)
     found = torch.zeros(1, dtype=torch.bool, device=dev)
     bidx = torch.full((312 * N,), -1, dtype=torch.int32, device=dev)
-    stream = torch.cuda.current_stream(dev)
-    q = L.shim_queue_create(C.c_void_p(stream.cuda_stream))
-    p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
-    s = tracker.settings
-    common = [C.c_int(s.max_steps), C.c_int(s.max_corrections), C.c_int(s.delta_t_inc_steps), p(ssa), p(tra), p(sp),
-              p(tp), p(dp)]
-    tables = [p(hx), p(ht)] if volta else [p(U)]
+    q = L.shim_queue_create(p(torch.cuda.current_stream(dev)))
+    tables = [p(lay.hx), p(lay.ht)] if volta else [p(lay.U)]
     if abort:
         E = tracker.edgels
         fn = L.shim_trunransac_volta if volta else L.shim_trunransac
-        rv = fn(C.c_void_p(q), C.c_int(N), C.c_int(E.shape[0]), *common, *tables, p(E), p(tracker.K), p(conv), p(inf),
-                p(found), p(bidx))
+        rv = fn(C.c_void_p(q), C.c_int(N), C.c_int(E.shape[0]), *lay.common(o), *tables, p(E), p(tracker.K), p(o.conv),
+                p(o.inf), p(found), p(bidx))
     elif truncate:
         fn = L.shim_trunpaths_volta if volta else L.shim_trunpaths
-        rv = fn(C.c_void_p(q), C.c_int(N), *common, *tables, p(conv), p(inf))
+        rv = fn(C.c_void_p(q), C.c_int(N), *lay.common(o), *tables, p(o.conv), p(o.inf))
     else:
         fn = L.shim_ph_codeopt_volta if volta else L.shim_ph_codeopt
-        rv = fn(C.c_void_p(q), C.c_int(N), *common, *tables, p(conv), p(inf))
+        rv = fn(C.c_void_p(q), C.c_int(N), *lay.common(o), *tables, p(o.conv), p(o.inf))
     torch.cuda.synchronize(dev)
     L.shim_queue_destroy(C.c_void_p(q))
     assert rv == 0.0
-    got_conv = conv.cpu().numpy().astype(np.uint8)
-    got_tr = tracks.cpu().numpy()
+    got = o.host()
     if not abort:
-        assert (got_conv == ref["converge"]).all() and (inf.cpu().numpy().astype(np.uint8) == ref["infinity"]).all()
-        assert np.array_equal(got_tr[:, :30], ref["tracks"][:, :30], equal_nan=True)
+        _assert_same_flags_and_tracks(got, ref)
     else:
         # which paths get skipped depends on scheduling; every path the shim tracked
         # equals the abort-off result and found ids are the direct ABI's passing set
         full = tracker.track(tgt[:N], dif[:N]).host()
         assert bool(found.item())
-        ids = np.nonzero(bidx.cpu().numpy() >= 0)[0]
+        ids = found_ids(dict(batch_index=bidx.cpu().numpy()))
         assert len(ids) and (full["converge"][ids] == 1).all()
-        moved = ~np.all(got_tr[:, :30] == np.tile(problem.start_sols[None, :, :30], (N, 1, 1, 1)).reshape(-1, 30, 2),
-                        axis=(1, 2))
-        assert np.array_equal(got_tr[moved, :30], full["tracks"][moved, :30], equal_nan=True)
-        assert (got_conv[moved] == full["converge"][moved]).all()
+        # the launchers report no step counts: a path that left its start solution was tracked
+        start = np.tile(problem.start_sols[None, :, :30], (N, 1, 1, 1)).reshape(-1, 30, 2)
+        moved = ~np.all(got["tracks"][:, :30] == start, axis=(1, 2))
+        _assert_same_flags_and_tracks(got, full, where=moved)
+        assert_untouched(got, problem.start_sols, ~moved, allow_empty=True)
 
 
 @pytest.mark.gpu
@@ -157,28 +180,14 @@ def test_shim_ph_launcher_matches_abi(problem, samples100, tracker):
     N = 2
     tgt, dif, _ = samples100
     ref = tracker.track(tgt[:N], dif[:N], truncate=False, explicit_rk=True).host()
-    ss = torch.from_numpy(problem.start_sols).to(dev)
-    tracks = ss.unsqueeze(0).expand(N, -1, -1, -1).reshape(N * 312, 31, 2).contiguous()
-    ssa = torch.tensor([ss.data_ptr() + k * 31 * 8 for k in range(312)], dtype=torch.int64, device=dev)
-    tra = torch.tensor([tracks.data_ptr() + b * 31 * 8 for b in range(312 * N)], dtype=torch.int64, device=dev)
-    sp = torch.from_numpy(problem.start_params).to(dev)
-    tp = torch.from_numpy(np.ascontiguousarray(tgt[:N])).to(dev)
-    dp = torch.from_numpy(np.ascontiguousarray(dif[:N])).to(dev)
-    hx = torch.from_numpy(np.ascontiguousarray(problem.dHdx_index.reshape(-1))).to(dev)
-    ht = torch.from_numpy(np.ascontiguousarray(problem.dHdt_index.reshape(-1))).to(dev)
-    conv = torch.zeros(312 * N, dtype=torch.bool, device=dev)
-    inf = torch.zeros(312 * N, dtype=torch.bool, device=dev)
-    q = L.shim_queue_create(C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
-    s = tracker.settings
-    rv = L.shim_ph(C.c_void_p(q), C.c_int(N), C.c_int(s.max_steps), C.c_int(s.max_corrections),
-                   C.c_int(s.delta_t_inc_steps), p(ssa), p(tra), p(sp), p(tp), p(dp), p(hx), p(ht), p(conv), p(inf))
+    lay = _reference_layout(problem, tracker, tgt[:N], dif[:N])
+    o = lay.outputs(N)
+    q = L.shim_queue_create(p(torch.cuda.current_stream(dev)))
+    rv = L.shim_ph(C.c_void_p(q), C.c_int(N), *lay.common(o), p(lay.hx), p(lay.ht), p(o.conv), p(o.inf))
     torch.cuda.synchronize(dev)
     L.shim_queue_destroy(C.c_void_p(q))
     assert rv == 0.0
-    assert (conv.cpu().numpy().astype(np.uint8) == ref["converge"]).all()
-    assert (inf.cpu().numpy().astype(np.uint8) == ref["infinity"]).all()
-    assert np.array_equal(tracks.cpu().numpy()[:, :30], ref["tracks"][:, :30], equal_nan=True)
+    _assert_same_flags_and_tracks(o.host(), ref)
 
 
 @pytest.mark.gpu
@@ -196,38 +205,24 @@ def test_shim_reserved_stream_never_allocates(problem, samples100, tracker):
     tgt, dif, _ = samples100
     ref = tracker.track(tgt[:N], dif[:N]).host()
     stream = torch.cuda.Stream(dev)
-    q = L.shim_queue_create(C.c_void_p(stream.cuda_stream))
+    q = L.shim_queue_create(p(stream))
     s = tracker.settings
     assert L.hc_trifocal_shim_reserve(C.c_void_p(q), N, s.max_steps) == 0
     wsb, grows = C.c_size_t(0), C.c_int(-1)
     assert L.hc_trifocal_shim_info(C.c_void_p(q), C.byref(wsb), C.byref(grows)) == 0
     reserved = wsb.value
     assert reserved == int(tracker.L.hc_trifocal_workspace_size_for_steps(N, s.max_steps)) and grows.value == 0
-    ss = torch.from_numpy(problem.start_sols).to(dev)
-    ssa = torch.tensor([ss.data_ptr() + k * 31 * 8 for k in range(312)], dtype=torch.int64, device=dev)
-    sp = torch.from_numpy(problem.start_params).to(dev)
-    tp = torch.from_numpy(np.ascontiguousarray(tgt[:N])).to(dev)
-    dp = torch.from_numpy(np.ascontiguousarray(dif[:N])).to(dev)
-    U = torch.from_numpy(problem.unified_index).to(dev)
-    hx = torch.from_numpy(np.ascontiguousarray(problem.dHdx_index.reshape(-1))).to(dev)
-    ht = torch.from_numpy(np.ascontiguousarray(problem.dHdt_index.reshape(-1))).to(dev)
-    p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    lay = _reference_layout(problem, tracker, tgt[:N], dif[:N])
     torch.cuda.synchronize(dev)
     for volta, n in ((False, N), (True, N), (False, 7)):
-        tracks = ss.unsqueeze(0).expand(n, -1, -1, -1).reshape(n * 312, 31, 2).contiguous()
-        tra = torch.tensor([tracks.data_ptr() + b * 31 * 8 for b in range(312 * n)], dtype=torch.int64, device=dev)
-        conv = torch.zeros(312 * n, dtype=torch.bool, device=dev)
-        inf = torch.zeros(312 * n, dtype=torch.bool, device=dev)
+        o = lay.outputs(n)
         torch.cuda.synchronize(dev)
-        common = [C.c_int(s.max_steps), C.c_int(s.max_corrections), C.c_int(s.delta_t_inc_steps), p(ssa), p(tra),
-                  p(sp), p(tp), p(dp)]
         if volta:
-            L.shim_trunpaths_volta(C.c_void_p(q), C.c_int(n), *common, p(hx), p(ht), p(conv), p(inf))
+            L.shim_trunpaths_volta(C.c_void_p(q), C.c_int(n), *lay.common(o), p(lay.hx), p(lay.ht), p(o.conv), p(o.inf))
         else:
-            L.shim_trunpaths(C.c_void_p(q), C.c_int(n), *common, p(U), p(conv), p(inf))
+            L.shim_trunpaths(C.c_void_p(q), C.c_int(n), *lay.common(o), p(lay.U), p(o.conv), p(o.inf))
         assert L.hc_trifocal_shim_status(C.c_void_p(q)) == 0
-        assert (conv.cpu().numpy().astype(np.uint8) == ref["converge"][:312 * n]).all()
-        assert np.array_equal(tracks.cpu().numpy()[:, :30], ref["tracks"][:312 * n, :30], equal_nan=True)
+        _assert_same_flags_and_tracks(o.host(), {k: ref[k][:312 * n] for k in ("tracks", "converge", "infinity")})
     assert L.hc_trifocal_shim_info(C.c_void_p(q), C.byref(wsb), C.byref(grows)) == 0
     assert grows.value == 0 and wsb.value == reserved
     L.shim_queue_destroy(C.c_void_p(q))
