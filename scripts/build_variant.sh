@@ -8,6 +8,11 @@
 # HC_PRIO_REM) live in commit 02bc69d.  The switches settled in rounds 5 to 7 and
 # v10.8 (HC_ABORT_GTAB with the LDS staging of the term tables, HC_LU_LATB with the
 # paired always-live groups, HC_RETRY_HOLD, HC_SMALL_LAUNCH) live in commit 12ddb46.
+# v10.9's parts were measured apart with -DHC_ABS_STEPS (bits: 1 the gather addresses, 2 the dH/dx term
+# operands, 4 the dH/dt | H operands from the slot-absolute tables, 8 the finiteness check on the dH/dx
+# entries) and -DHC_EV_TAHEAD (profiles/r13a_ab_abs_tables.jsonl, r13c_ab_leave_one_out.jsonl).  The
+# sources with these two switches are in no commit; DESIGN.md section 3.6 ("How the variants were
+# built") describes them site by site.
 set -e
 cd "$(dirname "$0")/../trifocal_pose_estimation_using_improved_gpuhc_amd/csrc"
 N=$1; shift

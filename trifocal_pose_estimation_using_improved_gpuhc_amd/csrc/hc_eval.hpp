@@ -404,4 +404,162 @@ __device__ __forceinline__ cf eval_rhs(const uint2 *s_ht, const SlotLDS &S, int 
     return cmk(acc.x, acc.y);
 }
 
+// Slot-absolute address tables (v10.9), for the throughput tracking kernel.
+// An operand address above is slot base + a table field: one SDWA add per
+// operand read, ~175 VALU per wave-stage, on values that depend only on the
+// index table and on which of the workgroup's eight path slots the lane
+// serves.  k_prep_tables does those adds once per table: a word here is the
+// operand's byte offset from the workgroup's first slot, slot * sizeof(SlotLDS)
+// + offset within the slot (slot = 2 * wave + half), so an operand read is a
+// DS read at base + word with the base (a link-time constant) in the
+// instruction's offset field and no VALU.  Indexed [wave][term][lane of the
+// wave]: a term's words are one 16-B (8-B) load per lane, 1 KB contiguous per
+// wave.  198 KB, read from L2 (they do not fit the L1 as the packed tables
+// do); the latency-critical kernels keep the packed tables.
+//  hx[w][k][l]   lane l's k-th dH/dx term: .x tp, .y x[u], .z x[v]; .w where the entry slot that ends at
+//                term k is stored (other terms: unused)
+//  ht[w][j][l]   full term j < HT_FULL of the lane's row: .x x[u], .y x[v], .z x[w], .w tp;
+//                j = HT_FULL: the x[w] of the light terms in .x, .y, .z
+//  htq[w][j][l]  .x qp, .y the coefficient as the float the term loop multiplies by (coef_ht's result)
+//  gm[w][q][l]   the gather addresses of columns 4q .. 4q + 3 of the lane's row
+constexpr int ABS_WAVES = 4;
+constexpr int ABS_GM_Q = (NV + 3) / 4;
+static_assert(HT_HELP <= 3, "the light terms' x[w] share one word group");
+struct AbsTables {
+    uint4 hx[ABS_WAVES][HX_SLOT_CAP][WAVE];
+    uint4 ht[ABS_WAVES][HT_FULL + 1][WAVE];
+    uint2 htq[ABS_WAVES][HT_FULL][WAVE];
+    uint4 gm[ABS_WAVES][ABS_GM_Q][WAVE];
+};
+static_assert(2 * ABS_WAVES * sizeof(SlotLDS) < 65536, "absolute offsets stay in the DS offset range");
+// table words are read this many terms ahead of their term (L2 latency; 4 and 8 measured the same)
+constexpr int EV_TAHEAD = 6;
+static_assert(EV_TAHEAD > EV_AHEAD, "the words come before the operands they address");
+
+// a wave's block of a table (uniform) and its lane's byte offset in a row of it
+template <typename W>
+__device__ __forceinline__ W abs_ld(const W *row, uint32_t lane_off) {
+    return *reinterpret_cast<const W *>(reinterpret_cast<const char *>(row) + (size_t)lane_off);
+}
+
+__device__ __forceinline__ HxOps hx_ops_abs(const char *l0, const uint4 &w) {
+    return HxOps{ldp(l0, w.x), ldp(l0, w.y), ldp(l0, w.z)};
+}
+// eval_hx_terms through the absolute tables.  l0: the workgroup's first slot;
+// hxw: the wave's hx block; l16: 16 * lane of the wave.  Also the finiteness
+// check of the tracker's sparse solve (hc_lu.hpp), on the entries where they
+// are stored instead of on the gathered rows: a row's non-zero entries are
+// exactly these, the rest of it are structural zeros.  Returns false where a
+// component sum of squares is not finite (an entry NaN, infinite or >= 2^64).
+// The gather's words (g, of gmw) are requested where the last term words have
+// been, so they arrive while the last terms are computed.
+__device__ __forceinline__ bool eval_hx_terms_abs(const uint4 (*hxw)[WAVE], char *l0, uint32_t l16,
+                                                  const uint4 (*gmw)[WAVE], uint4 (&g)[ABS_GM_Q]) {
+    uint4 w[HX_SLOT_CAP];
+#pragma unroll
+    for (int k = 0; k < EV_TAHEAD; k++) w[k] = abs_ld(hxw[k], l16);
+    HxOps o[EV_AHEAD + 1];
+#pragma unroll
+    for (int k = 0; k < EV_AHEAD; k++) o[k] = hx_ops_abs(l0, w[k]);
+    pf2 acc = {0.0f, 0.0f}, sq = {0.0f, 0.0f};
+#pragma unroll
+    for (int k = 0; k < HX_SLOT_CAP; k++) {
+        if (k + EV_TAHEAD < HX_SLOT_CAP) w[k + EV_TAHEAD] = abs_ld(hxw[k + EV_TAHEAD], l16);
+        if (k == HX_SLOT_CAP - EV_TAHEAD) {
+#pragma unroll
+            for (int q = 0; q < ABS_GM_Q; q++) g[q] = abs_ld(gmw[q], l16);
+        }
+        if (k + EV_AHEAD < HX_SLOT_CAP) o[(k + EV_AHEAD) % (EV_AHEAD + 1)] = hx_ops_abs(l0, w[k + EV_AHEAD]);
+        const HxOps &q = o[k % (EV_AHEAD + 1)];
+        const pf2 P = pcmul(q.t, q.xu);
+        acc = pcmadd(acc, P, q.xv);
+        if (hx_is_gend(k)) {
+            *reinterpret_cast<pf2 *>(l0 + w[k].w) = acc;
+            asm("v_pk_fma_f32 %0, %1, %1, %0" : "+v"(sq) : "v"(acc));
+            acc = pf2{0.0f, 0.0f};
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    return sq.x + sq.y < __builtin_inff();
+}
+
+// the gather through the words eval_hx_terms_abs requested
+__device__ __forceinline__ void gather_hx_abs(cf (&rA)[NV], const char *l0, const uint4 (&g)[ABS_GM_Q]) {
+#pragma unroll
+    for (int c = 0; c < NV; c++) {
+        const uint4 &gw = g[c / 4];
+        const pf2 v = ldp(l0, c % 4 == 0 ? gw.x : c % 4 == 1 ? gw.y : c % 4 == 2 ? gw.z : gw.w);
+        rA[c] = cmk(v.x, v.y);
+    }
+}
+
+template <int KIND>
+__device__ __forceinline__ RhsOps<KIND> rhs_ops_abs(const char *l0, const uint4 &w, const uint2 &wq) {
+    RhsOps<KIND> o;
+    if constexpr (KIND != RHS_HT) o.t = ldp(l0, w.w);
+    if constexpr (KIND != RHS_H) o.q = ldp(l0, wq.x);
+    o.xu = ldp(l0, w.x);
+    o.xv = ldp(l0, w.y);
+    o.xw = ldp(l0, w.z);
+    return o;
+}
+
+// eval_rhs through the absolute tables: the same loop, operation for operation
+template <int KIND>
+__device__ __forceinline__ cf eval_rhs_abs(const uint4 (*htw)[WAVE], const uint2 (*htqw)[WAVE], const char *l0,
+                                           uint32_t l16, bool ht_half, const RhsMasks &mk) {
+    constexpr bool SUB = KIND == RHS_HT;
+    constexpr bool Q = KIND != RHS_H;          // dH/dt terms: qp and the coefficient
+    const uint32_t l8 = l16 >> 1;
+    uint4 w[HT_FULL + 1];
+    uint2 wq[HT_FULL];   // (RHS_H: never loaded and never read; rhs_ops_abs takes it for the other kinds)
+#pragma unroll
+    for (int j = 0; j < EV_TAHEAD; j++) {
+        w[j] = abs_ld(htw[j], l16);
+        if constexpr (Q) wq[j] = abs_ld(htqw[j], l8);
+    }
+    RhsOps<KIND> o[EV_AHEAD + 1];
+#pragma unroll
+    for (int j = 0; j < EV_AHEAD; j++) o[j] = rhs_ops_abs<KIND>(l0, w[j], wq[j]);
+    pf2 acc = {0.0f, 0.0f};
+    pf2 hp[HT_HELP];
+#pragma unroll
+    for (int j = 0; j < HT_FULL; j++) {
+        if (j + EV_TAHEAD < HT_FULL + 1) w[j + EV_TAHEAD] = abs_ld(htw[j + EV_TAHEAD], l16);
+        if constexpr (Q)
+            if (j + EV_TAHEAD < HT_FULL) wq[j + EV_TAHEAD] = abs_ld(htqw[j + EV_TAHEAD], l8);
+        if (j + EV_AHEAD < HT_FULL)
+            o[(j + EV_AHEAD) % (EV_AHEAD + 1)] = rhs_ops_abs<KIND>(l0, w[j + EV_AHEAD], wq[j + EV_AHEAD]);
+        const RhsOps<KIND> &q = o[j % (EV_AHEAD + 1)];
+        pf2 P;
+        if constexpr (KIND == RHS_HT) {
+            const float co = __uint_as_float(wq[j].y);
+            const pf2 s = q.q * pf2{co, co};
+            P = pcmul(pcmul(s, q.xu), q.xv);
+        } else if constexpr (KIND == RHS_H) {
+            P = pcmul(pcmul(q.t, q.xu), q.xv);
+        } else {
+            const float co = __uint_as_float(wq[j].y);
+            const pf2 s = q.q * pf2{-co, -co};
+            const pf2 pre = {ht_half ? s.x : q.t.x, ht_half ? s.y : q.t.y};
+            P = pcmul(pcmul(pre, q.xu), q.xv);
+        }
+        if (j < HT_HELP_FIRST) {
+            acc = SUB ? pcmsub(acc, P, q.xw) : pcmadd(acc, P, q.xw);
+        } else {
+            hp[j - HT_HELP_FIRST] = P;
+            acc = pcmacc_masked<SUB>(acc, P, q.xw, mk.acc[j - HT_HELP_FIRST]);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+#pragma unroll
+    for (int q = 0; q < HT_HELP; q++) {
+        const pf2 P = from_partner(hp[q]);
+        const uint4 &lw = w[HT_FULL];
+        const pf2 xw = ldp(l0, q == 0 ? lw.x : q == 1 ? lw.y : lw.z);
+        acc = pcmacc_masked<SUB>(acc, P, xw, mk.light[q]);
+    }
+    return cmk(acc.x, acc.y);
+}
+
 }  // namespace hc

@@ -538,7 +538,7 @@ void hc_trifocal_set_small_launch(int mode) {
 void hc_trifocal_set_retry_reuse(int on) { hc::g_retry_reuse.store(on ? 1 : 0, std::memory_order_relaxed); }
 
 const char *hc_trifocal_version(void) {
-    return "hc_trifocal gfx950 v10.8 (2 paths/wave, structurally sparse LDS-broadcast LU with lean pivot steps, "
+    return "hc_trifocal gfx950 v10.9 (2 paths/wave, structurally sparse LDS-broadcast LU with lean pivot steps, "
            "one exec region per pivot step for the eligible rows with the column groups through scratch windows, "
            "column groups by structural class (never-fillable groups untested, always-live groups unconditional), "
            "pivot search narrowed to the candidate rows' DPP group "
@@ -547,7 +547,8 @@ const char *hc_trifocal_version(void) {
            "group untested), "
            "structure-agnostic twin kernels for other dH/dx structures, readlane back substitution, pipelined evals over "
            "per-slot prefix tables, 5 waves/SIMD, time slicing at step boundaries with least-attained-service "
-           "issue priority, a rejected step's retry reuses its first RK4 slope)";
+           "issue priority, a rejected step's retry reuses its first RK4 slope, the throughput kernel's operand "
+           "addresses read complete from per-slot tables and its finiteness check made on the dH/dx entries)";
 }
 
 }  // extern "C"

@@ -41,8 +41,12 @@ struct Workspace {
     unsigned pad1[3];
     // written by k_prep_tables
     EvalTables tab;
+    // the throughput tracking kernel's operand addresses (hc_eval.hpp), built with tab and valid with it
+    AbsTables abs;
 };
 static_assert(offsetof(Workspace, tab) == 64, "control block is 64 bytes");
+static_assert(ABS_WAVES == WAVES_PER_WG && offsetof(Workspace, abs) % 16 == 0, "one table block per wave, 16-B words");
+static_assert(sizeof(Workspace) < (1u << 20), "the base workspace stays below 1 MiB");
 
 // Time slicing (hc_ring.hpp).  Suspend block of path b (32 x 8 B): words 0..29 = x, word 30 = (t0, dt),
 // word 31 = (stepidx | nsteps << 16, ncorr | succ << 16 | flags << 30); the

@@ -815,12 +815,15 @@ __device__ __forceinline__ void lu_backward(const cf (&rA)[NV], cf &rB, int rowi
 // rows (row r writes column group J at scratch[2r + J]); the caller's data
 // there is lost.
 constexpr int LU_SCRATCH_CF = 2 * 31 + 32;   // 94: lane r's window scratch[2r .. 2r + 31]
-template <bool DENSE, int LAT = 0, bool STRUCT = false>
+// ENTCHK: the caller has made the finiteness check on the entries it gathered
+// the rows from (eval_hx_terms_abs) and passes the wave-uniform verdict in
+// ent_bad; the row loop below is left out.
+template <bool DENSE, int LAT = 0, bool STRUCT = false, bool ENTCHK = false>
 __device__ __forceinline__ cf lu_solve(cf (&rA)[NV], cf rB, int lane, uint32_t pattern, LUBuf &L, cf *scratch,
-                                      bool &redo, unsigned long long count_mask = ~0ull);
-template <bool DENSE, int LAT, bool STRUCT>
+                                      bool &redo, unsigned long long count_mask = ~0ull, bool ent_bad = false);
+template <bool DENSE, int LAT, bool STRUCT, bool ENTCHK>
 __device__ __forceinline__ cf lu_solve(cf (&rA)[NV], cf rB, int lane, uint32_t pattern, LUBuf &L, cf *scratch,
-                                      bool &redo, unsigned long long count_mask) {
+                                      bool &redo, unsigned long long count_mask, bool ent_bad) {
     (void)count_mask;   // diagnostic builds (HC_DIAG_LUWORK): lanes whose executed work is counted
     const int r = lane & 31, hb = lane & 32;
     const bool row_lane = r < NV;
@@ -828,7 +831,12 @@ __device__ __forceinline__ cf lu_solve(cf (&rA)[NV], cf rB, int lane, uint32_t p
     if constexpr (DENSE) HC_ISA_MARK("lu_dense");   // (scripts/isa_phases.py: the dense re-solve's copy)
     else HC_ISA_MARK("lu_sparse");
     HC_ISA_MARK("lu_finite");
-    if constexpr (!DENSE) {
+    if constexpr (!DENSE && ENTCHK) {
+        if (__builtin_expect(ent_bad, 0)) {
+            redo = true;
+            return cmk(0.0f, 0.0f);
+        }
+    } else if constexpr (!DENSE) {
         // every entry finite and below 2^64 in magnitude (inside the 2^88 the
         // sparse path needs): the per-component sums of squares (v_pk_fma_f32, 30
         // VALU) stay finite only then -- NaN propagates, an inf or |entry| >= 2^64

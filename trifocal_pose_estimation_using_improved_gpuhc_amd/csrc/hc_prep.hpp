@@ -12,7 +12,9 @@ namespace hc {
 // validated; a table that does not fit sets HC_ERROR_TABLE and the tracker
 // leaves its outputs untouched.  The tables persist in the workspace: a launch
 // whose index table hashes to the one they were built from (all 256 threads
-// hash it, ~10 KB each) skips the compaction.
+// hash it, ~10 KB each) skips the compaction.  The same pass writes the
+// throughput kernel's slot-absolute address tables (AbsTables) from the
+// finished words, so the two are always of one table.
 //
 // Also the per-launch reset of the time-slicing counters (rq != nullptr): head,
 // tail and avail zeroed, the ring epoch bumped; ring entries not cleared yet
@@ -441,6 +443,50 @@ __global__ void __launch_bounds__(PREP_THREADS) k_prep_tables(PrepArgs pa) {
         }
     }
     __syncthreads();
+    {
+        // F: the slot-absolute address tables of the throughput tracking kernel
+        // (hc_eval.hpp AbsTables), from the finished words of C and E: every
+        // field of a word plus the byte offset of the lane's path slot from the
+        // workgroup's first one.  Rebuilt whenever tab is (same pass, same hash).
+        AbsTables *A = &ws->abs;
+        auto slot_base = [](int i) -> uint32_t {   // i: (wave, lane) of a table row, wave * 64 + lane
+            return (uint32_t)(((i >> 6) * 2 + ((i >> 5) & 1)) * (int)sizeof(SlotLDS));
+        };
+        for (int i = tid; i < ABS_WAVES * HX_SLOT_CAP * WAVE; i += PREP_THREADS) {
+            const int l = i & 63, k = (i >> 6) % HX_SLOT_CAP, wv = (i >> 6) / HX_SLOT_CAP;
+            const uint32_t sb = slot_base(wv * 64 + l);
+            const uint32_t w = T->hx[k * 32 + (l & 31)];
+            const int sl = hx_gslot(k);
+            const uint32_t d = T->hxd[sl >> 1][l & 31];
+            A->hx[wv][k][l] = make_uint4(sb + (w & 0xFFFFu), sb + ((w >> 16) & 0xFFu), sb + (w >> 24),
+                                         sb + ((sl & 1) ? d >> 16 : d & 0xFFFFu));
+        }
+        for (int i = tid; i < ABS_WAVES * (HT_FULL + 1) * WAVE; i += PREP_THREADS) {
+            const int l = i & 63, j = (i >> 6) % (HT_FULL + 1), wv = (i >> 6) / (HT_FULL + 1);
+            const uint32_t sb = slot_base(wv * 64 + l);
+            if (j < HT_FULL) {
+                const uint2 w = T->ht[j * 32 + (l & 31)];
+                A->ht[wv][j][l] = make_uint4(sb + (w.y & 0xFFu), sb + ((w.y >> 8) & 0xFFu), sb + ((w.y >> 16) & 0xFFu),
+                                             sb + (w.x & 0xFFFFu));
+                A->htq[wv][j][l] = make_uint2(sb + (w.x >> 16), __float_as_uint(coef_ht(w)));
+            } else {
+                uint32_t xw[3] = {sb + x30, sb + x30, sb + x30};
+                for (int q = 0; q < HT_HELP; q++) xw[q] = sb + ((T->ht[(HT_FULL + q) * 32 + (l & 31)].y >> 16) & 0xFFu);
+                A->ht[wv][j][l] = make_uint4(xw[0], xw[1], xw[2], sb + x30);
+            }
+        }
+        for (int i = tid; i < ABS_WAVES * ABS_GM_Q * WAVE; i += PREP_THREADS) {
+            const int l = i & 63, q = (i >> 6) % ABS_GM_Q, wv = (i >> 6) / ABS_GM_Q;
+            const uint32_t sb = slot_base(wv * 64 + l);
+            uint32_t g[4];
+            for (int e = 0; e < 4; e++) {
+                const int c = 4 * q + e;
+                const uint32_t w = T->gm[min(c, NV - 1) >> 1][l & 31];   // (words past column 29: unused)
+                g[e] = sb + ((c & 1) ? w >> 16 : w & 0xFFFFu);
+            }
+            A->gm[wv][q][l] = make_uint4(g[0], g[1], g[2], g[3]);
+        }
+    }
     if (r == 0) {
         // eval_rhs masks: help term q of the helpers (no accumulation), light
         // term q of the owners

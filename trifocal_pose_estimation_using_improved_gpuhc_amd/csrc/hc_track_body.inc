@@ -16,6 +16,13 @@
 // kernel_GPUHC_trifocal_pose_PH_CodeOpt_TrunPaths (..._TrunPaths.cu:45-290) and,
 // with ABORT, ..._TrunPaths_TrunRANSAC (..._TrunRANSAC.cu:45-327).
     constexpr bool LUSTRUCT = LUS;
+    // The throughput tracking kernel reads its evaluations' operand addresses
+    // complete, from the slot-absolute tables (hc_eval.hpp AbsTables), and checks
+    // finiteness on the dH/dx entries instead of the gathered rows (hc_lu.hpp
+    // ENTCHK).  The latency-critical kernels keep the L1-resident packed tables.
+    // (The variant builds that measured the four parts apart are not kept; DESIGN.md section 3.6
+    // says how each ABSTAB site below was switched.)
+    constexpr bool ABSTAB = !ABORT && !ARCH && LULAT == 0;
     __shared__ cf s_sp[NPP];
     __shared__ SlotLDS s_slot[2 * WAVES_PER_WG];
     Workspace *ws = a.ws;
@@ -51,6 +58,10 @@
     __syncthreads();
     const bool rl = r < NV;
     wave_lds_sync();
+    // ABSTAB: the wave's blocks of the absolute tables (uniform) and the first slot they count from
+    const AbsTables *AT = &ws->abs;
+    const int wv = ABSTAB ? __builtin_amdgcn_readfirstlane(wid) : 0;
+    char *const l0 = reinterpret_cast<char *>(s_slot);
 
     // per-slot state (uniform within a half)
     int ph = PH_DEQ, b = -1, smp_loaded = -1;
@@ -487,6 +498,7 @@
         // constants (bpermute addresses, r == i masks) out of the path loop
         const int lane_v = lane_fresh();   // recomputed (2 VALU), not held across the loop
         const int r_v = lane_v & 31;
+        const uint32_t l16 = (uint32_t)lane_v << 4;   // ABSTAB: the lane's byte offset in a table row
         const uint32_t row_pat = s_rowc[GM_WORDS][r_v];
         const bool act = ph_in == PH_STAGE;
         const bool pred = act && s_in < 4;
@@ -504,22 +516,35 @@
 #endif
             if (any_p && any_c) {                                            // :185 | :221, one pass
                 HC_ISA_MARK("ev_rhs_mixed");
-                rB = eval_rhs<RHS_MIXED>(s_ht, S, r_v, pred, mk);
+                if constexpr (ABSTAB) rB = eval_rhs_abs<RHS_MIXED>(AT->ht[wv], AT->htq[wv], l0, l16, pred, mk);
+                else rB = eval_rhs<RHS_MIXED>(s_ht, S, r_v, pred, mk);
             } else if (any_p) {                                              // :185
                 HC_ISA_MARK("ev_rhs_ht");
-                const cf t = eval_rhs<RHS_HT>(s_ht, S, r_v, true, mk);
+                const cf t = ABSTAB ? eval_rhs_abs<RHS_HT>(AT->ht[wv], AT->htq[wv], l0, l16, true, mk)
+                                    : eval_rhs<RHS_HT>(s_ht, S, r_v, true, mk);
                 if (pred) rB = t;
             } else if (any_c) {                                              // :221
                 HC_ISA_MARK("ev_rhs_h");
-                const cf t = eval_rhs<RHS_H>(s_ht, S, r_v, false, mk);
+                const cf t = ABSTAB ? eval_rhs_abs<RHS_H>(AT->ht[wv], AT->htq[wv], l0, l16, false, mk)
+                                    : eval_rhs<RHS_H>(s_ht, S, r_v, false, mk);
                 if (!pred) rB = t;
             }
         }
         HC_DIAG_MARK(3);
         cf rA[NV];
         HC_ISA_MARK("ev_hx");
-        eval_hx(rA, s_hx, s_hxd, &s_rowc[0][0], S, r_v);                     // :184 / :220
+        bool ent_ok = true;   // ABSTAB: the entries' sums of squares are finite
+        if constexpr (ABSTAB) {
+            uint4 gmv[ABS_GM_Q];
+            ent_ok = eval_hx_terms_abs(AT->hx[wv], l0, l16, AT->gm[wv], gmv);
+            wave_lds_sync();
+            HC_ISA_MARK("ev_gather");
+            gather_hx_abs(rA, l0, gmv);
+        } else {
+            eval_hx(rA, s_hx, s_hxd, &s_rowc[0][0], S, r_v);                 // :184 / :220
+        }
         wave_lds_sync();
+        const bool ent_bad = ABSTAB && __ballot(!ent_ok) != 0ull;
         HC_DIAG_MARK(2);
         bool redo;
         LUBuf &LB = *reinterpret_cast<LUBuf *>(S.lu);
@@ -527,9 +552,9 @@
         // (a dense re-solve evaluates dH/dx again)
         static_assert(ENT_CAP >= LU_SCRATCH_CF && offsetof(SlotLDS, ent) % 16 == 0, "LU scratch in SlotLDS::ent");
 #ifdef HC_DIAG_LUWORK
-        cf k = lu_solve<false, LULAT, LUSTRUCT>(rA, rB, lane_v, row_pat, LB, S.ent, redo, __ballot(act));   // :188 / :224
+        cf k = lu_solve<false, LULAT, LUSTRUCT, ABSTAB>(rA, rB, lane_v, row_pat, LB, S.ent, redo, __ballot(act), ent_bad);   // :188 / :224
 #else
-        cf k = lu_solve<false, LULAT, LUSTRUCT>(rA, rB, lane_v, row_pat, LB, S.ent, redo);                  // :188 / :224
+        cf k = lu_solve<false, LULAT, LUSTRUCT, ABSTAB>(rA, rB, lane_v, row_pat, LB, S.ent, redo, ~0ull, ent_bad);           // :188 / :224
 #endif
         HC_ISA_MARK("ctl_redo");
         if (__builtin_expect(redo, 0)) {
@@ -543,21 +568,31 @@
             const bool act_r = S.st.ph == PH_STAGE, pred_r = act_r && S.st.s < 4;
             // a fresh lane id: the table addresses of the stage's evaluations
             // are not shared with (and held across the LU for) this rare path
-            const int r_r = lane_fresh() & 31;
+            const int l_r = lane_fresh(), r_r = l_r & 31;
+            const uint32_t l16_r = (uint32_t)l_r << 4;
             cf rb = cmk(0.0f, 0.0f);
             if (__ballot(pred_r) != 0ull) {
-                const cf t = eval_rhs<RHS_HT>(s_ht, S, r_r, true, rhs_masks(T));
+                const cf t = ABSTAB ? eval_rhs_abs<RHS_HT>(AT->ht[wv], AT->htq[wv], l0, l16_r, true, rhs_masks(T))
+                                    : eval_rhs<RHS_HT>(s_ht, S, r_r, true, rhs_masks(T));
                 if (pred_r) rb = t;
             }
             if (__ballot(act_r && !pred_r) != 0ull) {
-                const cf t = eval_rhs<RHS_H>(s_ht, S, r_r, false, rhs_masks(T));
+                const cf t = ABSTAB ? eval_rhs_abs<RHS_H>(AT->ht[wv], AT->htq[wv], l0, l16_r, false, rhs_masks(T))
+                                    : eval_rhs<RHS_H>(s_ht, S, r_r, false, rhs_masks(T));
                 if (!pred_r) rb = t;
             }
             // (eval_hx without its phase marker: the ISA phase count keeps this rare
             // copy under redo_evals)
-            eval_hx_terms(s_hx, s_hxd, reinterpret_cast<char *>(&S), r_r);
-            wave_lds_sync();
-            gather_hx(rA, &s_rowc[0][0], S, r_r);
+            if constexpr (ABSTAB) {
+                uint4 gmv[ABS_GM_Q];
+                eval_hx_terms_abs(AT->hx[wv], l0, l16_r, AT->gm[wv], gmv);
+                wave_lds_sync();
+                gather_hx_abs(rA, l0, gmv);
+            } else {
+                eval_hx_terms(s_hx, s_hxd, reinterpret_cast<char *>(&S), r_r);
+                wave_lds_sync();
+                gather_hx(rA, &s_rowc[0][0], S, r_r);
+            }
             wave_lds_sync();
 #ifdef HC_DIAG_LUWORK
             k = lu_solve<true>(rA, rb, lane_v, row_pat, LB, S.ent, redo, __ballot(act_r));
