@@ -2,8 +2,8 @@
 // launchers (magmaHC/gpu-kernels/magmaHC-kernels.hpp:24-105, implemented in
 // kernel_GPUHC_trifocal_2op1p_30x30_PH_CodeOpt_TrunPaths[_TrunRANSAC][_Volta].cu)
 // and of the archived ablation launchers ..._PH_CodeOpt[_Volta] (no path
-// truncation) and ..._PH (explicit RK as well; arxived_GPU_code/gpu-kernels/
-// magmaHC-kernels.hpp:42-96)
+// truncation), ..._PH (explicit RK as well) and ..._P2C (the original
+// parameter-to-coefficient tracker; arxived_GPU_code/gpu-kernels/magmaHC-kernels.hpp)
 // on top of this repository's C-ABI (include/hc_trifocal.h).
 //
 // A maintainer compiles this file in place of the four .cu files and links
@@ -35,6 +35,7 @@
 
 #include "hc_trifocal_shim.h"
 #include "magmaHC-kernels.hpp"
+#include "p2c/hc_trifocal_p2c.h"
 
 namespace {
 
@@ -298,4 +299,28 @@ real_Double_t kernel_GPUHC_trifocal_2op1p_30x30_PH(
                  d_startSols_array, d_Track_array, d_startParams, d_targetParams, d_diffParams, nullptr, d_dHdx_indx,
                  d_dHdt_indx, d_is_GPU_HC_Sol_Converge, d_is_GPU_HC_Sol_Infinity,
                  "kernel_GPUHC_trifocal_2op1p_30x30_PH", false, true);
+}
+
+// The archived P2C launcher (include/p2c/hc_trifocal_p2c.h): its index tables and
+// per-sample coefficient blocks go through as they are; no time slicing, so the
+// stream's base workspace is all it needs.
+real_Double_t kernel_GPUHC_trifocal_2op1p_30x30_P2C(
+    magma_queue_t my_queue, int sub_RANSAC_iters, int HC_max_steps, int HC_max_correction_steps,
+    int HC_delta_t_incremental_steps, magmaFloatComplex **d_startSols_array, magmaFloatComplex **d_Track_array,
+    int *d_Hx_idx_array, int *d_Ht_idx_array, magmaFloatComplex *d_phc_coeffs_Hx, magmaFloatComplex *d_phc_coeffs_Ht,
+    bool *d_is_GPU_HC_Sol_Converge, bool *d_is_GPU_HC_Sol_Infinity, magmaFloatComplex * /*d_Debug_Purpose*/) {
+    const char *name = "kernel_GPUHC_trifocal_2op1p_30x30_P2C";
+    hipStream_t s = magma_queue_get_hip_stream(my_queue);
+    StreamState *st = state_for(s, false);
+    if (!st) { report(HC_ERROR_WORKSPACE, name); return 0.0; }
+    hcTrackArgs a = make_args(sub_RANSAC_iters, HC_max_steps, HC_max_correction_steps, HC_delta_t_incremental_steps,
+                              d_startSols_array, d_Track_array, nullptr, nullptr, nullptr, nullptr,
+                              d_is_GPU_HC_Sol_Converge, d_is_GPU_HC_Sol_Infinity);
+    hcP2cArgs p{};
+    p.hx_index = reinterpret_cast<const int32_t *>(d_Hx_idx_array);
+    p.ht_index = reinterpret_cast<const int32_t *>(d_Ht_idx_array);
+    p.coeffs_hx = reinterpret_cast<const hcComplex *>(d_phc_coeffs_Hx);
+    p.coeffs_ht = reinterpret_cast<const hcComplex *>(d_phc_coeffs_Ht);
+    report(hc_trifocal_2op1p_30x30_track_p2c(&a, &p, st->workspace, st->ws_bytes, (hcStream)s), name);
+    return 0.0;
 }

@@ -42,6 +42,11 @@ double shim_ph(void *q, int n, int ms, int mc, int inc, mfc **ssa, mfc **tra, mf
     return kernel_GPUHC_trifocal_2op1p_30x30_PH(static_cast<magma_queue_t>(q), n, ms, mc, inc, ssa, tra, sp, tp, dp, hx,
                                                 ht, conv, inf, nullptr);
 }
+double shim_p2c(void *q, int n, int ms, int mc, int inc, mfc **ssa, mfc **tra, int *hx, int *ht, mfc *chx, mfc *cht,
+                bool *conv, bool *inf) {
+    return kernel_GPUHC_trifocal_2op1p_30x30_P2C(static_cast<magma_queue_t>(q), n, ms, mc, inc, ssa, tra, hx, ht, chx,
+                                                 cht, conv, inf, nullptr);
+}
 double shim_trunransac(void *q, int n, int e, int ms, int mc, int inc, mfc **ssa, mfc **tra, mfc *sp, mfc *tp,
                        mfc *dp, int *unified, float *edgels, float *K, bool *conv, bool *inf, bool *found,
                        int *batch_index) {

@@ -23,6 +23,8 @@
 #             (scripts/gated_stop.py [TRIALS]) -> TAG_gated.json
 #   gated_ab  the launches that existed before the gated one (scripts/gated_stop.py --existing) on builds
 #             NAME=lib/libX.so ... (package-relative), alternately, 2 rounds -> TAG_gated_existing.jsonl
+#   p2c       the ablation ladder from the archived P2C tracker up: P2C, PH, PH_CodeOpt and the headline launch
+#             alternately on config 2 (scripts/ablation_p2c.py [--reps R]) -> TAG_ablation_p2c.json
 #   validate  tests,luwork,bench,profile,datasets
 # Extra environment: BENCH_ARGS (bench step), AB_ROUNDS (ab step, default 3), AB_ARGS (more ab_track.py options), TTFP_ARGS (ttfp_ab step,
 # e.g. "--dataset 10").
@@ -103,6 +105,7 @@ for k,v in sorted(g.items()): print(k, v)" ;;
     multi) run multi 300 python scripts/multi_triplet.py "$@" > $O/${T}_multi.json; rc=$?; cat $O/${T}_multi.json ;;
     joint) run joint 600 python scripts/joint_pose.py "$@" > $O/${T}_joint.json; rc=$?; cat $O/${T}_joint.json ;;
     gated) run gated 900 python scripts/gated_stop.py "$@" > $O/${T}_gated.json; rc=$?; tail -c 600 $O/${T}_gated.json ;;
+    p2c) run p2c 300 python scripts/ablation_p2c.py --out $O/${T}_ablation_p2c.json "$@"; rc=$? ;;
     gated_ab)
       rc=0
       for rd in 0 1; do

@@ -6,7 +6,9 @@ Python through ctypes (this package).  See DESIGN.md.
 
 tracker.DeviceTracker drives the launches (track, track_grouped; with
 gate=<ratio> the grouped abort launch stops on joint inlier support), pose the
-pose-support calls, multi the multi-triplet layout.
+pose-support calls, multi the multi-triplet layout, p2c the archived
+parameter-to-coefficient formulation (its coefficient map and blocks; launched
+by DeviceTracker.track_p2c).
 """
 from . import _abi
 from .problem import (PROBLEM, Problem, RansacData, count_solutions, load_problem, load_ransac_data,

@@ -120,6 +120,14 @@ class hcJointGate(C.Structure):
                 ("joint_inliers", C.c_void_p)]
 
 
+class hcP2cArgs(C.Structure):
+    """include/p2c/hc_trifocal_p2c.h: the P2C launch's own argument block, 32 bytes."""
+    _fields_ = [("hx_index", C.c_void_p),
+                ("ht_index", C.c_void_p),
+                ("coeffs_hx", C.c_void_p),
+                ("coeffs_ht", C.c_void_p)]
+
+
 class hcIpcHandle(C.Structure):
     _fields_ = [("reserved", C.c_ubyte * 64)]
 
@@ -198,6 +206,16 @@ SIGNATURES = (
 )
 DECLARED_SYMBOLS = tuple(s.name for s in SIGNATURES)
 
+# include/p2c/hc_trifocal_p2c.h, the P2C mode's header beside include/*.h: a table
+# of its own, bound by lib() like SIGNATURES and held against its header the same
+# way (tests/test_p2c_host.py)
+P2C_SIGNATURES = (
+    Sig("hc_trifocal_2op1p_30x30_track_p2c", _ST, (_TA, C.POINTER(hcP2cArgs), *_WS), True),
+    Sig("hc_trifocal_p2c_eval_batched", _ST, (_i, _p, _p, _p, _p, _p, _p, _p, _p, _p, *_WS), True),
+    Sig("hc_p2c_coefficients", _ST, (_i, _p, _p, _p, _p, _p), True),
+)
+P2C_DECLARED_SYMBOLS = tuple(s.name for s in P2C_SIGNATURES)
+
 _lib = None
 
 
@@ -213,7 +231,7 @@ def lib() -> C.CDLL:
         # instead of pulling a second HIP/HSA runtime from /opt/rocm.
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
-        for s in SIGNATURES:
+        for s in SIGNATURES + P2C_SIGNATURES:
             fn = getattr(L, s.name, None)
             if fn is None:
                 if s.optional:

@@ -270,6 +270,53 @@ __device__ __forceinline__ void build_prefixes(SlotLDS &S, int r, const uint2 *p
     build_prefix_rounds(S, r, pre);
 }
 
+// The P2C mode (include/p2c/hc_trifocal_p2c.h): a term's parameter part is one
+// coefficient, a polynomial in t of the sample's block (the archived
+// dev-eval-indxing-..._P2C.cuh:45-64), so tp holds c * coefHx_k(t) per (c, k) and
+// qp coefHt_k(t) per k, and the term loops are the ones above: dH/dx
+// ((c coefHx_k) x_u) x_v, H (((c coefHx_k) x_u) x_v) x_w, dH/dt the same on
+// c coefHt_k, subtracted (:74-117).  Lane r stages coefficient r (lanes 0..5
+// also 32 + r): coefHx_k = C0 + C1*t + (C2*t)*t in ent[k], coefHt_k = D0 + D1*t
+// in ent[38 + k], complex * float.  chx: the sample's 38 x 3 block, cht: 38 x 2.
+constexpr int P2C_NK = 38;
+constexpr int SLOT_STG_P2C_HT_DELTA = 8 * P2C_NK;
+static_assert(2 * P2C_NK <= ENT_CAP - 1, "the P2C staging area lies below the structural zero");
+__device__ __forceinline__ void p2c_stage(SlotLDS &S, int r, const cf *chx, const cf *cht, float t) {
+    cf *stg = S.ent;
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+        const int k = r + 32 * q;
+        if (k < P2C_NK) {
+            stg[k] = cadd(cadd(chx[3 * k], cscale(chx[3 * k + 1], t)), cscale(cscale(chx[3 * k + 2], t), t));
+            stg[P2C_NK + k] = cadd(cht[2 * k], cscale(cht[2 * k + 1], t));
+        }
+    }
+}
+// build_prefix_rounds for the jobs k_prep_tables_p2c writes: .x = the staging
+// place of the job's coefficient, .y as there
+__device__ __forceinline__ void build_prefix_rounds_p2c(SlotLDS &S, int r, const uint2 *pre) {
+    char *sb = reinterpret_cast<char *>(&S);
+    wave_lds_sync();
+#pragma unroll
+    for (int k = 0; k < PRE_TP_ROUNDS; k++) {
+        const uint2 w = pre[k * 32 + r];
+        const pf2 c = ldp(sb, w.x & 0xFFFFu);
+        const float co = coef_b2(w.y);
+        *reinterpret_cast<pf2 *>(sb + (w.y & 0xFFFFu)) = c * pf2{co, co};                 // c * coefHx_k
+    }
+#pragma unroll
+    for (int k = PRE_TP_ROUNDS; k < PRE_ROUNDS; k++) {
+        const uint2 w = pre[k * 32 + r];
+        *reinterpret_cast<pf2 *>(sb + (w.y & 0xFFFFu)) = ldp(sb + SLOT_STG_P2C_HT_DELTA, w.x & 0xFFFFu);   // coefHt_k
+    }
+    wave_lds_sync();
+}
+__device__ __forceinline__ void build_prefixes_p2c(SlotLDS &S, int r, const uint2 *pre, const cf *chx, const cf *cht,
+                                                   float t0) {
+    p2c_stage(S, r, chx, cht, t0);
+    build_prefix_rounds_p2c(S, r, pre);
+}
+
 // dH/dt, H and the merged pass share one loop (eval_rhs).
 //  * dH/dt: b = -sum_j c*(d[a]*p[b] + d[b]*p[a])*x[u]*x[v]*x[w]  (:91-119),
 //    d[a]*p[b] + d[b]*p[a] from the slot's qp table;

@@ -8,6 +8,7 @@
 // the relative-pose error against the ground truth like Evaluations.cpp:360-543.
 #include "../../include/hc_host.h"
 #include "../../include/hc_pose.h"
+#include "../../include/p2c/hc_trifocal_p2c.h"
 
 #include <cmath>
 #include <cstdio>
@@ -300,6 +301,34 @@ int hc_pose_residuals(const float *gt21, const float *gt31, const float *R21, co
     out[2] = translation_residual(gt21 + 9, t21);
     out[3] = translation_residual(gt31 + 9, t31);
     return ((double)out[2] < 1e-1 && (double)out[3] < 1e-1 && (double)out[0] < 1e-1 && (double)out[1] < 1e-1) ? 1 : 0;
+}
+
+// The P2C coefficient blocks (include/p2c/hc_trifocal_p2c.h): coefficient k = p_a p_b
+// with p(t) = s + t d.  cmul / cadd of the arithmetic specification (hc_device.hpp).
+hcStatus hc_p2c_coefficients(int num_samples, const int32_t *coeff_map, const hcComplex *start_params,
+                             const hcComplex *diff_params, hcComplex *coeffs_hx, hcComplex *coeffs_ht) {
+    if (num_samples < 0 || !coeff_map || !start_params || (num_samples > 0 && (!diff_params || !coeffs_hx || !coeffs_ht)))
+        return HC_ERROR_INVALID_VALUE;
+    for (int k = 0; k < 2 * HC_P2C_NUM_COEFFS; k++)
+        if (coeff_map[k] < 0 || coeff_map[k] >= NPP) return HC_ERROR_INVALID_VALUE;
+    auto mul = [](hcComplex a, hcComplex b) {
+        return hcComplex{std::fmaf(a.re, b.re, -(a.im * b.im)), std::fmaf(a.re, b.im, a.im * b.re)};
+    };
+    auto add = [](hcComplex a, hcComplex b) { return hcComplex{a.re + b.re, a.im + b.im}; };
+    for (int n = 0; n < num_samples; n++) {
+        const hcComplex *d = diff_params + (size_t)n * NPP;
+        for (int k = 0; k < HC_P2C_NUM_COEFFS; k++) {
+            const int a = coeff_map[2 * k], b = coeff_map[2 * k + 1];
+            const hcComplex c0 = mul(start_params[a], start_params[b]);
+            const hcComplex c1 = add(mul(start_params[a], d[b]), mul(d[a], start_params[b]));
+            const hcComplex c2 = mul(d[a], d[b]);
+            hcComplex *hx = coeffs_hx + ((size_t)n * HC_P2C_NUM_COEFFS + k) * 3;
+            hcComplex *ht = coeffs_ht + ((size_t)n * HC_P2C_NUM_COEFFS + k) * 2;
+            hx[0] = c0; hx[1] = c1; hx[2] = c2;
+            ht[0] = c1; ht[1] = add(c2, c2);
+        }
+    }
+    return HC_SUCCESS;
 }
 
 }  // extern "C"

@@ -17,14 +17,17 @@
 // One translation unit: the device side is the headers below, one per concern,
 // this file the host side.  The plain kernels are emitted in the order of these
 // includes (k_prep_tables, k_cgesv, k_eval, k_ring_check), which is part of the
-// library's build id: keep it.
+// library's build id: keep it.  (The P2C mode's plain kernels
+// are templates for that reason: hc_p2c.hpp.)
 #include "hc_layout.hpp"
 #include "hc_prep.hpp"
 #include "hc_components.hpp"
 #include "hc_ring.hpp"
 #include "hc_score.hpp"
 #include "hc_track.hpp"
+#include "hc_p2c.hpp"
 #include "../../include/hc_trifocal_testing.h"
+#include "../../include/p2c/hc_trifocal_p2c.h"
 
 #include <atomic>
 #include <climits>
@@ -117,13 +120,14 @@ static int resident_wgs(const void *kernel) { return grid_for(INT_MAX, kernel); 
 
 // The launches that exist, one per tracking entry point of hc_trifocal.h, and
 // the one argument block each needs besides hcTrackArgs (the others stay null).
-// Declared in the order of track_kernels' table.
-enum class TrackMode { GatedAbort, GroupedAbort, Abort, Ph, PhCodeopt, Track };
+// Declared in the order of track_kernels' table (P2c: the pair named after it).
+enum class TrackMode { GatedAbort, GroupedAbort, Abort, Ph, PhCodeopt, Track, P2c };
 struct TrackLaunch {
     TrackMode mode;
     const hcAbortArgs *ab = nullptr;          // Abort
     const hcGroupedAbortArgs *gr = nullptr;   // GroupedAbort, GatedAbort (non-null: checked by the entry point)
     const hcJointGate *jg = nullptr;          // GatedAbort (validated by its entry point)
+    const hcP2cArgs *p2c = nullptr;           // P2c (non-null, its pointers too: checked by the entry point)
 };
 
 // (mode, small-launch decision) -> the kernel whose LU is specialised to this
@@ -132,7 +136,7 @@ struct TrackLaunch {
 // LDS per workgroup -> 5 waves/SIMD.  Abort mode: HC_ABORT_MINW
 // (hc_track.hpp).  The device compiler emits the instantiations in the order
 // this function first names them, after the plain kernels: a
-// new kernel goes at the end of a row, and the small-launch pair stays last.
+// new kernel is named after all of them, as the P2C pair below.
 struct TrackKernels { const void *lus, *any; };
 static TrackKernels track_kernels(TrackMode mode, bool small) {
     static const void *const by_mode[2][6] = {
@@ -144,6 +148,8 @@ static TrackKernels track_kernels(TrackMode mode, bool small) {
          (const void *)k_track<false, 5, true, true, false>, (const void *)k_track<false, 5, true, true, false>,
          (const void *)k_track<false, 5, true, false, false>}};
     if (small) return {(const void *)k_track_small<true>, (const void *)k_track_small<false>};
+    // (named last, after the small-launch pair: every older instantiation keeps its place)
+    if (mode == TrackMode::P2c) return {(const void *)k_track_p2c<true>, (const void *)k_track_p2c<false>};
     return {by_mode[0][(int)mode], by_mode[1][(int)mode]};
 }
 
@@ -172,14 +178,17 @@ static hcStatus launch_track(const hcTrackArgs *t, const TrackLaunch &l, void *w
     const bool abort_mode = grouped || l.mode == TrackMode::Abort;
     const hcAbortArgs *ab = l.mode == TrackMode::Abort ? l.ab : nullptr;
     const hcGroupedAbortArgs *gr = grouped ? l.gr : nullptr;
+    const hcP2cArgs *pc = l.mode == TrackMode::P2c ? l.p2c : nullptr;
     if (!t || t->sub_ransac_iters < 0) return HC_ERROR_INVALID_VALUE;
     if (grouped && (gr->num_groups < 1 || !gr->groups || !gr->sample_group || !gr->group_found ||
                     !gr->trifocal_sols_batch_index))
         return HC_ERROR_INVALID_VALUE;
     if (!workspace || wsb < ws_bytes_needed()) return HC_ERROR_WORKSPACE;
     if (t->sub_ransac_iters == 0) return HC_SUCCESS;
-    if ((!t->start_sols && !t->start_sols_array) || (!t->tracks && !t->track_array) || !t->start_params ||
-        !t->target_params || !t->diff_params || !t->unified_index || !t->converge || !t->infinity)
+    if ((!t->start_sols && !t->start_sols_array) || (!t->tracks && !t->track_array) || !t->converge || !t->infinity)
+        return HC_ERROR_INVALID_VALUE;
+    // (the P2C launch reads its own tables and coefficient blocks instead)
+    if (!pc && (!t->start_params || !t->target_params || !t->diff_params || !t->unified_index))
         return HC_ERROR_INVALID_VALUE;
     if (t->settings.max_steps < 0 || t->settings.max_corrections < 0 || t->settings.delta_t_inc_steps < 0)
         return HC_ERROR_INVALID_VALUE;
@@ -197,8 +206,9 @@ static hcStatus launch_track(const hcTrackArgs *t, const TrackLaunch &l, void *w
     // abort mode dequeues sample-major, so whole hypotheses finish as early as possible
     k.ordered = abort_mode ? 0 : 1;
     // the archived ablations: PH_CodeOpt tracks without truncation, PH also with the explicit RK helpers
-    k.truncate = (l.mode == TrackMode::PhCodeopt || l.mode == TrackMode::Ph) ? 0 : 1;
-    k.explicit_rk = l.mode == TrackMode::Ph ? 1 : 0;
+    // (the archived P2C kernel is ..._PH's in both)
+    k.truncate = (l.mode == TrackMode::PhCodeopt || l.mode == TrackMode::Ph || pc) ? 0 : 1;
+    k.explicit_rk = (l.mode == TrackMode::Ph || pc) ? 1 : 0;
     k.max_steps = t->settings.max_steps;
     k.max_corr = t->settings.max_corrections;
     k.inc_steps = t->settings.delta_t_inc_steps;
@@ -207,8 +217,9 @@ static hcStatus launch_track(const hcTrackArgs *t, const TrackLaunch &l, void *w
     k.tracks = (cf *)t->tracks;
     k.track_array = (cf *const *)t->track_array;
     k.start_params = (const cf *)t->start_params;
-    k.target_params = (const cf *)t->target_params;
-    k.diff_params = (const cf *)t->diff_params;
+    // P2C: the samples' coefficient blocks take the places of target and diff (hc_track_body.inc)
+    k.target_params = (const cf *)(pc ? pc->coeffs_hx : t->target_params);
+    k.diff_params = (const cf *)(pc ? pc->coeffs_ht : t->diff_params);
     k.conv = t->converge;
     k.inf = t->infinity;
     k.stats = t->stats;
@@ -235,7 +246,7 @@ static hcStatus launch_track(const hcTrackArgs *t, const TrackLaunch &l, void *w
         k.batch_index = ab->trifocal_sols_batch_index;
     }
     const SliceLayout area = slice_layout(paths, t->settings.max_steps);
-    const bool sliced = sliced_launch(abort_mode, t->settings, area, wsb);
+    const bool sliced = !pc && sliced_launch(abort_mode, t->settings, area, wsb);   // (no time slicing for P2C)
     if (sliced) {
         k.ring_cap = (unsigned)area.ring_cap;
         k.rq = (unsigned *)((char *)workspace + area.rq);
@@ -247,11 +258,12 @@ static hcStatus launch_track(const hcTrackArgs *t, const TrackLaunch &l, void *w
     }
     // control block reset, compacted tables (skipped when cached), ring reset
     // (a grouped launch's flags are the caller's group_found words: Workspace::found stays 0, unused)
-    PrepArgs pa{t->unified_index, ws, ab ? ab->found_trifocal_sols : nullptr, ab ? ab->peer_found : nullptr,
+    PrepArgs pa{pc ? pc->hx_index : t->unified_index, ws, ab ? ab->found_trifocal_sols : nullptr, ab ? ab->peer_found : nullptr,
                 k.rq, k.ring, k.ring_cap,
                 sliced ? (unsigned)area.susp_entry0 : 0u,
                 sliced ? (unsigned)area.susp_entry1 : 0u};
-    hipLaunchKernelGGL(k_prep_tables, dim3(1), dim3(PREP_THREADS), 0, s, pa);
+    if (pc) hipLaunchKernelGGL(k_prep_tables_p2c<true>, dim3(1), dim3(PREP_THREADS), 0, s, pa, pc->ht_index);
+    else hipLaunchKernelGGL(k_prep_tables, dim3(1), dim3(PREP_THREADS), 0, s, pa);
     if (launch_status(HC_ERROR_LAUNCH) != HC_SUCCESS) return HC_ERROR_LAUNCH;
     // the twin is enqueued after the specialised kernel: exactly one of the two
     // tracks (EvalTables::lu_struct), the other returns at its first load
@@ -361,6 +373,14 @@ hcStatus hc_trifocal_2op1p_30x30_track_ph(const hcTrackArgs *args, void *workspa
     return hc::launch_track(args, {hc::TrackMode::Ph}, workspace, workspace_bytes, stream);
 }
 
+hcStatus hc_trifocal_2op1p_30x30_track_p2c(const hcTrackArgs *args, const hcP2cArgs *p2c, void *workspace,
+                                           size_t workspace_bytes, hcStream stream) {
+    if (!p2c || !p2c->hx_index || !p2c->ht_index || !p2c->coeffs_hx || !p2c->coeffs_ht) return HC_ERROR_INVALID_VALUE;
+    hc::TrackLaunch l{hc::TrackMode::P2c};
+    l.p2c = p2c;
+    return hc::launch_track(args, l, workspace, workspace_bytes, stream);
+}
+
 hcStatus hc_trifocal_workspace_status(const void *workspace) {
     if (!workspace) return HC_ERROR_INVALID_VALUE;
     hc::Workspace h;
@@ -417,6 +437,27 @@ hcStatus hc_trifocal_eval_batched(int n, const int32_t *unified_index, const hcC
     hipLaunchKernelGGL(hc::k_eval, dim3((n + per - 1) / per), dim3(hc::WG_THREADS), 0, s, n, ws,
                        (const hc::cf *)x, (const hc::cf *)p, (const hc::cf *)d, (hc::cf *)Hx, (hc::cf *)Ht,
                        (hc::cf *)H);
+    return hc::launch_status(HC_ERROR_LAUNCH);
+}
+
+hcStatus hc_trifocal_p2c_eval_batched(int n, const int32_t *hx_index, const int32_t *ht_index, const hcComplex *x,
+                                      const hcComplex *coeffs_hx, const hcComplex *coeffs_ht, const float *t,
+                                      hcComplex *Hx, hcComplex *Ht, hcComplex *H, void *workspace,
+                                      size_t workspace_bytes, hcStream stream) {
+    if (n < 0 || !hx_index || !ht_index || (n > 0 && (!x || !coeffs_hx || !coeffs_ht || !t || !Hx || !Ht || !H)))
+        return HC_ERROR_INVALID_VALUE;
+    if (!workspace || workspace_bytes < hc::ws_bytes_needed()) return HC_ERROR_WORKSPACE;
+    if (n == 0) return HC_SUCCESS;
+    hipStream_t s = (hipStream_t)stream;
+    hc::Workspace *ws = (hc::Workspace *)workspace;
+    (void)hipGetLastError();
+    hc::PrepArgs pa{hx_index, ws, nullptr, nullptr, nullptr, nullptr, 0u, 0u, 0u};
+    hipLaunchKernelGGL(hc::k_prep_tables_p2c<true>, dim3(1), dim3(hc::PREP_THREADS), 0, s, pa, ht_index);
+    if (hc::launch_status(HC_ERROR_LAUNCH) != HC_SUCCESS) return HC_ERROR_LAUNCH;
+    const int per = 2 * hc::WAVES_PER_WG;
+    hipLaunchKernelGGL(hc::k_eval_p2c<true>, dim3((n + per - 1) / per), dim3(hc::WG_THREADS), 0, s, n, ws,
+                       (const hc::cf *)x, (const hc::cf *)coeffs_hx, (const hc::cf *)coeffs_ht, t, (hc::cf *)Hx,
+                       (hc::cf *)Ht, (hc::cf *)H);
     return hc::launch_status(HC_ERROR_LAUNCH);
 }
 

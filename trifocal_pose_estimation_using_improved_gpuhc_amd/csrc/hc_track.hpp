@@ -1,4 +1,4 @@
-// The tracker kernels: four __global__ wrappers around one textually included
+// The tracker kernels: five __global__ wrappers around one textually included
 // body (hc_track_body.inc; DESIGN.md §3 on why it is no function template).
 #pragma once
 
@@ -77,6 +77,7 @@ __global__ void __launch_bounds__(WG_THREADS, MINW) k_track(KArgs a) {
     // until a version that moves the build id anyway
     static_assert(GTAB, "the term tables are read from the workspace");
     constexpr bool GROUPED = false, GATED = false;   // (k_track_grouped, k_track_gated below)
+    constexpr bool P2C = false;                      // (k_track_p2c below)
     // LU (hc_lu.hpp): the abort kernel's time to the first pose is a lone
     // path's latency, so it runs the latency mode (one LDS round trip per pivot
     // step, in batches of HC_LU_LATB_COLS columns); the tracking kernel the
@@ -93,7 +94,7 @@ __global__ void __launch_bounds__(WG_THREADS, MINW) k_track(KArgs a) {
 // HC_SMALL_MINW waves/SIMD and HC_SMALL_LAT columns per LU batch (above).
 template <bool LUS>
 __global__ void __launch_bounds__(WG_THREADS, HC_SMALL_MINW) k_track_small(KArgs a) {
-    constexpr bool ABORT = false, ARCH = false, GROUPED = false, GATED = false;
+    constexpr bool ABORT = false, ARCH = false, GROUPED = false, GATED = false, P2C = false;
     constexpr int LULAT = HC_SMALL_LAT;
 #include "hc_track_body.inc"
 }
@@ -107,7 +108,7 @@ __global__ void __launch_bounds__(WG_THREADS, HC_SMALL_MINW) k_track_small(KArgs
 // instantiations keep their code and their names in kernel traces.
 template <bool LUS>
 __global__ void __launch_bounds__(WG_THREADS, HC_ABORT_MINW) k_track_grouped(KArgs a) {
-    constexpr bool ABORT = true, ARCH = false, GROUPED = true, GATED = false;
+    constexpr bool ABORT = true, ARCH = false, GROUPED = true, GATED = false, P2C = false;
     constexpr int LULAT = HC_LU_LATB_COLS;
 #include "hc_track_body.inc"
 }
@@ -119,8 +120,28 @@ __global__ void __launch_bounds__(WG_THREADS, HC_ABORT_MINW) k_track_grouped(KAr
 // of its own, so the grouped instantiations keep their code.
 template <bool LUS>
 __global__ void __launch_bounds__(WG_THREADS, HC_ABORT_MINW) k_track_gated(KArgs a) {
-    constexpr bool ABORT = true, ARCH = false, GROUPED = true, GATED = true;
+    constexpr bool ABORT = true, ARCH = false, GROUPED = true, GATED = true, P2C = false;
     constexpr int LULAT = HC_LU_LATB_COLS;
+#include "hc_track_body.inc"
+}
+
+// The archived parameter-to-coefficient tracker (include/p2c/hc_trifocal_p2c.h;
+// kernel_GPUHC_trifocal_pose_P2C, arxived ..._P2C.cu:56-263): the archived ..._PH
+// instantiation's body and configuration (k_track<false, 5, true, true>: ARCH,
+// launched with truncate = 0 and explicit_rk = 1, throughput LU, 5 waves/SIMD)
+// with P2C on, which starts a path at a step of 0.05 and builds the slot's
+// prefix tables from the sample's coefficient blocks, interpolated at the
+// slot's t (hc_eval.hpp build_prefixes_p2c), instead of from p(t).  The
+// archived kernel's other differences from ..._PH follow from that: its clamp
+// 1 - 0.05 - t0 is PH's 0.95 - t0 in double, its third stage keeps the second's
+// coefficients (the same t), and its corrector evaluates H from the Hx
+// coefficients of the fourth stage (tp at the step's last t).  No time slicing
+// and no small-launch variant.  Again a kernel of its own, so the existing
+// instantiations keep their code.
+template <bool LUS>
+__global__ void __launch_bounds__(WG_THREADS, 5) k_track_p2c(KArgs a) {
+    constexpr bool ABORT = false, ARCH = true, GROUPED = false, GATED = false, P2C = true;
+    constexpr int LULAT = 0;
 #include "hc_track_body.inc"
 }
 

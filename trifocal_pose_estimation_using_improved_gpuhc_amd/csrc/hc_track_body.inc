@@ -1,9 +1,11 @@
-// The body of the tracker kernels k_track, k_track_small, k_track_grouped and k_track_gated (hc_track.hpp),
-// included inside each: ABORT, GROUPED, GATED, ARCH, LUS and LULAT are their
+// The body of the tracker kernels k_track, k_track_small, k_track_grouped, k_track_gated and
+// k_track_p2c (hc_track.hpp),
+// included inside each: ABORT, GROUPED, GATED, P2C, ARCH, LUS and LULAT are their
 // template parameters or constants, `a` their argument block.  GATED
-// (k_track_gated) replaces the scoring block of PH_FINISH and nothing else.
+// (k_track_gated) replaces the scoring block of PH_FINISH and nothing else; P2C
+// (k_track_p2c) the source of the prefix tables and the first step size.
 // Included textually on purpose (DESIGN.md §3.2): a change here is a codegen
-// change of all twelve instantiations.  The other names it takes from its
+// change of all fourteen instantiations.  The other names it takes from its
 // surroundings:
 //   hc_layout.hpp  KArgs, Workspace, WG_THREADS, WAVES_PER_WG, PRIO_TENTHS,
 //                  path_of_queue_pos, SLICE_Q, SLICE_QBIG, SUSP_WORDS, RQ_*
@@ -35,7 +37,9 @@
     const uint2 *s_ht = T->ht;
     const uint32_t *s_hx = T->hx;
     const uint32_t *s_hxd = &T->hxd[0][0];
-    if (threadIdx.x < NPP) s_sp[threadIdx.x] = a.start_params[threadIdx.x];
+    // (P2C, k_track_p2c: no parameters; a.target_params / a.diff_params are the
+    // samples' coefficient blocks, 38 x 3 and 38 x 2 each)
+    if (!P2C && threadIdx.x < NPP) s_sp[threadIdx.x] = a.start_params[threadIdx.x];
     {
         float *z = reinterpret_cast<float *>(s_slot);
         for (int i = threadIdx.x; i < (int)(sizeof(s_slot) / 4); i += WG_THREADS) z[i] = 0.0f;
@@ -267,7 +271,7 @@
                         x = rl ? dtrack[r] : cmk(0.0f, 0.0f);                 // :101-103
                         sols = rl ? dstart[r] : cmk(0.0f, 0.0f);
                         xl = x;
-                        t0 = 0.0f; t_step = 0.0f; dt = 0.01f;                 // :80
+                        t0 = 0.0f; t_step = 0.0f; dt = P2C ? 0.05f : 0.01f;   // :80 (..._P2C.cu:75)
                         end_zone = false; check = !ARCH || a.truncate != 0; isSucc = false; isInf = false;
                         succ = 0; nsteps = 0; ncorr = 0; stepidx = 0; piece = 0;
                         k1v = false;
@@ -489,7 +493,14 @@
 #endif
             const int rs = lane_fresh() & 31;   // == r; the LDS addresses are not hoisted and held across the loop
             const size_t so = (size_t)(smp_loaded > 0 ? smp_loaded : 0) * NPP;
-            build_prefixes(S, rs, &T->pre[0][0], a.target_params + so, a.diff_params + so, s_sp, t0);
+            if constexpr (P2C) {
+                // the coefficients at the slot's t (..._P2C.cu:133, :147, :172; its third stage
+                // and its corrector keep the last ones, which are this t's: no rebuild there)
+                const size_t sk = (size_t)(smp_loaded > 0 ? smp_loaded : 0) * P2C_NK;
+                build_prefixes_p2c(S, rs, &T->pre[0][0], a.target_params + sk * 3, a.diff_params + sk * 2, t0);
+            } else {
+                build_prefixes(S, rs, &T->pre[0][0], a.target_params + so, a.diff_params + so, s_sp, t0);
+            }
         }
         wave_lds_sync();
         const int s_in = s, ph_in = ph;

@@ -98,6 +98,8 @@ class DeviceTracker:
         self.workspace = torch.zeros(self.ws_bytes, dtype=torch.uint8, device=dev)
         self.edgels = None
         self.K = None
+        self._problem = problem       # track_p2c: the PH tables and the start parameters on the host
+        self._p2c_default = None      # track_p2c: (device tables, map) of p2c.tables_from_ph, made on first use
 
     def set_ransac_data(self, data: RansacData):
         self.edgels = torch.from_numpy(np.ascontiguousarray(data.locations)).to(self.device)
@@ -355,6 +357,75 @@ class DeviceTracker:
         self.reset_tracks(r)
         self.launch(tgt, dif, r, abort=abort, inflight_stop=inflight_stop, truncate=truncate, explicit_rk=explicit_rk,
                     time_slicing=time_slicing)
+        torch.cuda.synchronize(self.device)
+        self.workspace_status()
+        return r
+
+    def launch_p2c(self, tables, coeffs_hx: torch.Tensor, coeffs_ht: torch.Tensor, r: TrackResult,
+                   stream: torch.cuda.Stream | None = None, workspace: torch.Tensor | None = None,
+                   num_samples: int | None = None) -> None:
+        """Enqueue one run of the archived P2C tracker on `stream` (no
+        synchronisation): hc_trifocal_2op1p_30x30_track_p2c over the first
+        num_samples samples (default: all) of the coefficient blocks coeffs_hx
+        (N, 38, 3, 2) and coeffs_ht (N, 38, 2, 2) into r.  tables: the device
+        tensors (hx_index, ht_index) of the P2C index tables (p2c_tables)."""
+        hx, ht = tables
+        if num_samples is None:
+            num_samples = coeffs_hx.shape[0]
+        if num_samples < 0 or num_samples > coeffs_hx.shape[0] or num_samples > coeffs_ht.shape[0] or \
+                num_samples * 312 > r.tracks.shape[0]:
+            raise _abi.HCError("sample range outside the buffers")
+        if hx.numel() != 28800 or ht.numel() != 2400 or hx.dtype != torch.int32 or ht.dtype != torch.int32:
+            raise _abi.HCError("P2C tables: 28800 and 2400 int32 values")
+        if tuple(coeffs_hx.shape[1:]) != (38, 3, 2) or tuple(coeffs_ht.shape[1:]) != (38, 2, 2) or \
+                coeffs_hx.dtype != torch.float32 or coeffs_ht.dtype != torch.float32 or \
+                not coeffs_hx.is_contiguous() or not coeffs_ht.is_contiguous():
+            raise _abi.HCError("P2C coefficient blocks: contiguous float32 (N, 38, 3, 2) and (N, 38, 2, 2)")
+        ws_t = self._workspace(workspace)
+        a = _abi.hcTrackArgs()
+        a.sub_ransac_iters = num_samples
+        a.settings = self.settings
+        a.start_sols = self.start_sols.data_ptr()
+        a.tracks = r.tracks.data_ptr()
+        a.converge = r.converge.data_ptr()
+        a.infinity = r.infinity.data_ptr()
+        a.stats = r.stats.data_ptr() if r.stats is not None else None
+        pa = _abi.hcP2cArgs(hx.data_ptr(), ht.data_ptr(), coeffs_hx.data_ptr(), coeffs_ht.data_ptr())
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        _abi.call("hc_trifocal_2op1p_30x30_track_p2c", C.byref(a), C.byref(pa), _abi.ptr(ws_t), self.ws_bytes,
+                  _abi.ptr(s))
+
+    def p2c_tables(self, tables):
+        """(hx_index, ht_index) host arrays -> the device tensors launch_p2c takes."""
+        hx, ht = tables
+        return (torch.from_numpy(np.ascontiguousarray(hx, np.int32).reshape(-1)).to(self.device),
+                torch.from_numpy(np.ascontiguousarray(ht, np.int32).reshape(-1)).to(self.device))
+
+    def track_p2c(self, target: np.ndarray, diff: np.ndarray, tables=None, coeff_map=None,
+                  stats: bool = True) -> TrackResult:
+        """Synchronous convenience wrapper of the archived P2C tracker: the
+        samples' coefficient blocks from diff (p2c.coefficients, on the host),
+        H2D, reset tracks, launch_p2c, sync, status check.  tables: the P2C
+        index tables (hx_index, ht_index) with their coeff_map (38, 2)
+        (p2c.derive_coeff_map); by default those p2c.tables_from_ph makes of the
+        problem's PH tables.  target is not read (diff = target - start)."""
+        from . import p2c
+        if tables is None:
+            if self._p2c_default is None:
+                hx, ht, m = p2c.tables_from_ph(self._problem)
+                self._p2c_default = (self.p2c_tables((hx, ht)), m)
+            dev_tables, default_map = self._p2c_default
+            if coeff_map is None:
+                coeff_map = default_map
+        else:
+            if coeff_map is None:
+                coeff_map = p2c.derive_coeff_map(self._problem, tables[0], tables[1])
+            dev_tables = self.p2c_tables(tables)
+        chx, cht = p2c.coefficients(coeff_map, self._problem.start_params, diff)
+        chx_t, cht_t = torch.from_numpy(chx).to(self.device), torch.from_numpy(cht).to(self.device)
+        r = self.allocate(chx.shape[0], stats=stats)
+        self.reset_tracks(r)
+        self.launch_p2c(dev_tables, chx_t, cht_t, r)
         torch.cuda.synchronize(self.device)
         self.workspace_status()
         return r
