@@ -19,6 +19,8 @@
 #   stress    time slicing under concurrent streams (scripts/slice_stress.py: 4 cold, 4 warm, 8 cold)
 #   multi     T sequential single-triplet runs against one grouped run (scripts/multi_triplet.py) -> TAG_multi.json
 #   joint     per-view against joint pose selection, config-5 protocol (scripts/joint_pose.py [TRIALS [REPS]]) -> TAG_joint.json
+#   refine    the joint selection against the same selection refined on its inliers, config-5 protocol
+#             (scripts/refine_pose.py [TRIALS [REPS]]) -> TAG_refine.json
 #   gated     the gated abort launch against plain tracking + joint selection, config-5 protocol
 #             (scripts/gated_stop.py [TRIALS]) -> TAG_gated.json
 #   gated_ab  the launches that existed before the gated one (scripts/gated_stop.py --existing) on builds
@@ -104,6 +106,7 @@ for k,v in sorted(g.items()): print(k, v)" ;;
     phases) HC_TRIFOCAL_LIB=$L/libhc_trifocal_phases.so run phases 300 python scripts/diag_phases.py > $O/${T}_phases.json; rc=$?; cat $O/${T}_phases.json ;;
     multi) run multi 300 python scripts/multi_triplet.py "$@" > $O/${T}_multi.json; rc=$?; cat $O/${T}_multi.json ;;
     joint) run joint 600 python scripts/joint_pose.py "$@" > $O/${T}_joint.json; rc=$?; cat $O/${T}_joint.json ;;
+    refine) run refine 600 python scripts/refine_pose.py "$@" > $O/${T}_refine.json; rc=$?; tail -c 1500 $O/${T}_refine.json ;;
     gated) run gated 900 python scripts/gated_stop.py "$@" > $O/${T}_gated.json; rc=$?; tail -c 600 $O/${T}_gated.json ;;
     p2c) run p2c 300 python scripts/ablation_p2c.py --out $O/${T}_ablation_p2c.json "$@"; rc=$? ;;
     gated_ab)

@@ -8,7 +8,9 @@ The boundary is described once: the ctypes mirrors of the argument structs and
 SIGNATURES, one (name, restype, argtypes, optional) entry per declared function.
 lib() binds the table, DECLARED_SYMBOLS is its names, and tests/test_abi_host.py
 holds both against the headers (layouts through the C compiler, signatures
-against the prototypes).  Callers go through two helpers: ptr(x), the c_void_p
+against the prototypes).  The two headers in directories of their own
+(include/p2c, include/refine) have tables of their own, P2C_SIGNATURES and
+REFINE_SIGNATURES, checked the same way.  Callers go through two helpers: ptr(x), the c_void_p
 of a tensor, array or stream, and call(name, *args), which raises HCError on a
 status other than HC_SUCCESS.
 """
@@ -132,6 +134,25 @@ class hcIpcHandle(C.Structure):
     _fields_ = [("reserved", C.c_ubyte * 64)]
 
 
+HC_REFINE_MAX_ITERATIONS = 32
+HC_REFINE_NONE, HC_REFINE_TOO_FEW, HC_REFINE_SINGULAR = 1, 2, 4
+
+
+class hcRefineSettings(C.Structure):
+    """include/refine/hc_pose_refine.h: 16 bytes; 0 selects a default (10 iterations, 16 inliers)"""
+    _fields_ = [("iterations", C.c_int32), ("min_inliers", C.c_int32), ("pad", C.c_int32 * 2)]
+
+
+class hcRefineReport(C.Structure):
+    """include/refine/hc_pose_refine.h: what one refinement did, 176 bytes"""
+    _fields_ = [("status", C.c_int32), ("iterations_run", C.c_int32), ("best_iteration", C.c_int32),
+                ("joint_history", C.c_int32 * (HC_REFINE_MAX_ITERATIONS + 1)),
+                ("rms_px_in", C.c_double * 2), ("rms_px_out", C.c_double * 2)]
+
+
+REFINE_REPORT_BYTES = C.sizeof(hcRefineReport)   # 176
+
+
 # One entry per function of include/*.h: restype and argtypes as the prototype
 # reads (None for void; c_void_p for device and host buffers and for hcStream,
 # POINTER(struct) for the argument structs, c_char_p for paths).  optional: a
@@ -216,6 +237,16 @@ P2C_SIGNATURES = (
 )
 P2C_DECLARED_SYMBOLS = tuple(s.name for s in P2C_SIGNATURES)
 
+# include/refine/hc_pose_refine.h, the pose refinement's header beside
+# include/hc_pose.h: its table, bound and checked the same way
+# (tests/test_refine_host.py)
+_RS = C.POINTER(hcRefineSettings)
+REFINE_SIGNATURES = (
+    Sig("hc_trifocal_pose_refine", _ST, (_p, _i, _p, _p, _RS, _p, _p, _p), True),
+    Sig("hc_trifocal_pose_refine_grouped", _ST, (_i, _p, _p, _RS, _p, _p, _p), True),
+)
+REFINE_DECLARED_SYMBOLS = tuple(s.name for s in REFINE_SIGNATURES)
+
 _lib = None
 
 
@@ -231,7 +262,7 @@ def lib() -> C.CDLL:
         # instead of pulling a second HIP/HSA runtime from /opt/rocm.
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
-        for s in SIGNATURES + P2C_SIGNATURES:
+        for s in SIGNATURES + P2C_SIGNATURES + REFINE_SIGNATURES:
             fn = getattr(L, s.name, None)
             if fn is None:
                 if s.optional:

@@ -26,9 +26,12 @@
 // the candidate filter, make_pose and the edgel loop exist once, so a path's
 // counts and pose bits are the same in every form.  k_pose_inlier_mask lists a
 // joint selection's inlier edgels as a bit mask, through the same edgel_views.
+// k_pose_refine<GROUPED> (include/refine/hc_pose_refine.h, described where it
+// is defined below) refines a joint selection on the edgels edgel_views accepts.
 #include <type_traits>
 
 #include "../../include/hc_pose.h"
+#include "../../include/refine/hc_pose_refine.h"
 #include "hc_device.hpp"
 #include "hc_pose_device.hpp"   // make_pose, reproj_inlier, edgel_views, is_candidate: shared with the gated tracker
 
@@ -275,6 +278,354 @@ hcStatus pose_support_grouped(int num_paths, const hcComplex *tracks, const uint
     return launch_pose_support<JOINT, true>(a, stream);
 }
 
+// ---- refinement of a joint selection (include/refine/hc_pose_refine.h) ------
+//
+// k_pose_refine<GROUPED>: one workgroup of 256 threads per selection, the whole
+// Gauss-Newton loop in one launch.  An iterate is one pass over the edgels:
+// thread i takes edgels i, i + 256, ..., scores each with edgel_views on the
+// state rounded to float (the bits k_pose_inlier_mask and the support kernel
+// test) and, for a joint inlier, adds the residual and its 2x5 Jacobian of both
+// views, in double at the double state, to its 2 x (15 + 5 + 1) sums.  The sums
+// go through a butterfly over the wave's lanes, then through LDS over the four
+// waves as (w0 + w1) + (w2 + w3): a fixed tree, no floating-point atomics.
+// Lanes 0 and 1 solve the two 5x5 systems and write the new state to LDS, from
+// where every thread reads it.  Nothing waits on another workgroup.
+constexpr int RF_THREADS = 256, RF_WAVES = RF_THREADS / WAVE;
+constexpr int RF_SYS = 21;   // per view: the 15 upper entries of A = sum J'J, the 5 of g = sum J'r, sum r'r
+
+struct RefineArgs {
+    const hcTrifocalSelection *in;
+    hcTrifocalSelection *out;   // may be in
+    hcRefineReport *rep;        // or nullptr
+    int E;                      // the scene, or with GROUPED that of groups[blockIdx.x]
+    const float *loc;
+    const float *K;
+    const hcTripletGroup *groups;
+    int iterations, min_inliers;
+};
+
+__device__ __forceinline__ double wave_sum_d(double v) {
+    v += __shfl_xor(v, 32);
+    v += __shfl_xor(v, 16);
+    v += __shfl_xor(v, 8);
+    v += __shfl_xor(v, 4);
+    v += __shfl_xor(v, 2);
+    v += __shfl_xor(v, 1);
+    return v;   // the same bits in every lane: each step adds the same pair on both sides
+}
+
+// b[0..2] = b1 = normalize(t x e_i), i the axis of smallest |t_i| (the lowest on a tie); b[3..5] = b2 = t x b1
+__device__ __forceinline__ void tangent_basis(const double *t, double *b) {
+    int i = 0;
+    double m = __builtin_fabs(t[0]);
+    if (__builtin_fabs(t[1]) < m) { i = 1; m = __builtin_fabs(t[1]); }
+    if (__builtin_fabs(t[2]) < m) i = 2;
+    b[0] = i == 0 ? 0.0 : (i == 1 ? -t[2] : t[1]);
+    b[1] = i == 0 ? t[2] : (i == 1 ? 0.0 : -t[0]);
+    b[2] = i == 0 ? -t[1] : (i == 1 ? t[0] : 0.0);
+    const double n = __builtin_sqrt((b[0] * b[0] + b[1] * b[1]) + b[2] * b[2]);
+    b[0] /= n; b[1] /= n; b[2] /= n;
+    b[3] = t[1] * b[2] - t[2] * b[1];
+    b[4] = t[2] * b[0] - t[0] * b[2];
+    b[5] = t[0] * b[1] - t[1] * b[0];
+}
+
+// One view of one edgel: reproj_inlier's m - p in double, its derivative along
+// the five local directions (w = e0, e1, e2 with dR = [w]x R; dt = b1, b2), and
+// the sums.  c = R e3, a = c.h, m = R g, rho = (t2 a - c.t) / (1 - m2 a), q = m rho + t.
+__device__ __forceinline__ void view_accumulate(double g0, double g1, double h0, double h1, const double *R,
+                                                const double *t, const double *b, double K0, double K2, double K4,
+                                                double K5, double *acc) {
+    const double c[3] = {R[2], R[5], R[8]};
+    const double a = (c[0] * h0 + c[1] * h1) + c[2];
+    const double ct = (c[0] * t[0] + c[1] * t[1]) + c[2] * t[2];
+    const double m[3] = {(R[0] * g0 + R[1] * g1) + R[2], (R[3] * g0 + R[4] * g1) + R[5], (R[6] * g0 + R[7] * g1) + R[8]};
+    const double den = 1.0 - m[2] * a;
+    const double rho = (t[2] * a - ct) / den;
+    const double q[3] = {m[0] * rho + t[0], m[1] * rho + t[1], m[2] * rho + t[2]};
+    const double x = q[0] / q[2], y = q[1] / q[2];
+    const double r0 = (x * K0 + K2) - (h0 * K0 + K2), r1 = (y * K4 + K5) - (h1 * K4 + K5);
+    const double iden = 1.0 / den, iq2 = 1.0 / q[2];   // the derivatives multiply by the reciprocals: 5 divisions, not 18
+    double J0[5], J1[5];
+#pragma unroll
+    for (int d = 0; d < 5; d++) {
+        double dc[3] = {0.0, 0.0, 0.0}, dm[3] = {0.0, 0.0, 0.0}, dt[3] = {0.0, 0.0, 0.0};
+        if (d == 0) { dc[1] = -c[2]; dc[2] = c[1]; dm[1] = -m[2]; dm[2] = m[1]; }        // e0 x v = (0, -v2, v1)
+        else if (d == 1) { dc[0] = c[2]; dc[2] = -c[0]; dm[0] = m[2]; dm[2] = -m[0]; }   // e1 x v = (v2, 0, -v0)
+        else if (d == 2) { dc[0] = -c[1]; dc[1] = c[0]; dm[0] = -m[1]; dm[1] = m[0]; }   // e2 x v = (-v1, v0, 0)
+        else { dt[0] = b[3 * (d - 3)]; dt[1] = b[3 * (d - 3) + 1]; dt[2] = b[3 * (d - 3) + 2]; }
+        const double da = (dc[0] * h0 + dc[1] * h1) + dc[2];
+        const double dct = ((dc[0] * t[0] + dc[1] * t[1]) + dc[2] * t[2]) + ((c[0] * dt[0] + c[1] * dt[1]) + c[2] * dt[2]);
+        const double dnum = (dt[2] * a + t[2] * da) - dct;
+        const double dden = -(dm[2] * a + m[2] * da);
+        const double drho = (dnum - rho * dden) * iden;
+        const double dq0 = (dm[0] * rho + m[0] * drho) + dt[0];
+        const double dq1 = (dm[1] * rho + m[1] * drho) + dt[1];
+        const double dq2 = (dm[2] * rho + m[2] * drho) + dt[2];
+        J0[d] = K0 * ((dq0 - x * dq2) * iq2);
+        J1[d] = K4 * ((dq1 - y * dq2) * iq2);
+    }
+    int n = 0;
+#pragma unroll
+    for (int i = 0; i < 5; i++)
+#pragma unroll
+        for (int j = i; j < 5; j++) acc[n++] += J0[i] * J0[j] + J1[i] * J1[j];
+#pragma unroll
+    for (int i = 0; i < 5; i++) acc[15 + i] += J0[i] * r0 + J1[i] * r1;
+    acc[20] += r0 * r0 + r1 * r1;
+}
+
+// (A + 1e-9 diag A) d = -g by Cholesky, s = one view's sums; false when a pivot
+// is not positive or a value is not finite
+__device__ __forceinline__ bool refine_solve(const double *s, double *d) {
+    double M[5][5], L[5][5];
+    int n = 0;
+#pragma unroll
+    for (int i = 0; i < 5; i++)
+#pragma unroll
+        for (int j = i; j < 5; j++) { M[i][j] = M[j][i] = s[n]; n++; }
+    bool ok = true;
+#pragma unroll
+    for (int i = 0; i < 5; i++) {
+        M[i][i] = M[i][i] + 1e-9 * M[i][i];
+        ok = ok && __builtin_isfinite(s[15 + i]);
+#pragma unroll
+        for (int j = 0; j < 5; j++) ok = ok && __builtin_isfinite(M[i][j]);
+    }
+#pragma unroll
+    for (int j = 0; j < 5; j++) {
+        double p = M[j][j];
+#pragma unroll
+        for (int k = 0; k < j; k++) p -= L[j][k] * L[j][k];
+        ok = ok && p > 0.0;
+        L[j][j] = __builtin_sqrt(p);
+#pragma unroll
+        for (int i = j + 1; i < 5; i++) {
+            double v = M[i][j];
+#pragma unroll
+            for (int k = 0; k < j; k++) v -= L[i][k] * L[j][k];
+            L[i][j] = v / L[j][j];
+        }
+    }
+    double y[5];
+#pragma unroll
+    for (int i = 0; i < 5; i++) {
+        double v = -s[15 + i];
+#pragma unroll
+        for (int k = 0; k < i; k++) v -= L[i][k] * y[k];
+        y[i] = v / L[i][i];
+    }
+#pragma unroll
+    for (int i = 4; i >= 0; i--) {
+        double v = y[i];
+#pragma unroll
+        for (int k = i + 1; k < 5; k++) v -= L[k][i] * d[k];
+        d[i] = v / L[i][i];
+        ok = ok && __builtin_isfinite(d[i]);
+    }
+    return ok;
+}
+
+// st = R (9, row-major) | t (3) of one view in LDS: R <- Exp(w) R by Rodrigues'
+// formula, column by column; t <- normalize(t + u0 b1 + u1 b2).  d = (w, u).
+__device__ __forceinline__ void refine_apply(double *st, const double *d) {
+    const double th2 = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2];
+    double A = 1.0 - th2 / 6.0, B = 0.5 - th2 / 24.0;
+    if (th2 >= 1e-16) {
+        const double th = __builtin_sqrt(th2), sh = sin(0.5 * th);
+        A = sin(th) / th;
+        B = 2.0 * sh * sh / th2;
+    }
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+        const double c0 = st[j], c1 = st[3 + j], c2 = st[6 + j];
+        const double w0 = d[1] * c2 - d[2] * c1, w1 = d[2] * c0 - d[0] * c2, w2 = d[0] * c1 - d[1] * c0;   // w x c
+        const double v0 = d[1] * w2 - d[2] * w1, v1 = d[2] * w0 - d[0] * w2, v2 = d[0] * w1 - d[1] * w0;   // w x (w x c)
+        st[j] = c0 + (A * w0 + B * v0);
+        st[3 + j] = c1 + (A * w1 + B * v1);
+        st[6 + j] = c2 + (A * w2 + B * v2);
+    }
+    double t[3] = {st[9], st[10], st[11]}, b[6];
+    tangent_basis(t, b);
+#pragma unroll
+    for (int i = 0; i < 3; i++) t[i] = t[i] + (d[3] * b[i] + d[4] * b[3 + i]);
+    const double n = __builtin_sqrt((t[0] * t[0] + t[1] * t[1]) + t[2] * t[2]);
+#pragma unroll
+    for (int i = 0; i < 3; i++) st[9 + i] = t[i] / n;
+}
+
+template <bool GROUPED>
+__global__ void __launch_bounds__(RF_THREADS) k_pose_refine(const RefineArgs a) {
+    __shared__ double s_sum[RF_WAVES][2 * RF_SYS];
+    __shared__ double s_state[2][12];   // per view R | t, the double state
+    __shared__ float s_best[24];        // the best iterate's scored floats: R21 | t21 | R31 | t31
+    __shared__ int s_cnt[RF_WAVES][3];
+    __shared__ int s_singular;
+    const int tid = threadIdx.x, lane = lane_id(), wave = tid / WAVE, sel = blockIdx.x;
+    Scene sc;
+    if constexpr (GROUPED) {
+        const hcTripletGroup g = a.groups[sel];
+        sc = load_scene(g.num_edgels, g.locations, g.K);
+    } else {
+        sc = load_scene(a.E, a.loc, a.K);
+    }
+    // every thread reads the input here, before the first barrier; thread 0
+    // writes the output after the last one (out may be in)
+    const hcTrifocalSelection keep = a.in[sel];
+    hcRefineReport *rep = a.rep ? a.rep + sel : nullptr;
+    if (keep.path < 0) {
+        if (tid == 0) {
+            a.out[sel] = keep;
+            if (rep) {
+                rep->status = HC_REFINE_NONE;
+                rep->iterations_run = rep->best_iteration = 0;
+                for (int i = 0; i <= HC_REFINE_MAX_ITERATIONS; i++) rep->joint_history[i] = -1;
+                rep->rms_px_in[0] = rep->rms_px_in[1] = rep->rms_px_out[0] = rep->rms_px_out[1] = 0.0;
+            }
+        }
+        return;
+    }
+    if (tid == 0) {
+#pragma unroll
+        for (int i = 0; i < 9; i++) { s_state[0][i] = (double)keep.R21[i]; s_state[1][i] = (double)keep.R31[i]; }
+#pragma unroll
+        for (int i = 0; i < 3; i++) { s_state[0][9 + i] = (double)keep.t21[i]; s_state[1][9 + i] = (double)keep.t31[i]; }
+    }
+    __syncthreads();
+    const double K0 = (double)sc.K0, K2 = (double)sc.K2, K4 = (double)sc.K4, K5 = (double)sc.K5;
+    int status = 0, k = 0, bestJ = -1, best21 = 0, best31 = 0, bestK = 0;
+    double rms_in[2] = {0.0, 0.0}, rms_out[2] = {0.0, 0.0};
+    for (;;) {
+        double R[18], T[6], B[12];
+        float Rf[18], Tf[6];
+#pragma unroll
+        for (int i = 0; i < 9; i++) { R[i] = s_state[0][i]; R[9 + i] = s_state[1][i]; }
+#pragma unroll
+        for (int i = 0; i < 3; i++) { T[i] = s_state[0][9 + i]; T[3 + i] = s_state[1][9 + i]; }
+#pragma unroll
+        for (int i = 0; i < 18; i++) Rf[i] = (float)R[i];
+#pragma unroll
+        for (int i = 0; i < 6; i++) Tf[i] = (float)T[i];
+        tangent_basis(T, B);
+        tangent_basis(T + 3, B + 6);
+        double acc[2 * RF_SYS];
+#pragma unroll
+        for (int i = 0; i < 2 * RF_SYS; i++) acc[i] = 0.0;
+        int c21 = 0, c31 = 0, cJ = 0;
+        for (int e = tid; e < sc.E; e += RF_THREADS) {
+            bool in21, in31;
+            edgel_views(sc, e, Rf, Tf, Rf + 9, Tf + 3, in21, in31);
+            c21 += in21 ? 1 : 0;
+            c31 += in31 ? 1 : 0;
+            if (in21 && in31) {
+                cJ++;
+                const float *p = sc.loc + (size_t)e * 6;
+                const double g0 = (double)p[0], g1 = (double)p[1];
+                view_accumulate(g0, g1, (double)p[2], (double)p[3], R, T, B, K0, K2, K4, K5, acc);
+                view_accumulate(g0, g1, (double)p[4], (double)p[5], R + 9, T + 3, B + 6, K0, K2, K4, K5, acc + RF_SYS);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 2 * RF_SYS; i++) acc[i] = wave_sum_d(acc[i]);
+        c21 = wave_sum_i(c21);
+        c31 = wave_sum_i(c31);
+        cJ = wave_sum_i(cJ);
+        if (lane == 0) {
+#pragma unroll
+            for (int i = 0; i < 2 * RF_SYS; i++) s_sum[wave][i] = acc[i];
+            s_cnt[wave][0] = cJ;
+            s_cnt[wave][1] = c21;
+            s_cnt[wave][2] = c31;
+        }
+        __syncthreads();
+        // the totals, the same in every thread
+        cJ = (s_cnt[0][0] + s_cnt[1][0]) + (s_cnt[2][0] + s_cnt[3][0]);
+        c21 = (s_cnt[0][1] + s_cnt[1][1]) + (s_cnt[2][1] + s_cnt[3][1]);
+        c31 = (s_cnt[0][2] + s_cnt[1][2]) + (s_cnt[2][2] + s_cnt[3][2]);
+        double rms[2];
+#pragma unroll
+        for (int v = 0; v < 2; v++) {
+            const int i = v * RF_SYS + 20;
+            const double sse = (s_sum[0][i] + s_sum[1][i]) + (s_sum[2][i] + s_sum[3][i]);
+            rms[v] = cJ > 0 ? __builtin_sqrt(sse / (double)cJ) : 0.0;
+        }
+        if (k == 0) { rms_in[0] = rms[0]; rms_in[1] = rms[1]; }
+        if (tid == 0 && rep) rep->joint_history[k] = cJ;
+        if (cJ >= bestJ) {   // a tie goes to the later iterate
+            bestJ = cJ; best21 = c21; best31 = c31; bestK = k;
+            rms_out[0] = rms[0]; rms_out[1] = rms[1];
+            if (tid == 0) {
+#pragma unroll
+                for (int i = 0; i < 9; i++) { s_best[i] = Rf[i]; s_best[12 + i] = Rf[9 + i]; }
+#pragma unroll
+                for (int i = 0; i < 3; i++) { s_best[9 + i] = Tf[i]; s_best[21 + i] = Tf[3 + i]; }
+            }
+        }
+        if (cJ < a.min_inliers) { status |= HC_REFINE_TOO_FEW; break; }
+        if (k == a.iterations) break;
+        if (wave == 0) {
+            bool ok = true;
+            double d[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+            if (lane < 2) {
+                double s[RF_SYS];
+#pragma unroll
+                for (int i = 0; i < RF_SYS; i++) {
+                    const int j = lane * RF_SYS + i;
+                    s[i] = (s_sum[0][j] + s_sum[1][j]) + (s_sum[2][j] + s_sum[3][j]);
+                }
+                ok = refine_solve(s, d);
+            }
+            const bool bad = __ballot(!ok) != 0;
+            if (lane == 0) s_singular = bad ? 1 : 0;
+            if (!bad && lane < 2) refine_apply(s_state[lane], d);
+        }
+        __syncthreads();
+        if (s_singular) { status |= HC_REFINE_SINGULAR; break; }
+        k++;
+    }
+    if (tid != 0) return;
+    hcTrifocalSelection o = keep;
+    if (bestJ >= a.min_inliers || bestK > 0) {   // otherwise iterate 0 had too few: the input, unchanged
+        o.inliers = bestJ;
+        o.inliers21 = best21;
+        o.inliers31 = best31;
+        o.key = ((uint64_t)(uint32_t)bestJ << 32) | (uint32_t)keep.path;
+#pragma unroll
+        for (int i = 0; i < 9; i++) { o.R21[i] = s_best[i]; o.R31[i] = s_best[12 + i]; }
+#pragma unroll
+        for (int i = 0; i < 3; i++) { o.t21[i] = s_best[9 + i]; o.t31[i] = s_best[21 + i]; }
+    }
+    a.out[sel] = o;
+    if (rep) {
+        rep->status = status;
+        rep->iterations_run = k;
+        rep->best_iteration = bestK;
+        for (int i = k + 1; i <= HC_REFINE_MAX_ITERATIONS; i++) rep->joint_history[i] = -1;
+        rep->rms_px_in[0] = rms_in[0]; rep->rms_px_in[1] = rms_in[1];
+        rep->rms_px_out[0] = rms_out[0]; rep->rms_px_out[1] = rms_out[1];
+    }
+}
+
+// settings (a host pointer or nullptr) -> the values the kernel runs with; false when out of range
+inline bool refine_settings(const hcRefineSettings *s, int &iterations, int &min_inliers) {
+    iterations = 10;
+    min_inliers = 16;
+    if (!s) return true;
+    if (s->iterations < 0 || s->iterations > HC_REFINE_MAX_ITERATIONS) return false;
+    if (s->min_inliers < 0 || (s->min_inliers > 0 && s->min_inliers < 6)) return false;
+    if (s->iterations > 0) iterations = s->iterations;
+    if (s->min_inliers > 0) min_inliers = s->min_inliers;
+    return true;
+}
+
+template <bool GROUPED>
+hcStatus launch_pose_refine(const RefineArgs &a, int num_selections, hcStream stream) {
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(k_pose_refine<GROUPED>, dim3(num_selections), dim3(RF_THREADS), 0, (hipStream_t)stream, a);
+    if ((g_last_hip_error = hipGetLastError()) != hipSuccess) return HC_ERROR_LAUNCH;
+    return HC_SUCCESS;
+}
+
 }  // namespace
 
 }  // namespace hc
@@ -327,4 +678,27 @@ extern "C" hcStatus hc_trifocal_pose_inlier_mask(const hcTrifocalSelection *sele
                        locations, K, words, reinterpret_cast<unsigned long long *>(mask));
     if ((g_last_hip_error = hipGetLastError()) != hipSuccess) return HC_ERROR_LAUNCH;
     return HC_SUCCESS;
+}
+
+extern "C" hcStatus hc_trifocal_pose_refine(const hcTrifocalSelection *in, int num_edgels, const float *locations,
+                                            const float *K, const hcRefineSettings *settings,
+                                            hcTrifocalSelection *out, hcRefineReport *report, hcStream stream) {
+    using namespace hc;
+    int iterations, min_inliers;
+    if (!in || num_edgels <= 0 || !locations || !K || !out || !refine_settings(settings, iterations, min_inliers))
+        return HC_ERROR_INVALID_VALUE;
+    const RefineArgs a{in, out, report, num_edgels, locations, K, nullptr, iterations, min_inliers};
+    return launch_pose_refine<false>(a, 1, stream);
+}
+
+extern "C" hcStatus hc_trifocal_pose_refine_grouped(int num_groups, const hcTripletGroup *groups,
+                                                    const hcTrifocalSelection *in, const hcRefineSettings *settings,
+                                                    hcTrifocalSelection *out, hcRefineReport *reports,
+                                                    hcStream stream) {
+    using namespace hc;
+    int iterations, min_inliers;
+    if (num_groups <= 0 || !groups || !in || !out || !refine_settings(settings, iterations, min_inliers))
+        return HC_ERROR_INVALID_VALUE;
+    const RefineArgs a{in, out, reports, 0, nullptr, nullptr, groups, iterations, min_inliers};
+    return launch_pose_refine<true>(a, num_groups, stream);
 }

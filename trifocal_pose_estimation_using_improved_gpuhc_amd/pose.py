@@ -12,6 +12,11 @@ are inliers in both; hc_trifocal_pose_inlier_mask lists those edgels and
 hc_pose_merge_joint merges per-launch selections (pose_support_joint,
 pose_support_joint_grouped, inlier_mask, merge_joint below).
 
+Refinement (not in the reference): hc_trifocal_pose_refine and its grouped form
+(include/refine/hc_pose_refine.h) fit a joint selection's pose to its joint
+inliers on the device and return a selection of the same layout
+(launch_refine_joint, refine_joint, refine_joint_grouped below).
+
 The four pose-support calls (per view / joint, one triplet / grouped) share one
 launcher and one synchronous wrapper (_launch, _run), parameterised by a _Rule.
 Every native call goes through the signature table of _abi: buffers and streams
@@ -228,6 +233,122 @@ def inlier_mask(selection, edgels: torch.Tensor, K: torch.Tensor, packed: bool =
     if packed:
         return w
     return np.unpackbits(w.view(np.uint8), bitorder="little")[:E].astype(bool)
+
+
+# ---- refinement of a joint selection (include/refine/hc_pose_refine.h) --------
+REPORT_BYTES = _abi.REFINE_REPORT_BYTES
+
+
+def refine_report_dict(raw) -> dict:
+    r = _struct_from_raw(_abi.hcRefineReport, REPORT_BYTES, raw)
+    return dict(status=r.status, none=bool(r.status & _abi.HC_REFINE_NONE),
+                too_few=bool(r.status & _abi.HC_REFINE_TOO_FEW), singular=bool(r.status & _abi.HC_REFINE_SINGULAR),
+                iterations_run=r.iterations_run, best_iteration=r.best_iteration,
+                joint_history=np.array(r.joint_history[:], np.int32),
+                rms_px_in=np.array(r.rms_px_in[:], np.float64), rms_px_out=np.array(r.rms_px_out[:], np.float64))
+
+
+def _device_selections(selections, dev, count: int, what: str) -> torch.Tensor:
+    """count joint selections as device bytes: a uint8 device tensor as it is;
+    a dict or struct, or a list of them, uploaded."""
+    if not isinstance(selections, torch.Tensor):
+        items = selections if isinstance(selections, (list, tuple)) else [selections]
+        structs = [joint_selection_from_dict(s) if isinstance(s, dict) else joint_selection_struct(s) for s in items]
+        raw = b"".join(bytes(s) for s in structs)
+        selections = torch.from_numpy(np.frombuffer(raw, np.uint8).copy()).to(dev)
+    if not selections.is_cuda or not selections.is_contiguous() or selections.device != dev:
+        raise _abi.HCError(f"{what}: buffers must be contiguous tensors on one device")
+    if selections.numel() * selections.element_size() < count * JOINT_SEL_BYTES:
+        raise _abi.HCError(f"{what}: {count} hcTrifocalSelection expected")
+    return selections
+
+
+def _refine_settings(iterations, min_inliers, what: str) -> _abi.hcRefineSettings:
+    """The explicit values of the Python interface (the header's 0 = default is
+    not offered here: 0 iterations is refused, as every other value it would refuse)."""
+    for v in (iterations, min_inliers):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise _abi.HCError(f"{what}: iterations and min_inliers must be integers")
+    if not 1 <= iterations <= _abi.HC_REFINE_MAX_ITERATIONS:
+        raise _abi.HCError(f"{what}: iterations {iterations} outside 1..{_abi.HC_REFINE_MAX_ITERATIONS}")
+    if min_inliers < 6:
+        raise _abi.HCError(f"{what}: min_inliers {min_inliers} below 6")
+    s = _abi.hcRefineSettings()
+    s.iterations, s.min_inliers = int(iterations), int(min_inliers)
+    return s
+
+
+def launch_refine_joint(selection, edgels: torch.Tensor, K: torch.Tensor, iterations: int = 10,
+                        min_inliers: int = 16, stream=None, out: torch.Tensor | None = None):
+    """Enqueue hc_trifocal_pose_refine (no sync): the joint selection's pose
+    fitted to its joint inliers among the E edgels, the inlier set recomputed at
+    every iterate.  selection: the device bytes of an hcTrifocalSelection, or a
+    dict / struct (e.g. a merge_joint result), which is uploaded.  out: the
+    device bytes to write (may be selection itself); default a new tensor.
+    Returns (refined selection (JOINT_SEL_BYTES,) u8, report (REPORT_BYTES,) u8),
+    both on the device."""
+    what = "refine_joint"
+    settings = _refine_settings(iterations, min_inliers, what)
+    dev = edgels.device
+    selection = _device_selections(selection, dev, 1, what)
+    for t in (edgels, K):
+        if not t.is_cuda or not t.is_contiguous() or t.device != dev:
+            raise _abi.HCError(f"{what}: buffers must be contiguous tensors on one device")
+    if out is None:
+        out = torch.empty(JOINT_SEL_BYTES, dtype=torch.uint8, device=dev)
+    out = _device_selections(out, dev, 1, what)
+    report = torch.empty(REPORT_BYTES, dtype=torch.uint8, device=dev)
+    _abi.call("hc_trifocal_pose_refine", _abi.ptr(selection), int(edgels.shape[0]), _abi.ptr(edgels), _abi.ptr(K),
+              C.byref(settings), _abi.ptr(out), _abi.ptr(report),
+              _abi.ptr(stream if stream is not None else torch.cuda.current_stream(dev)))
+    return out, report
+
+
+def refine_joint(selection, edgels: torch.Tensor, K: torch.Tensor, iterations: int = 10, min_inliers: int = 16,
+                 return_device_selection: bool = False):
+    """Synchronous wrapper: (refined selection dict, report dict), and with
+    return_device_selection also the refined selection's device bytes."""
+    out, report = launch_refine_joint(selection, edgels, K, iterations, min_inliers)
+    torch.cuda.synchronize(edgels.device)
+    res = (joint_selection_dict(joint_selection_struct(out)), refine_report_dict(report))
+    return (*res, out) if return_device_selection else res
+
+
+def launch_refine_joint_grouped(selections, batch, iterations: int = 10, min_inliers: int = 16, stream=None):
+    """Enqueue hc_trifocal_pose_refine_grouped (no sync): selection t refined on
+    triplet t of batch (a multi.DeviceTripletBatch).  selections: T selections
+    as device bytes, or a list of dicts / structs, which is uploaded.  Returns
+    (selections (T * JOINT_SEL_BYTES,) u8, reports (T * REPORT_BYTES,) u8)."""
+    what = "refine_joint_grouped"
+    settings = _refine_settings(iterations, min_inliers, what)
+    dev = batch.device
+    T = batch.num_groups
+    if not isinstance(selections, torch.Tensor) and len(selections) != T:
+        raise _abi.HCError(f"{what}: {len(selections)} selections for {T} triplets")
+    selections = _device_selections(selections, dev, T, what)
+    batch.check()   # edgel counts: the kernel does not validate them
+    out = torch.empty(T * JOINT_SEL_BYTES, dtype=torch.uint8, device=dev)
+    reports = torch.empty(T * REPORT_BYTES, dtype=torch.uint8, device=dev)
+    _abi.call("hc_trifocal_pose_refine_grouped", T, _abi.ptr(batch.groups), _abi.ptr(selections), C.byref(settings),
+              _abi.ptr(out), _abi.ptr(reports),
+              _abi.ptr(stream if stream is not None else torch.cuda.current_stream(dev)))
+    return out, reports
+
+
+def refine_joint_grouped(selections, batch, iterations: int = 10, min_inliers: int = 16, device=None):
+    """Synchronous wrapper: ([refined selection dict] * T, [report dict] * T).
+    batch: a multi.TripletBatch (copied to device, or to the selections' device)
+    or a multi.DeviceTripletBatch."""
+    if not hasattr(batch, "groups"):
+        if device is None:
+            device = selections.device if isinstance(selections, torch.Tensor) else "cuda:0"
+        batch = batch.to(device)
+    out, reports = launch_refine_joint_grouped(selections, batch, iterations, min_inliers)
+    torch.cuda.synchronize(batch.device)
+    T = batch.num_groups
+    sels = out.cpu().numpy().reshape(T, JOINT_SEL_BYTES)
+    reps = reports.cpu().numpy().reshape(T, REPORT_BYTES)
+    return ([joint_selection_dict(joint_selection_struct(r)) for r in sels], [refine_report_dict(r) for r in reps])
 
 
 def merge_joint(parts: list, path_offsets: list) -> dict:
