@@ -61,7 +61,8 @@ def golden_passing(g):
 # ---- one run against another ----------------------------------------------
 
 def tracked(r):
-    """Paths an abort-mode launch tracked (every path of the committed inputs takes >= 13 steps)."""
+    """Paths an abort-mode launch tracked (every path of the committed inputs takes >= 13 steps
+    at the default limits, and at least 1 at any: test_limits_host.py)."""
     return r["stats"]["steps"] > 0
 
 
@@ -306,6 +307,34 @@ def ring_counters(tracker, workspace=None):
     off = int(tracker.L.hc_trifocal_workspace_size())
     rq = np.frombuffer(ws[off:off + 768].cpu().numpy().tobytes(), np.uint32)
     return int(rq[0]), int(rq[64]), int(rq[128])
+
+
+def ring_epoch(tracker, workspace=None):
+    """The ring epoch (KArgs::rq word 192), which k_prep_tables bumps on a
+    sliced launch only: 0 in a new workspace, one more after every launch that
+    ran with time slicing, unchanged by one that fell back to an unsliced run.
+    The workspace must have been made for slicing (new_workspace(n > 0))."""
+    ws = tracker.workspace if workspace is None else workspace
+    off = int(tracker.L.hc_trifocal_workspace_size()) + 4 * 192
+    assert ws.numel() >= off + 4, "a workspace without the time-slicing area"
+    return int(np.frombuffer(ws[off:off + 4].cpu().numpy().tobytes(), np.uint32)[0])
+
+
+def last_suspensions(tracker, num_samples, workspace):
+    """The step-control words of every path's suspend block after a sliced
+    launch of num_samples samples on workspace (made by new_workspace(num_samples)
+    and used by that launch only): what the path's last suspension packed
+    (hc_layout.hpp: word 31 = stepidx | nsteps << 16, ncorr | succ << 16 |
+    end_zone << 30 | check << 31; a running path's kept slope overwrites words
+    0..29 only).  A path that was never suspended has an all-zero word.  The
+    blocks are the last 256 B per path of the time-slicing area."""
+    paths = 312 * num_samples
+    total = int(tracker.L.hc_trifocal_workspace_size_for_steps(num_samples, tracker.settings.max_steps))
+    assert workspace.numel() == total, "the workspace was not made for this launch size"
+    blocks = np.frombuffer(workspace[total - 256 * paths:].cpu().numpy().tobytes(), np.uint32).reshape(paths, 64)
+    w2, w3 = blocks[:, 62].astype(np.int64), blocks[:, 63].astype(np.int64)
+    return dict(suspended=(w2 | w3) != 0, stepidx=w2 & 0xFFFF, nsteps=w2 >> 16, ncorr=w3 & 0xFFFF,
+                succ=(w3 >> 16) & 0x3FFF, end_zone=(w3 >> 30) & 1, check=(w3 >> 31) & 1)
 
 
 def run_cli(tmp_path, *args, timeout=300):

@@ -219,8 +219,9 @@ def test_invalid_arguments_are_rejected_before_any_device_work():
     for f in ("start_sols", "tracks", "start_params", "target_params", "diff_params", "unified_index",
               "converge", "infinity"):
         setattr(a, f, 0x1000)
-    a.settings = _abi.hcTrackSettings(-1, 3, 4)
-    assert L.hc_trifocal_2op1p_30x30_track(C.byref(a), dummy, ws, None) == 1
+    for bad in ((-1, 3, 4), (80, -1, 4), (80, 3, -1)):
+        a.settings = _abi.hcTrackSettings(*bad)
+        assert L.hc_trifocal_2op1p_30x30_track(C.byref(a), dummy, ws, None) == 1, bad
     a.settings = _abi.hcTrackSettings(80, 3, 4)
     # too many paths for the int32 batch index of the reference interface
     a.sub_ransac_iters = (1 << 31) // 312 + 1
