@@ -21,6 +21,8 @@
 #   joint     per-view against joint pose selection, config-5 protocol (scripts/joint_pose.py [TRIALS [REPS]]) -> TAG_joint.json
 #   refine    the joint selection against the same selection refined on its inliers, config-5 protocol
 #             (scripts/refine_pose.py [TRIALS [REPS]]) -> TAG_refine.json
+#   topk      the refined joint winner against the best of the K refined top-K candidates, K = 1..16, config-5 protocol
+#             (scripts/topk_refine.py [TRIALS [REPS]]) -> TAG_topk.json
 #   gated     the gated abort launch against plain tracking + joint selection, config-5 protocol
 #             (scripts/gated_stop.py [TRIALS]) -> TAG_gated.json
 #   gated_ab  the launches that existed before the gated one (scripts/gated_stop.py --existing) on builds
@@ -107,6 +109,7 @@ for k,v in sorted(g.items()): print(k, v)" ;;
     multi) run multi 300 python scripts/multi_triplet.py "$@" > $O/${T}_multi.json; rc=$?; cat $O/${T}_multi.json ;;
     joint) run joint 600 python scripts/joint_pose.py "$@" > $O/${T}_joint.json; rc=$?; cat $O/${T}_joint.json ;;
     refine) run refine 600 python scripts/refine_pose.py "$@" > $O/${T}_refine.json; rc=$?; tail -c 1500 $O/${T}_refine.json ;;
+    topk) run topk 600 python scripts/topk_refine.py "$@" > $O/${T}_topk.json; rc=$?; tail -c 1500 $O/${T}_topk.json ;;
     gated) run gated 900 python scripts/gated_stop.py "$@" > $O/${T}_gated.json; rc=$?; tail -c 600 $O/${T}_gated.json ;;
     p2c) run p2c 300 python scripts/ablation_p2c.py --out $O/${T}_ablation_p2c.json "$@"; rc=$? ;;
     gated_ab)

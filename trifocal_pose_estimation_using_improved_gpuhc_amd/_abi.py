@@ -8,9 +8,9 @@ The boundary is described once: the ctypes mirrors of the argument structs and
 SIGNATURES, one (name, restype, argtypes, optional) entry per declared function.
 lib() binds the table, DECLARED_SYMBOLS is its names, and tests/test_abi_host.py
 holds both against the headers (layouts through the C compiler, signatures
-against the prototypes).  The two headers in directories of their own
-(include/p2c, include/refine) have tables of their own, P2C_SIGNATURES and
-REFINE_SIGNATURES, checked the same way.  Callers go through two helpers: ptr(x), the c_void_p
+against the prototypes).  The three headers in directories of their own
+(include/p2c, include/refine, include/topk) have tables of their own,
+P2C_SIGNATURES, REFINE_SIGNATURES and TOPK_SIGNATURES, checked the same way.  Callers go through two helpers: ptr(x), the c_void_p
 of a tensor, array or stream, and call(name, *args), which raises HCError on a
 status other than HC_SUCCESS.
 """
@@ -247,6 +247,18 @@ REFINE_SIGNATURES = (
 )
 REFINE_DECLARED_SYMBOLS = tuple(s.name for s in REFINE_SIGNATURES)
 
+# include/topk/hc_pose_topk.h, the top-k candidates' header beside the refinement's:
+# its table, bound and checked the same way (tests/test_topk_host.py)
+HC_TOPK_MAX = 32
+TOPK_SIGNATURES = (
+    Sig("hc_trifocal_pose_topk_joint", _ST, (_i, _p, _p, _i, _p, _p), True),
+    Sig("hc_trifocal_pose_topk_joint_grouped", _ST, (_i, _p, _p, _i, _p, _i, _p, _p), True),
+    Sig("hc_trifocal_pose_refine_topk", _ST, (_i, _p, _i, _p, _p, _RS, _p, _p, _p, _p, _p), True),
+    Sig("hc_trifocal_pose_refine_topk_grouped", _ST, (_i, _p, _i, _p, _RS, _p, _p, _p, _p, _p), True),
+    Sig("hc_pose_merge_topk", None, (_i, _i, _p, _p, _p), True),
+)
+TOPK_DECLARED_SYMBOLS = tuple(s.name for s in TOPK_SIGNATURES)
+
 _lib = None
 
 
@@ -262,7 +274,7 @@ def lib() -> C.CDLL:
         # instead of pulling a second HIP/HSA runtime from /opt/rocm.
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
-        for s in SIGNATURES + P2C_SIGNATURES + REFINE_SIGNATURES:
+        for s in SIGNATURES + P2C_SIGNATURES + REFINE_SIGNATURES + TOPK_SIGNATURES:
             fn = getattr(L, s.name, None)
             if fn is None:
                 if s.optional:

@@ -9,6 +9,7 @@
 #include "../../include/hc_host.h"
 #include "../../include/hc_pose.h"
 #include "../../include/p2c/hc_trifocal_p2c.h"
+#include "../../include/topk/hc_pose_topk.h"
 
 #include <cmath>
 #include <cstdio>
@@ -266,6 +267,36 @@ void hc_pose_merge_joint(int n, const hcTrifocalSelection *parts, const int32_t 
         r.pad2 = 0.0f;
     }
     *out = r;
+}
+
+void hc_pose_merge_topk(int n, int k, const hcTrifocalSelection *parts, const int32_t *off, hcTrifocalSelection *out) {
+    // one top-k launch over all paths would have kept the k largest of the same keys (hc_pose.hip)
+    if (k < 1 || k > HC_TOPK_MAX) return;
+    hcTrifocalSelection none{};
+    none.path = none.inliers = none.inliers21 = none.inliers31 = -1;
+    for (int i = 0; i < n; i++)
+        if (parts[(size_t)i * k].num_candidates > 0) none.num_candidates += parts[(size_t)i * k].num_candidates;
+    for (int r = 0; r < k; r++) out[r] = none;
+    for (int i = 0; i < n; i++) {
+        for (int j = 0; j < k; j++) {
+            const hcTrifocalSelection &p = parts[(size_t)i * k + j];
+            if (p.num_candidates <= 0 || p.path < 0) continue;
+            hcTrifocalSelection c = p;
+            c.num_candidates = none.num_candidates;
+            c.key = ((p.key >> 32) << 32) | (uint64_t)((uint32_t)p.key + (uint32_t)off[i]);
+            c.path = p.path + off[i];
+            c.pad = 0;
+            c.pad2 = 0.0f;
+            // insert into the descending list; a candidate below its last entry is dropped
+            for (int r = 0; r < k; r++) {
+                if (out[r].path >= 0 && out[r].key >= c.key) continue;
+                const hcTrifocalSelection lower = out[r];
+                out[r] = c;
+                c = lower;
+                if (c.path < 0) break;
+            }
+        }
+    }
 }
 
 namespace {

@@ -28,10 +28,14 @@
 // joint selection's inlier edgels as a bit mask, through the same edgel_views.
 // k_pose_refine<GROUPED> (include/refine/hc_pose_refine.h, described where it
 // is defined below) refines a joint selection on the edgels edgel_views accepts.
+// k_pose_topk<GROUPED>, k_pose_topk_final and k_pose_topk_select
+// (include/topk/hc_pose_topk.h, described below the refinement) rank the k best
+// joint candidates and select among their refinements.
 #include <type_traits>
 
 #include "../../include/hc_pose.h"
 #include "../../include/refine/hc_pose_refine.h"
+#include "../../include/topk/hc_pose_topk.h"
 #include "hc_device.hpp"
 #include "hc_pose_device.hpp"   // make_pose, reproj_inlier, edgel_views, is_candidate: shared with the gated tracker
 
@@ -154,13 +158,11 @@ __device__ __forceinline__ void decode_selection(int num_paths, const cf *__rest
     }
 }
 
-// decode the key of one joint selection: the selected path's counts, its pose
-// for both views and |Re x[21..23]| / |Re x[18..20]| (the norms unit3 divides by)
-__device__ __forceinline__ void decode_joint(int num_paths, const cf *__restrict__ tracks,
-                                             const int32_t *__restrict__ inl, hcTrifocalSelection *sel) {
-    int b = -1;
-    if (sel->num_candidates > 0) b = (int)(uint32_t)sel->key;
-    if (b >= num_paths) b = -1;
+// the joint selection of path b (-1: none): its counts, its pose for both views
+// and |Re x[21..23]| / |Re x[18..20]| (the norms unit3 divides by).  num_candidates,
+// key and the padding are not written: they are the launch's zeroes and atomics.
+__device__ __forceinline__ void write_joint_path(int b, const cf *__restrict__ tracks, const int32_t *__restrict__ inl,
+                                                 hcTrifocalSelection *sel) {
     Pose P;
     for (int i = 0; i < 18; i++) P.R[i] = 0.0f;
     for (int i = 0; i < 6; i++) P.t[i] = 0.0f;
@@ -183,6 +185,15 @@ __device__ __forceinline__ void decode_joint(int num_paths, const cf *__restrict
     sel->inliers21 = c21;
     sel->inliers31 = c31;
     sel->scale31 = scale;
+}
+
+// decode the key of one joint selection
+__device__ __forceinline__ void decode_joint(int num_paths, const cf *__restrict__ tracks,
+                                             const int32_t *__restrict__ inl, hcTrifocalSelection *sel) {
+    int b = -1;
+    if (sel->num_candidates > 0) b = (int)(uint32_t)sel->key;
+    if (b >= num_paths) b = -1;
+    write_joint_path(b, tracks, inl, sel);
 }
 
 // one thread per selection (num_sel = 1 for the single-triplet calls)
@@ -297,11 +308,12 @@ struct RefineArgs {
     const hcTrifocalSelection *in;
     hcTrifocalSelection *out;   // may be in
     hcRefineReport *rep;        // or nullptr
-    int E;                      // the scene, or with GROUPED that of groups[blockIdx.x]
+    int E;                      // the scene, or with GROUPED that of groups[blockIdx.x / per_group]
     const float *loc;
     const float *K;
     const hcTripletGroup *groups;
     int iterations, min_inliers;
+    int per_group;              // GROUPED: selections per triplet (1, or the k of the top-k call)
 };
 
 __device__ __forceinline__ double wave_sum_d(double v) {
@@ -464,13 +476,14 @@ __global__ void __launch_bounds__(RF_THREADS) k_pose_refine(const RefineArgs a) 
     const int tid = threadIdx.x, lane = lane_id(), wave = tid / WAVE, sel = blockIdx.x;
     Scene sc;
     if constexpr (GROUPED) {
-        const hcTripletGroup g = a.groups[sel];
+        const hcTripletGroup g = a.groups[sel / a.per_group];
         sc = load_scene(g.num_edgels, g.locations, g.K);
     } else {
         sc = load_scene(a.E, a.loc, a.K);
     }
     // every thread reads the input here, before the first barrier; thread 0
-    // writes the output after the last one (out may be in)
+    // writes the output after the last one (out may be in; a workgroup touches
+    // no other selection than its own)
     const hcTrifocalSelection keep = a.in[sel];
     hcRefineReport *rep = a.rep ? a.rep + sel : nullptr;
     if (keep.path < 0) {
@@ -626,6 +639,129 @@ hcStatus launch_pose_refine(const RefineArgs &a, int num_selections, hcStream st
     return HC_SUCCESS;
 }
 
+// ---- the k best joint candidates (include/topk/hc_pose_topk.h) ---------------
+//
+// k_pose_topk<GROUPED>: one pass over the per-path joint counts, one thread per
+// batch id (grid-stride).  The k output slots of a group are the data structure:
+// a candidate offers its key v = joint << 32 | b to slot 0 with a 64-bit
+// atomicMax, carries the smaller of (old, v) to slot 1, and so on; a value that
+// is 0 or falls off the end is dropped.  Slot i ends with the i-th largest key:
+// every key is offered to slot 0, which ends with the maximum; every key that
+// does not end in slot 0 is at some moment carried to slot 1; and so on down.
+// The keys are distinct (b is in them), so the final state does not depend on
+// the order of arrival: two runs write the same bytes.  A slot's value only
+// grows, so a key below what slot k-1 holds at any moment can be skipped.
+// Candidates are about 0.1 % of the paths: no pre-reduction.  The group's
+// candidates are counted in slot 0's num_candidates, as k_pose_support does.
+// The key 0 (no joint inlier, batch id 0) is never inserted and needs not be:
+// it is the smallest key, and the zeroed slot that it would end in holds it.
+struct TopkArgs {
+    int num_paths;
+    const cf *tracks;
+    const int32_t *inl;            // (joint, c21, c31) per path, joint < 0: no candidate
+    const int32_t *sample_group;   // GROUPED
+    int k;
+    hcTrifocalSelection *cand;     // num_groups x k
+    int num_groups;
+};
+
+template <bool GROUPED>
+__global__ void __launch_bounds__(256) k_pose_topk(const TopkArgs a) {
+    const int stride = gridDim.x * blockDim.x;
+    for (int b = blockIdx.x * blockDim.x + threadIdx.x; b < a.num_paths; b += stride) {
+        const int cJ = a.inl[3 * (size_t)b];
+        if (cJ < 0) continue;
+        hcTrifocalSelection *slots = a.cand;
+        if constexpr (GROUPED) slots += (size_t)a.sample_group[b / NTRK] * a.k;
+        atomicAdd(&slots[0].num_candidates, 1);
+        unsigned long long v = sel_key(cJ, b, false);
+        const unsigned long long last =
+            __atomic_load_n(reinterpret_cast<unsigned long long *>(&slots[a.k - 1].key), __ATOMIC_RELAXED);
+        if (v < last) continue;   // a stale value only skips less
+        for (int i = 0; i < a.k && v != 0; i++) {
+            const unsigned long long old = atomicMax(reinterpret_cast<unsigned long long *>(&slots[i].key), v);
+            if (old < v) v = old;
+        }
+    }
+}
+
+// one thread per (group, rank): the selection of the rank's key, "none" at or
+// beyond the number of candidates.  Slot 0's num_candidates is the pass's
+// counter and is only read here; the other ranks copy it.
+__global__ void __launch_bounds__(64) k_pose_topk_final(const TopkArgs a) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.num_groups * a.k) return;
+    const int r = i % a.k;
+    hcTrifocalSelection *sel = a.cand + i;
+    const int nc = a.cand[i - r].num_candidates;
+    int b = -1;
+    if (r < nc) b = (int)(uint32_t)sel->key;
+    if (b >= a.num_paths) b = -1;
+    write_joint_path(b, a.tracks, a.inl, sel);
+    if (r > 0) sel->num_candidates = nc;
+}
+
+// one thread per group: the refined selection with the largest key among those
+// with a path, or "none" with rank -1
+__global__ void __launch_bounds__(64) k_pose_topk_select(int num_groups, int k,
+                                                         const hcTrifocalSelection *__restrict__ refined,
+                                                         hcTrifocalSelection *__restrict__ best,
+                                                         int32_t *__restrict__ best_rank) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= num_groups) return;
+    const hcTrifocalSelection *in = refined + (size_t)t * k;
+    int rank = -1;
+    uint64_t key = 0;
+    for (int r = 0; r < k; r++) {
+        if (in[r].path < 0) continue;
+        if (rank < 0 || in[r].key > key) { rank = r; key = in[r].key; }
+    }
+    hcTrifocalSelection o;
+    if (rank >= 0) {
+        o = in[rank];
+    } else {
+        o.num_candidates = in[0].num_candidates;
+        o.path = o.inliers = o.inliers21 = o.inliers31 = -1;
+        o.pad = 0;
+        o.key = 0;
+        for (int i = 0; i < 9; i++) o.R21[i] = o.R31[i] = 0.0f;
+        for (int i = 0; i < 3; i++) o.t21[i] = o.t31[i] = 0.0f;
+        o.scale31 = o.pad2 = 0.0f;
+    }
+    best[t] = o;
+    best_rank[t] = rank;
+}
+
+// zeroed slots, the pass over the paths, the decoding epilogue (arguments validated)
+template <bool GROUPED>
+hcStatus launch_pose_topk(const TopkArgs &a, hcStream stream) {
+    hipStream_t s = (hipStream_t)stream;
+    const int slots = a.num_groups * a.k;
+    (void)hipGetLastError();
+    if ((g_last_hip_error = hipMemsetAsync(a.cand, 0, sizeof(hcTrifocalSelection) * (size_t)slots, s)) != hipSuccess)
+        return HC_ERROR_LAUNCH;
+    if (a.num_paths > 0) {
+        const int want = (a.num_paths + 255) / 256;
+        hipLaunchKernelGGL(k_pose_topk<GROUPED>, dim3(want < 2048 ? want : 2048), dim3(256), 0, s, a);
+        if ((g_last_hip_error = hipGetLastError()) != hipSuccess) return HC_ERROR_LAUNCH;
+    }
+    hipLaunchKernelGGL(k_pose_topk_final, dim3((slots + 63) / 64), dim3(64), 0, s, a);
+    if ((g_last_hip_error = hipGetLastError()) != hipSuccess) return HC_ERROR_LAUNCH;
+    return HC_SUCCESS;
+}
+
+// k refinements per scene, then the selection among them
+template <bool GROUPED>
+hcStatus launch_refine_topk(const RefineArgs &a, int num_groups, hcTrifocalSelection *best, int32_t *best_rank,
+                            hcStream stream) {
+    const hcStatus st = launch_pose_refine<GROUPED>(a, num_groups * a.per_group, stream);
+    if (st != HC_SUCCESS) return st;
+    hipLaunchKernelGGL(k_pose_topk_select, dim3((num_groups + 63) / 64), dim3(64), 0, (hipStream_t)stream, num_groups,
+                       a.per_group, a.out, best, best_rank);
+    if ((g_last_hip_error = hipGetLastError()) != hipSuccess) return HC_ERROR_LAUNCH;
+    return HC_SUCCESS;
+}
+
 }  // namespace
 
 }  // namespace hc
@@ -687,7 +823,7 @@ extern "C" hcStatus hc_trifocal_pose_refine(const hcTrifocalSelection *in, int n
     int iterations, min_inliers;
     if (!in || num_edgels <= 0 || !locations || !K || !out || !refine_settings(settings, iterations, min_inliers))
         return HC_ERROR_INVALID_VALUE;
-    const RefineArgs a{in, out, report, num_edgels, locations, K, nullptr, iterations, min_inliers};
+    const RefineArgs a{in, out, report, num_edgels, locations, K, nullptr, iterations, min_inliers, 1};
     return launch_pose_refine<false>(a, 1, stream);
 }
 
@@ -699,6 +835,57 @@ extern "C" hcStatus hc_trifocal_pose_refine_grouped(int num_groups, const hcTrip
     int iterations, min_inliers;
     if (num_groups <= 0 || !groups || !in || !out || !refine_settings(settings, iterations, min_inliers))
         return HC_ERROR_INVALID_VALUE;
-    const RefineArgs a{in, out, reports, 0, nullptr, nullptr, groups, iterations, min_inliers};
+    const RefineArgs a{in, out, reports, 0, nullptr, nullptr, groups, iterations, min_inliers, 1};
     return launch_pose_refine<true>(a, num_groups, stream);
+}
+
+extern "C" hcStatus hc_trifocal_pose_topk_joint(int num_paths, const hcComplex *tracks, const int32_t *inliers, int k,
+                                                hcTrifocalSelection *candidates, hcStream stream) {
+    using namespace hc;
+    if (k < 1 || k > HC_TOPK_MAX || num_paths < 0 || !candidates) return HC_ERROR_INVALID_VALUE;
+    if (num_paths > 0 && (!tracks || !inliers)) return HC_ERROR_INVALID_VALUE;
+    const TopkArgs a{num_paths, (const cf *)tracks, inliers, nullptr, k, candidates, 1};
+    return launch_pose_topk<false>(a, stream);
+}
+
+extern "C" hcStatus hc_trifocal_pose_topk_joint_grouped(int num_paths, const hcComplex *tracks,
+                                                        const int32_t *inliers, int num_groups,
+                                                        const int32_t *sample_group, int k,
+                                                        hcTrifocalSelection *candidates, hcStream stream) {
+    using namespace hc;
+    if (k < 1 || k > HC_TOPK_MAX || num_paths < 0 || num_paths % NTRK != 0 || num_groups < 1 || !candidates)
+        return HC_ERROR_INVALID_VALUE;
+    if (num_groups > 0x7FFFFFFF / HC_TOPK_MAX) return HC_ERROR_INVALID_VALUE;
+    if (num_paths > 0 && (!tracks || !inliers || !sample_group)) return HC_ERROR_INVALID_VALUE;
+    const TopkArgs a{num_paths, (const cf *)tracks, inliers, sample_group, k, candidates, num_groups};
+    return launch_pose_topk<true>(a, stream);
+}
+
+extern "C" hcStatus hc_trifocal_pose_refine_topk(int k, const hcTrifocalSelection *candidates, int num_edgels,
+                                                 const float *locations, const float *K,
+                                                 const hcRefineSettings *settings, hcTrifocalSelection *refined,
+                                                 hcRefineReport *reports, hcTrifocalSelection *best,
+                                                 int32_t *best_rank, hcStream stream) {
+    using namespace hc;
+    int iterations, min_inliers;
+    if (k < 1 || k > HC_TOPK_MAX || !candidates || num_edgels <= 0 || !locations || !K || !refined || !best ||
+        !best_rank || !refine_settings(settings, iterations, min_inliers))
+        return HC_ERROR_INVALID_VALUE;
+    const RefineArgs a{candidates, refined, reports, num_edgels, locations, K, nullptr, iterations, min_inliers, k};
+    return launch_refine_topk<false>(a, 1, best, best_rank, stream);
+}
+
+extern "C" hcStatus hc_trifocal_pose_refine_topk_grouped(int num_groups, const hcTripletGroup *groups, int k,
+                                                         const hcTrifocalSelection *candidates,
+                                                         const hcRefineSettings *settings,
+                                                         hcTrifocalSelection *refined, hcRefineReport *reports,
+                                                         hcTrifocalSelection *best, int32_t *best_rank,
+                                                         hcStream stream) {
+    using namespace hc;
+    int iterations, min_inliers;
+    if (num_groups < 1 || num_groups > 0x7FFFFFFF / HC_TOPK_MAX || !groups || k < 1 || k > HC_TOPK_MAX ||
+        !candidates || !refined || !best || !best_rank || !refine_settings(settings, iterations, min_inliers))
+        return HC_ERROR_INVALID_VALUE;
+    const RefineArgs a{candidates, refined, reports, 0, nullptr, nullptr, groups, iterations, min_inliers, k};
+    return launch_refine_topk<true>(a, num_groups, best, best_rank, stream);
 }

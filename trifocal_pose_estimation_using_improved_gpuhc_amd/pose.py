@@ -17,6 +17,12 @@ Refinement (not in the reference): hc_trifocal_pose_refine and its grouped form
 inliers on the device and return a selection of the same layout
 (launch_refine_joint, refine_joint, refine_joint_grouped below).
 
+Top-k (not in the reference): the calls of include/topk/hc_pose_topk.h rank the
+k best joint candidates from the per-path counts, refine all k on one scene in
+one launch and select the refined one with the most joint inliers (topk_joint,
+refine_topk, their grouped forms, merge_topk, and select_refined, which chains
+joint support, top-k and refine-and-select on one stream).
+
 The four pose-support calls (per view / joint, one triplet / grouped) share one
 launcher and one synchronous wrapper (_launch, _run), parameterised by a _Rule.
 Every native call goes through the signature table of _abi: buffers and streams
@@ -363,6 +369,235 @@ def merge_joint(parts: list, path_offsets: list) -> dict:
     out = _abi.hcTrifocalSelection()
     _abi.lib().hc_pose_merge_joint(n, C.cast(arr, C.c_void_p), _abi.ptr(offs), C.byref(out))
     return joint_selection_dict(out)
+
+
+# ---- the k best joint candidates, refined, and the selection among them -------
+# (include/topk/hc_pose_topk.h)
+TOPK_MAX = _abi.HC_TOPK_MAX
+
+
+def _check_k(k, what: str) -> int:
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= TOPK_MAX:
+        raise _abi.HCError(f"{what}: k {k!r} outside 1..{TOPK_MAX}")
+    return int(k)
+
+
+def _selection_dicts(raw: torch.Tensor, count: int) -> list:
+    rows = raw.cpu().numpy().view(np.uint8).reshape(-1)[:count * JOINT_SEL_BYTES].reshape(count, JOINT_SEL_BYTES)
+    return [joint_selection_dict(joint_selection_struct(r)) for r in rows]
+
+
+def _launch_topk(what, tracks, inliers, k, groups, sample_group, candidates, stream):
+    k = _check_k(k, what)
+    n = int(tracks.shape[0])
+    dev = tracks.device
+    if candidates is None:
+        candidates = torch.empty(groups * k * JOINT_SEL_BYTES, dtype=torch.uint8, device=dev)
+    bufs = (tracks, inliers, candidates) + (() if sample_group is None else (sample_group,))
+    for t in bufs:
+        if not t.is_cuda or not t.is_contiguous() or t.device != dev:
+            raise _abi.HCError(f"{what}: buffers must be contiguous tensors on one device")
+    if inliers.numel() < 3 * n or candidates.numel() * candidates.element_size() < groups * k * JOINT_SEL_BYTES or \
+            (sample_group is not None and sample_group.numel() * _abi.NUM_TRACKS != n):
+        raise _abi.HCError(f"{what}: buffer sizes do not match")
+    s = _abi.ptr(stream if stream is not None else torch.cuda.current_stream(dev))
+    if sample_group is None:
+        _abi.call("hc_trifocal_pose_topk_joint", n, _abi.ptr(tracks), _abi.ptr(inliers), k, _abi.ptr(candidates), s)
+    else:
+        _abi.call("hc_trifocal_pose_topk_joint_grouped", n, _abi.ptr(tracks), _abi.ptr(inliers), groups,
+                  _abi.ptr(sample_group), k, _abi.ptr(candidates), s)
+    return candidates
+
+
+def launch_topk_joint(tracks: torch.Tensor, inliers: torch.Tensor, k: int, candidates: torch.Tensor | None = None,
+                      stream=None) -> torch.Tensor:
+    """Enqueue hc_trifocal_pose_topk_joint (no sync): the k candidates with the
+    most joint inliers (ties -> the larger batch id), best first, from the (n, 3)
+    counts a joint pose-support call has written.  Returns candidates, the device
+    bytes of k hcTrifocalSelection (a new tensor unless given); ranks beyond the
+    number of candidates are "none" selections."""
+    return _launch_topk("topk_joint", tracks, inliers, k, 1, None, candidates, stream)
+
+
+def topk_joint(tracks: torch.Tensor, inliers: torch.Tensor, k: int, return_device_selection: bool = False):
+    """Synchronous wrapper: [selection dict] * k, and with
+    return_device_selection also their device bytes."""
+    cand = launch_topk_joint(tracks, inliers, k)
+    torch.cuda.synchronize(tracks.device)
+    dicts = _selection_dicts(cand, _check_k(k, "topk_joint"))
+    return (dicts, cand) if return_device_selection else dicts
+
+
+def launch_topk_joint_grouped(tracks: torch.Tensor, inliers: torch.Tensor, batch, k: int,
+                              candidates: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+    """Enqueue hc_trifocal_pose_topk_joint_grouped (no sync): per triplet t of
+    batch (a multi.DeviceTripletBatch) the k best candidates among its own
+    samples, at candidates[t * k + r], with the call's batch ids."""
+    what = "topk_joint_grouped"
+    _check_k(k, what)
+    if tracks.shape[0] != batch.num_samples * _abi.NUM_TRACKS or tracks.device != batch.device:
+        raise _abi.HCError(f"{what}: tracks do not cover the batch's samples on its device")
+    batch.check()   # group ids: the kernel does not validate them
+    return _launch_topk(what, tracks, inliers, k, batch.num_groups, batch.sample_group, candidates, stream)
+
+
+def topk_joint_grouped(tracks: torch.Tensor, inliers: torch.Tensor, batch, k: int):
+    """Synchronous wrapper: a list of T lists of k selection dicts.  batch: a
+    multi.TripletBatch (copied to the tracks' device) or a multi.DeviceTripletBatch."""
+    if not hasattr(batch, "groups"):
+        batch = batch.to(tracks.device)
+    cand = launch_topk_joint_grouped(tracks, inliers, batch, k)
+    torch.cuda.synchronize(tracks.device)
+    d = _selection_dicts(cand, batch.num_groups * k)
+    return [d[t * k:(t + 1) * k] for t in range(batch.num_groups)]
+
+
+def _launch_refine_topk(what, candidates, k, scene, iterations, min_inliers, stream, refined):
+    """scene: (edgels, K) or a multi.DeviceTripletBatch."""
+    k = _check_k(k, what)
+    settings = _refine_settings(iterations, min_inliers, what)
+    grouped = not isinstance(scene, tuple)
+    dev = scene.device if grouped else scene[0].device
+    T = scene.num_groups if grouped else 1
+    if not isinstance(candidates, torch.Tensor) and len(candidates) != T * k:
+        raise _abi.HCError(f"{what}: {len(candidates)} candidates for {T} x {k}")
+    candidates = _device_selections(candidates, dev, T * k, what)
+    if refined is None:
+        refined = torch.empty(T * k * JOINT_SEL_BYTES, dtype=torch.uint8, device=dev)
+    refined = _device_selections(refined, dev, T * k, what)
+    reports = torch.empty(T * k * REPORT_BYTES, dtype=torch.uint8, device=dev)
+    best = torch.empty(T * JOINT_SEL_BYTES, dtype=torch.uint8, device=dev)
+    best_rank = torch.empty(T, dtype=torch.int32, device=dev)
+    s = _abi.ptr(stream if stream is not None else torch.cuda.current_stream(dev))
+    out = (_abi.ptr(refined), _abi.ptr(reports), _abi.ptr(best), _abi.ptr(best_rank), s)
+    if grouped:
+        scene.check()   # edgel counts: the kernel does not validate them
+        _abi.call("hc_trifocal_pose_refine_topk_grouped", T, _abi.ptr(scene.groups), k, _abi.ptr(candidates),
+                  C.byref(settings), *out)
+    else:
+        for t in scene:
+            if not t.is_cuda or not t.is_contiguous() or t.device != dev:
+                raise _abi.HCError(f"{what}: buffers must be contiguous tensors on one device")
+        _abi.call("hc_trifocal_pose_refine_topk", k, _abi.ptr(candidates), int(scene[0].shape[0]), _abi.ptr(scene[0]),
+                  _abi.ptr(scene[1]), C.byref(settings), *out)
+    return best, best_rank, refined, reports
+
+
+def _topk_count(candidates, what: str) -> int:
+    if isinstance(candidates, torch.Tensor):
+        n, rem = divmod(candidates.numel() * candidates.element_size(), JOINT_SEL_BYTES)
+        if rem:
+            raise _abi.HCError(f"{what}: the candidates are not a whole number of hcTrifocalSelection")
+        return n
+    return len(candidates)
+
+
+def launch_refine_topk(candidates, edgels: torch.Tensor, K: torch.Tensor, iterations: int = 10, min_inliers: int = 16,
+                       stream=None, refined: torch.Tensor | None = None):
+    """Enqueue hc_trifocal_pose_refine_topk (no sync): every candidate refined
+    on the E edgels as launch_refine_joint refines it, in one launch, and the
+    refined selection with the most joint inliers (ties -> the larger batch id)
+    selected.  candidates: the device bytes of k hcTrifocalSelection (the output
+    of launch_topk_joint: k is their number), or a list of k dicts / structs,
+    which is uploaded.  refined: the device bytes to write (may be candidates).
+    Returns device tensors (best (JOINT_SEL_BYTES,) u8, best_rank (1,) i32,
+    refined (k * JOINT_SEL_BYTES,) u8, reports (k * REPORT_BYTES,) u8)."""
+    what = "refine_topk"
+    _refine_settings(iterations, min_inliers, what)
+    return _launch_refine_topk(what, candidates, _topk_count(candidates, what), (edgels, K), iterations, min_inliers,
+                               stream, refined)
+
+
+def _refine_topk_dicts(best, best_rank, refined, reports, T, k):
+    sels = _selection_dicts(refined, T * k)
+    reps = reports.cpu().numpy().reshape(T * k, REPORT_BYTES)
+    ranks = best_rank.cpu().numpy()
+    return [dict(best=b, best_rank=int(ranks[t]), refined=sels[t * k:(t + 1) * k],
+                 reports=[refine_report_dict(r) for r in reps[t * k:(t + 1) * k]])
+            for t, b in enumerate(_selection_dicts(best, T))]
+
+
+def refine_topk(candidates, edgels: torch.Tensor, K: torch.Tensor, iterations: int = 10, min_inliers: int = 16):
+    """Synchronous wrapper: (best dict, best_rank, [refined dict] * k, [report dict] * k)."""
+    out = launch_refine_topk(candidates, edgels, K, iterations, min_inliers)
+    torch.cuda.synchronize(edgels.device)
+    d = _refine_topk_dicts(*out, 1, _topk_count(candidates, "refine_topk"))[0]
+    return d["best"], d["best_rank"], d["refined"], d["reports"]
+
+
+def launch_refine_topk_grouped(candidates, batch, k: int, iterations: int = 10, min_inliers: int = 16, stream=None,
+                               refined: torch.Tensor | None = None):
+    """Enqueue hc_trifocal_pose_refine_topk_grouped (no sync): candidates
+    [t * k + r] refined on triplet t of batch (a multi.DeviceTripletBatch), one
+    selection per triplet.  Returns (best (T * JOINT_SEL_BYTES,) u8, best_rank
+    (T,) i32, refined, reports)."""
+    _check_k(k, "refine_topk_grouped")
+    return _launch_refine_topk("refine_topk_grouped", candidates, k, batch, iterations, min_inliers, stream, refined)
+
+
+def refine_topk_grouped(candidates, batch, k: int, iterations: int = 10, min_inliers: int = 16, device=None):
+    """Synchronous wrapper: per triplet a dict(best, best_rank, refined, reports)
+    of dicts.  batch: a multi.TripletBatch (copied to device, or to the
+    candidates' device) or a multi.DeviceTripletBatch."""
+    _check_k(k, "refine_topk_grouped")
+    _refine_settings(iterations, min_inliers, "refine_topk_grouped")
+    if not hasattr(batch, "groups"):
+        if device is None:
+            device = candidates.device if isinstance(candidates, torch.Tensor) else "cuda:0"
+        batch = batch.to(device)
+    out = launch_refine_topk_grouped(candidates, batch, k, iterations, min_inliers)
+    torch.cuda.synchronize(batch.device)
+    return _refine_topk_dicts(*out, batch.num_groups, k)
+
+
+def merge_topk(parts: list, path_offsets: list, k: int) -> list:
+    """hc_pose_merge_topk: the top-k lists of several launches / GPUs (each a
+    list of k dicts / structs, or the raw bytes of k selections) with their first
+    batch ids -> the k best of all, with global batch ids."""
+    k = _check_k(k, "merge_topk")
+    n = len(parts)
+    if len(path_offsets) != n:
+        raise _abi.HCError(f"merge_topk: {len(path_offsets)} offsets for {n} parts")
+    arr = (_abi.hcTrifocalSelection * max(1, n * k))()
+    for i, part in enumerate(parts):
+        if isinstance(part, (torch.Tensor, np.ndarray)):
+            raw = part.cpu().numpy() if isinstance(part, torch.Tensor) else part
+            raw = np.ascontiguousarray(raw).view(np.uint8).reshape(-1)
+            part = [raw[j * JOINT_SEL_BYTES:(j + 1) * JOINT_SEL_BYTES] for j in range(raw.size // JOINT_SEL_BYTES)]
+        if len(part) != k:
+            raise _abi.HCError(f"merge_topk: part {i} has {len(part)} selections, not {k}")
+        for j, p in enumerate(part):
+            arr[i * k + j] = joint_selection_from_dict(p) if isinstance(p, dict) else joint_selection_struct(p)
+    offs = np.ascontiguousarray(path_offsets if n else [0], np.int32)
+    out = (_abi.hcTrifocalSelection * k)()
+    _abi.lib().hc_pose_merge_topk(n, k, C.cast(arr, C.c_void_p), _abi.ptr(offs), C.cast(out, C.c_void_p))
+    return [joint_selection_dict(s) for s in out]
+
+
+def select_refined(tracks: torch.Tensor, converge: torch.Tensor, edgels: torch.Tensor, K: torch.Tensor, k: int = 8,
+                   iterations: int = 10, min_inliers: int = 16, stream=None):
+    """Joint pose support, the k best candidates, their refinement and the
+    selection among the refined ones, enqueued on one stream with a single
+    synchronisation at the end.  Returns (best dict, info); info: joint (the
+    joint call's winner, = candidate 0), best_rank, candidates and refined
+    ([dict] * k), refined_inliers ([int] * k, -1 for a "none" rank) and reports."""
+    what = "select_refined"
+    k = _check_k(k, what)
+    _refine_settings(iterations, min_inliers, what)
+    dev = tracks.device
+    n = converge.numel()
+    inl = torch.empty((n, 3), dtype=torch.int32, device=dev)
+    sel = torch.empty(JOINT_SEL_BYTES, dtype=torch.uint8, device=dev)
+    stream = stream if stream is not None else torch.cuda.current_stream(dev)
+    launch_pose_support_joint(tracks, converge, edgels, K, inl, sel, stream)
+    cand = launch_topk_joint(tracks, inl, k, stream=stream)
+    out = launch_refine_topk(cand, edgels, K, iterations, min_inliers, stream)
+    stream.synchronize()
+    d = _refine_topk_dicts(*out, 1, k)[0]
+    info = dict(joint=joint_selection_dict(joint_selection_struct(sel)), best_rank=d["best_rank"],
+                candidates=_selection_dicts(cand, k), refined=d["refined"],
+                refined_inliers=[r["inliers"] for r in d["refined"]], reports=d["reports"])
+    return d["best"], info
 
 
 def residuals(data: RansacData, sel: dict):
