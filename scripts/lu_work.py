@@ -34,7 +34,7 @@ def main():
     fn = L.hc_diag_luwork
     fn.argtypes = [C.POINTER(C.c_ulonglong), C.c_int]
     fn.restype = C.c_int
-    out = (C.c_ulonglong * 11)()   # DIAG_LUWORK_WORDS (csrc/hc_lu.hpp)
+    out = (C.c_ulonglong * 42)()   # DIAG_LUWORK_WORDS (csrc/hc_lu.hpp)
     dev = torch.device("cuda:0")
     problem = load_problem()
     argv = sys.argv[1:]
@@ -90,6 +90,11 @@ def main():
            "wave_solves": wsolves,
            "live_groups_per_wave_solve": groups / max(1, wsolves),
            "rare_steps_per_wave_solve": rare / max(1, wsolves),
+           # per pivot step, counted where they happen (solves that end in a dense re-solve
+           # included), and the wave-solves a fused level 0..3 would hand to its fallback
+           "rare_steps_at": [int(out[11 + i]) for i in range(30)],
+           "wave_solves_rare_in_fusable_steps": int(out[41]),
+           "wave_solves_rare_in_fusable_steps_frac": int(out[41]) / max(1, wsolves),
            "wave_stages": sum(ev),
            "rhs_eval_kinds": {"mixed": ev[0], "dHdt_only": ev[1], "H_only": ev[2]},
            "prefix_rebuilds": int(out[9]),

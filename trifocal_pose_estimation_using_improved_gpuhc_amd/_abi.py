@@ -259,6 +259,15 @@ TOPK_SIGNATURES = (
 )
 TOPK_DECLARED_SYMBOLS = tuple(s.name for s in TOPK_SIGNATURES)
 
+# include/lu/hc_lu_testing.h, the fused LU levels' test hooks beside
+# include/hc_trifocal_testing.h: its table, bound and checked the same way
+# (tests/test_lu_levels.py)
+LU_SIGNATURES = (
+    Sig("hc_lu_step_level", _i, (_i,), True),
+    Sig("hc_cgesv_30x30_struct_batched", _ST, (_i, _p, _p, _p, _p), True),
+)
+LU_DECLARED_SYMBOLS = tuple(s.name for s in LU_SIGNATURES)
+
 _lib = None
 
 
@@ -274,7 +283,7 @@ def lib() -> C.CDLL:
         # instead of pulling a second HIP/HSA runtime from /opt/rocm.
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
-        for s in SIGNATURES + P2C_SIGNATURES + REFINE_SIGNATURES + TOPK_SIGNATURES:
+        for s in SIGNATURES + P2C_SIGNATURES + REFINE_SIGNATURES + TOPK_SIGNATURES + LU_SIGNATURES:
             fn = getattr(L, s.name, None)
             if fn is None:
                 if s.optional:

@@ -37,6 +37,57 @@ __global__ void __launch_bounds__(WG_THREADS) k_cgesv(int n, const cf *__restric
     if (ok) X[(size_t)sys * NV + r] = x;
 }
 
+// The throughput tracker's solve alone: lu_solve with the template arguments of
+// hc_track_body.inc where ABSTAB holds (sparse, the problem's structure, the
+// caller's finiteness verdict), row patterns from LU_STRUCT_PAT, and on `redo`
+// the tracker's fallback: the system loaded again and solved densely.  Every
+// entry outside LU_STRUCT_PAT must be zero: k_cgesv_struct_check sets *bad
+// otherwise, and the host launches the solve only when it stays 0
+// (hc_cgesv_30x30_struct_batched).
+__global__ void __launch_bounds__(WG_THREADS) k_cgesv_struct_check(int n, const cf *__restrict__ A,
+                                                                   unsigned *__restrict__ bad) {
+    const size_t i = (size_t)blockIdx.x * WG_THREADS + threadIdx.x;   // one thread per row
+    if (i >= (size_t)n * NV) return;
+    const uint32_t pat = LU_STRUCT_PAT[i % NV];
+    bool out = false;
+    for (int c = 0; c < NV; c++) {
+        const cf a = A[i * NV + c];
+        // NaN counts as non-zero
+        if (!((pat >> c) & 1u) && (a.x != 0.0f || a.y != 0.0f)) out = true;
+    }
+    if (out) *bad = 1u;
+}
+__global__ void __launch_bounds__(WG_THREADS) k_cgesv_struct(int n, const cf *__restrict__ A,
+                                                             const cf *__restrict__ B, cf *__restrict__ X) {
+    __shared__ LUBuf s_lu[2 * WAVES_PER_WG];
+    __shared__ __attribute__((aligned(16))) cf s_scr[2 * WAVES_PER_WG][LU_SCRATCH_FUSED_CF];
+    const int lane = lane_id();
+    const int r = lane & 31;
+    const int sys = (blockIdx.x * WAVES_PER_WG + threadIdx.x / WAVE) * 2 + (lane >> 5);
+    const bool ok = sys < n && r < NV;
+    cf rA[NV];
+    pf2 sq = {0.0f, 0.0f};   // the entries' sums of squares, as eval_hx_terms_abs takes them
+#pragma unroll
+    for (int c = 0; c < NV; c++) {
+        rA[c] = ok ? A[((size_t)sys * NV + r) * NV + c] : cmk(0.0f, 0.0f);
+        sq.x = __builtin_fmaf(rA[c].x, rA[c].x, sq.x);
+        sq.y = __builtin_fmaf(rA[c].y, rA[c].y, sq.y);
+    }
+    const bool ent_bad = __ballot(!(sq.x + sq.y < __builtin_inff())) != 0ull;
+    const uint32_t pat = r < NV ? LU_STRUCT_PAT[r] : 0u;
+    const cf rB = ok ? B[(size_t)sys * NV + r] : cmk(0.0f, 0.0f);
+    LUBuf &LB = s_lu[(threadIdx.x / WAVE) * 2 + (lane >> 5)];
+    cf *scr = s_scr[(threadIdx.x / WAVE) * 2 + (lane >> 5)];
+    bool redo;
+    cf x = lu_solve<false, 0, true, true, true>(rA, rB, lane, pat, LB, scr, redo, __ballot(sys < n), ent_bad);
+    if (__builtin_expect(redo, 0)) {
+#pragma unroll
+        for (int c = 0; c < NV; c++) rA[c] = ok ? A[((size_t)sys * NV + r) * NV + c] : cmk(0.0f, 0.0f);
+        x = lu_solve<true>(rA, rB, lane, pat, LB, scr, redo);
+    }
+    if (ok) X[(size_t)sys * NV + r] = x;
+}
+
 
 // dH/dx, dH/dt, H at n points: one point per half-wave
 __global__ void __launch_bounds__(WG_THREADS) k_eval(int n, const Workspace *ws, const cf *__restrict__ X,

@@ -28,6 +28,7 @@
 #include "hc_p2c.hpp"
 #include "../../include/hc_trifocal_testing.h"
 #include "../../include/p2c/hc_trifocal_p2c.h"
+#include "../../include/lu/hc_lu_testing.h"
 
 #include <atomic>
 #include <climits>
@@ -421,6 +422,37 @@ hcStatus hc_cgesv_30x30_batched(int n, const hcComplex *A, const hcComplex *b, h
     return hc::launch_status(HC_ERROR_LAUNCH);
 }
 
+// tests only (include/lu/hc_lu_testing.h): the throughput tracker's solve on
+// systems within the compiled-in structure.  Blocks: the structure check's
+// verdict is read back before the solve is launched.
+hcStatus hc_cgesv_30x30_struct_batched(int n, const hcComplex *A, const hcComplex *b, hcComplex *x, hcStream stream) {
+    if (n < 0 || (n > 0 && (!A || !b || !x))) return HC_ERROR_INVALID_VALUE;
+    if (n == 0) return HC_SUCCESS;
+    hipStream_t s = (hipStream_t)stream;
+    (void)hipGetLastError();
+    unsigned *bad = nullptr, h_bad = 0u;
+    if ((hc::g_last_hip_error = hipMalloc((void **)&bad, sizeof(unsigned))) != hipSuccess) return HC_ERROR_DEVICE;
+    hipError_t e = hipMemsetAsync(bad, 0, sizeof(unsigned), s);
+    if (e == hipSuccess) {
+        const size_t rows = (size_t)n * hc::NV;
+        hipLaunchKernelGGL(hc::k_cgesv_struct_check, dim3((unsigned)((rows + hc::WG_THREADS - 1) / hc::WG_THREADS)),
+                           dim3(hc::WG_THREADS), 0, s, n, (const hc::cf *)A, bad);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&h_bad, bad, sizeof(unsigned), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    (void)hipFree(bad);
+    if (e != hipSuccess) {
+        hc::g_last_hip_error = e;
+        return HC_ERROR_LAUNCH;
+    }
+    if (h_bad != 0u) return HC_ERROR_INVALID_VALUE;
+    const int per = 2 * hc::WAVES_PER_WG;
+    hipLaunchKernelGGL(hc::k_cgesv_struct, dim3((n + per - 1) / per), dim3(hc::WG_THREADS), 0, s, n,
+                       (const hc::cf *)A, (const hc::cf *)b, (hc::cf *)x);
+    return hc::launch_status(HC_ERROR_LAUNCH);
+}
+
 hcStatus hc_trifocal_eval_batched(int n, const int32_t *unified_index, const hcComplex *x, const hcComplex *p,
                                   const hcComplex *d, hcComplex *Hx, hcComplex *Ht, hcComplex *H, void *workspace,
                                   size_t workspace_bytes, hcStream stream) {
@@ -543,6 +575,7 @@ int hc_trifocal_abi_version(void) { return HC_TRIFOCAL_ABI_VERSION; }
 unsigned hc_lu_struct_pattern(int row) { return row >= 0 && row < hc::NV ? hc::LU_STRUCT_PAT[row] : 0u; }
 unsigned hc_lu_candidates(int step) { return step >= 0 && step < hc::NV ? hc::LU_BOUND.cand[step] : 0u; }
 int hc_lu_search_span(int step) { return step >= 0 && step < hc::NV ? hc::lu_search_span(step) : -1; }
+int hc_lu_step_level(int step) { return step >= 0 && step < hc::NV ? hc::LU_LEVELS.level[step] : -1; }
 int hc_lu_group_class(int step, int group) {
     if (step < 0 || step >= hc::NV - 1 || group < 0 || group >= hc::LuChunks::count(step)) return -1;
     return hc::lu_group_class(step, group);
@@ -579,7 +612,7 @@ void hc_trifocal_set_small_launch(int mode) {
 void hc_trifocal_set_retry_reuse(int on) { hc::g_retry_reuse.store(on ? 1 : 0, std::memory_order_relaxed); }
 
 const char *hc_trifocal_version(void) {
-    return "hc_trifocal gfx950 v10.9 (2 paths/wave, structurally sparse LDS-broadcast LU with lean pivot steps, "
+    return "hc_trifocal gfx950 v10.10 (2 paths/wave, structurally sparse LDS-broadcast LU with lean pivot steps fused by level, "
            "one exec region per pivot step for the eligible rows with the column groups through scratch windows, "
            "column groups by structural class (never-fillable groups untested, always-live groups unconditional), "
            "pivot search narrowed to the candidate rows' DPP group "

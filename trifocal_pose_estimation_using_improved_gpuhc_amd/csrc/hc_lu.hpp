@@ -65,6 +65,8 @@
 // re-solve evaluates dH/dx again).
 #pragma once
 
+#include <initializer_list>
+
 #include "hc_eval.hpp"
 
 namespace hc {
@@ -273,6 +275,82 @@ constexpr bool lu_classes_consistent() {   // no measured-always group is provab
 }
 static_assert(lu_classes_consistent(), "LU_ALWAYS names a provably dead group");
 
+// Independent pivot steps.  A step reads and writes only its candidate rows
+// (cand[I]: every other row holds an exact zero in column I, so it neither
+// wins the search nor takes a multiple of the pivot row), so two steps whose
+// candidate sets are disjoint read nothing the other writes and commute
+// exactly.  level[j] = 1 + max level[i] over the earlier steps i whose
+// candidates meet step j's (0 without one): the steps of one level are
+// pairwise independent, and a level's steps come after every step of the
+// levels below that they depend on.  A step is fusable when its candidates are
+// one or two triples of adjacent rows (at most LU_FUSE_ROWS rows: what a
+// chain-segmented pivot search covers); a level's fusable steps can run as one
+// step.  For this problem they are steps 0..17 in four levels -- a forest of
+// depth 4 that the forward elimination walks as 18 serial steps; step 18 is
+// on level 3 as well but reduces over 15 rows and stays sequential with 19..29.
+constexpr int LU_FUSE_ROWS = 6;
+struct LuLevels {
+    int level[NV];          // level of step I
+    int nlevels;            // levels that hold a fusable step (they are 0 .. nlevels - 1)
+    uint32_t fused[NV];     // fused[l]: the fusable steps of level l (bit I)
+    uint32_t rows[NV];      // rows[l]: the rows those steps work on (bit r)
+    uint32_t cols[NV];      // cols[l]: the columns they can touch, OR of LU_BOUND.s
+};
+constexpr int lu_popcount(uint32_t x) { int n = 0; for (; x; x &= x - 1u) n++; return n; }
+constexpr bool lu_step_fusable(int I) {
+    const int n = lu_popcount(LU_BOUND.cand[I]);
+    return n > 0 && n <= LU_FUSE_ROWS;
+}
+constexpr LuLevels lu_struct_levels() {
+    LuLevels v{};
+    for (int j = 0; j < NV; j++) {
+        int l = 0;
+        for (int i = 0; i < j; i++)
+            if ((LU_BOUND.cand[i] & LU_BOUND.cand[j]) != 0u && v.level[i] + 1 > l) l = v.level[i] + 1;
+        v.level[j] = l;
+        if (lu_step_fusable(j)) {
+            v.fused[l] |= 1u << j;
+            v.rows[l] |= LU_BOUND.cand[j];
+            v.cols[l] |= LU_BOUND.s[j];
+            if (l + 1 > v.nlevels) v.nlevels = l + 1;
+        }
+    }
+    return v;
+}
+constexpr LuLevels LU_LEVELS = lu_struct_levels();
+constexpr bool lu_levels_disjoint() {   // the members of a level have pairwise disjoint candidates
+    for (int i = 0; i < NV; i++)
+        for (int j = i + 1; j < NV; j++)
+            if (LU_LEVELS.level[i] == LU_LEVELS.level[j] && (LU_BOUND.cand[i] & LU_BOUND.cand[j]) != 0u) return false;
+    return true;
+}
+constexpr bool lu_levels_ordered() {   // a fused step's dependencies are fused steps of lower levels
+    for (int j = 0; j < NV; j++)
+        for (int i = 0; i < j; i++)
+            if (lu_step_fusable(j) && (LU_BOUND.cand[i] & LU_BOUND.cand[j]) != 0u &&
+                !(lu_step_fusable(i) && LU_LEVELS.level[i] < LU_LEVELS.level[j])) return false;
+    return true;
+}
+constexpr uint32_t lu_fused_steps() {
+    uint32_t m = 0u;
+    for (int l = 0; l < LU_LEVELS.nlevels; l++) m |= LU_LEVELS.fused[l];
+    return m;
+}
+constexpr uint32_t lu_bits(std::initializer_list<int> v) {
+    uint32_t m = 0u;
+    for (int b : v) m |= 1u << b;
+    return m;
+}
+static_assert(lu_levels_disjoint(), "two steps of one level share a candidate row");
+static_assert(lu_levels_ordered(), "a fused step depends on a step outside the lower fused levels");
+static_assert(lu_fused_steps() == (1u << 18) - 1u, "the fused levels cover exactly steps 0..17");
+static_assert(LU_LEVELS.nlevels == 4 && LU_LEVELS.fused[0] == lu_bits({0, 1, 2, 5, 8, 9, 10, 11}) &&
+              LU_LEVELS.fused[1] == lu_bits({3, 4, 12, 15}) && LU_LEVELS.fused[2] == lu_bits({6, 7, 13, 16}) &&
+              LU_LEVELS.fused[3] == lu_bits({14, 17}), "the levels of DESIGN.md §3.5");
+static_assert(LU_LEVELS.rows[0] == (1u << NV) - 1u && LU_LEVELS.rows[1] == (LU_LEVELS.rows[0] & ~lu_bits({0, 1, 2, 9, 10, 11})) &&
+              LU_LEVELS.rows[2] == LU_LEVELS.rows[1] && LU_LEVELS.rows[3] == (0x3FFC0000u & LU_LEVELS.rows[0]),
+              "the rows the levels work on");
+
 // Group tests on one bit: gbits = pmw | pmw >> 1 | pmw >> 2 | pmw >> 3, so bit J
 // says "some column of J..J+3 may be non-zero" and a group test is s_bitcmp1
 // + s_cbranch (the compiler keeps an s_cmp after a multi-bit s_and).
@@ -297,10 +375,14 @@ __device__ __forceinline__ bool group_live(uint32_t pmw, uint32_t gb) {
 // solves); wave-level: [3] sparse wave-solves, [4] live column groups, [5] rare
 // pivot steps; [6..8] stages whose right-hand side ran the mixed / dH/dt-only /
 // H-only evaluation, [9] stages that rebuilt the prefix tables (k_track),
-// [10] path-level stage 0s taken from the kept slope of a rejected step (retry reuse)
-constexpr int DIAG_LUWORK_WORDS = 11;
+// [10] path-level stage 0s taken from the kept slope of a rejected step (retry reuse);
+// [11 + I] rare pivot steps of the sparse wave-solves at step I (counted where they
+// happen, also in solves that end in `redo`), [41] sparse wave-solves with a rare
+// step among the fusable steps 0..17 (what a fused level hands to its fallback)
+constexpr int DIAG_LUWORK_RARE_AT = 11, DIAG_LUWORK_RARE_FUSABLE = DIAG_LUWORK_RARE_AT + NV;
+constexpr int DIAG_LUWORK_WORDS = DIAG_LUWORK_RARE_FUSABLE + 1;
 __device__ unsigned long long g_diag_luwork[DIAG_LUWORK_WORDS];
-struct LuWork { unsigned long long acc, mask, groups, rare, excl; };   // mask: lanes whose work counts (active
+struct LuWork { unsigned long long acc, mask, groups, rare, excl, rare_fusable; };   // mask: lanes whose work counts (active
                                                                       // path slots); excl: lanes that update by l = 0
 #define HC_LU_WORK(ncols) (lu_work_acc.acc += (unsigned long long)(ncols) * \
     (unsigned long long)__builtin_popcountll(__builtin_amdgcn_read_exec() & lu_work_acc.mask & ~lu_work_acc.excl))
@@ -644,14 +726,250 @@ __device__ __forceinline__ void lu_step_body(cf (&rA)[NV], cf &rB, int &rowid, u
     lu_store_update<I, 0>(rA, cmk(lp.x, lp.y), pmw, gb, L, is_piv, below HC_LU_WORK_PASS);
 }
 
+// ---------------------------------------------------------------- fused levels
+// One step for all the fusable steps of a level (LU_LEVELS; the throughput
+// tracker's solve only: lu_solve<..., FUSE>).  The steps' candidate sets are
+// pairwise disjoint "chains" of one or two lane triples, and every lane of a
+// chain does for its own chain's column what a step does for column I:
+//  * candidate: the lane's entry in its chain's column (a select over the
+//    level's members on static lane masks); 1 / candidate once;
+//  * search: the maximum key over the lane's own chain -- inside the triple
+//    with four DPP wave shifts masked by the lane's place in it, across the two
+//    triples of a 6-row chain with one ds_bpermute (rows 15..17 cross the
+//    16-lane DPP row).  One maximum per chain and half, all in the fast
+//    reciprocal range, or the solve leaves the fused path: `redo` (the labels
+//    inside a level are not sequential, so the rare path's first-position rule
+//    cannot be applied here; the dense re-solve is exact);
+//  * broadcast and update: chain k of the level owns a pivot-row window
+//    scratch[LU_SCRATCH_CF + 2k + J] for column pair J; its pivot lane writes
+//    there, every other eligible lane to its own window scratch[2r + J] as in a
+//    single step (so the store needs no exec switch), and every lane reads its
+//    own chain's window.  1/pivot and the rhs travel in pair 0.  The column
+//    pairs are those that hold a column of LU_LEVELS.cols, untested: where a
+//    chain's pivot row has no such column it holds an exact zero (equivalence
+//    3 of DESIGN.md §4).  A pair may hold a member's own pivot column: the
+//    rows below then take a_I - l * pivot there, a value nothing reads (column
+//    I of a row that is not step I's pivot row is dead after the multiplier;
+//    the back substitution's unmasked update only feeds right-hand sides that
+//    are dead as well);
+//  * pattern: a row that holds its chain's column takes the member's bound
+//    LU_BOUND.s (a superset of the pivot rows' patterns);
+//  * row labels: the members' relabels one after the other in increasing I,
+//    from the pivot ballot (v_readlane of the pivot lanes' labels).
+constexpr int lu_level_count(int lv) { return lu_popcount(LU_LEVELS.fused[lv]); }
+constexpr int lu_level_member(int lv, int k) {   // the k-th fusable step of level lv
+    for (int i = 0; i < NV; i++)
+        if ((LU_LEVELS.fused[lv] >> i) & 1u) {
+            if (k == 0) return i;
+            k--;
+        }
+    return -1;
+}
+// rows whose chain partner triple is `off` lanes away (0: rows of 3-row chains)
+constexpr int lu_partner_off(int lv, int row) {
+    for (int k = 0; k < lu_level_count(lv); k++) {
+        const uint32_t c = LU_BOUND.cand[lu_level_member(lv, k)];
+        if (!((c >> row) & 1u) || lu_popcount(c) <= 3) continue;
+        int lo = 0, hi = 31;
+        while (!((c >> lo) & 1u)) lo++;
+        while (!((c >> hi) & 1u)) hi--;
+        return row < lo + 3 ? (hi - 2) - lo : lo - (hi - 2);
+    }
+    return 0;
+}
+constexpr uint32_t lu_partner_rows(int lv, int off) {
+    uint32_t m = 0u;
+    for (int r = 0; r < NV; r++)
+        if (lu_partner_off(lv, r) == off) m |= 1u << r;
+    return m;
+}
+constexpr bool lu_chains_are_triples() {   // every fusable candidate set: one or two aligned lane triples
+    for (int i = 0; i < NV; i++) {
+        if (!lu_step_fusable(i)) continue;
+        uint32_t c = LU_BOUND.cand[i], t = 0u;
+        for (int q = 0; q < NV; q += 3)
+            if (((c >> q) & 7u) == 7u) t |= 7u << q;
+        if (t != c) return false;
+    }
+    return true;
+}
+static_assert(lu_chains_are_triples(), "a fusable step's candidates are not whole lane triples");
+constexpr uint32_t lu_member_cols(int lv) { return LU_LEVELS.fused[lv]; }   // bit I: step I pivots column I
+constexpr int LU_CHAIN_WIN0 = 2 * 31 + 32;                       // (= LU_SCRATCH_CF, below)
+constexpr int LU_SCRATCH_FUSED_CF = LU_CHAIN_WIN0 + 2 * 7 + 32;   // the chains' pivot-row windows behind the rows'
+constexpr unsigned long long lu_both(uint32_t m) { return (unsigned long long)m | ((unsigned long long)m << 32); }
+constexpr uint32_t LU_TRI0 = 0x09249249u, LU_TRI1 = LU_TRI0 << 1, LU_TRI2 = LU_TRI0 << 2;   // rows 3q, 3q + 1, 3q + 2 (< 30)
+constexpr int DPP_WAVE_SHL1 = 0x130, DPP_WAVE_SHR1 = 0x138;   // lane i takes lane i + 1 / i - 1 (GFX9)
+
+// the levels lu_solve<..., FUSE> runs fused (bit l: level l; a prefix of the
+// levels, since a level's steps need every lower level done): all four.  The
+// A/B variants are this constant set to 0 (no level: the sequential steps),
+// 1, 3 or 7; the unfused steps then run one by one between the fused levels.
+constexpr uint32_t LU_FUSE_LEVELS = 0xF;
+static_assert((LU_FUSE_LEVELS & (LU_FUSE_LEVELS + 1u)) == 0u && LU_FUSE_LEVELS < (1u << LU_LEVELS.nlevels),
+              "the fused levels are a prefix of the levels");
+constexpr bool lu_step_fused(int I) { return lu_step_fusable(I) && ((LU_FUSE_LEVELS >> LU_LEVELS.level[I]) & 1u); }
+
+// each lane's candidate, its member's bound and its chain's window offset
+template <int LV, int K>
+__device__ __forceinline__ void lvl_pick(const cf (&rA)[NV], pf2 &c, uint32_t &bnd, int &cwo) {
+    if constexpr (K < lu_level_count(LV)) {
+        constexpr int I = lu_level_member(LV, K);
+        const bool in = __builtin_amdgcn_inverse_ballot_w64(lu_both(LU_BOUND.cand[I]));
+        c.x = in ? rA[I].x : c.x;
+        c.y = in ? rA[I].y : c.y;
+        bnd = in ? LU_BOUND.s[I] : bnd;
+        cwo = in ? LU_CHAIN_WIN0 + 2 * K : cwo;
+        lvl_pick<LV, K + 1>(rA, c, bnd, cwo);
+    }
+}
+// the members' relabels in increasing I (:70-82): the pivot lane takes label
+// I, the lane that held I takes the pivot lane's old label.  Over the whole
+// solve the order is level by level (0, 1, 2, 5, 8..11, then 3, 4, 12, 15, ...),
+// not 0..17, and the labels before step 18 are still exactly the sequential
+// ones: a relabel exchanges the label values I and label(p_I), the pivot lanes
+// p_I are chosen from the entries, never from the labels, and two relabels with
+// different pivot lanes p, q commute -- both orders end with p at I, q at J,
+// and the former holders of I and J (where they are not p or q) at the old
+// labels of p and q; if p held J, the holder of I ends with q's old label
+// either way.  So any order of the 18 relabels gives the same labels.
+template <int LV, int K>
+__device__ __forceinline__ void lvl_relabel(int &rowid, unsigned long long m, int hb) {
+    if constexpr (K < lu_level_count(LV)) {
+        constexpr int I = lu_level_member(LV, K);
+        const unsigned long long mi = and_halves<LU_BOUND.cand[I]>(m);
+        const int p0 = __builtin_amdgcn_readlane(rowid, __builtin_ctz((unsigned)mi));
+        const int p1 = __builtin_amdgcn_readlane(rowid, 32 + __builtin_ctz((unsigned)(mi >> 32)));
+        const int piv_pos = hb ? p1 : p0;
+        const bool is_p = __builtin_amdgcn_inverse_ballot_w64(mi);
+        rowid = is_p ? I : (rowid == I ? piv_pos : rowid);
+        lvl_relabel<LV, K + 1>(rowid, m, hb);
+    }
+}
+// the level's column pairs J, J + 1 (J even) inside the eligible rows' region
+template <int LV, int J>
+__device__ __forceinline__ void lvl_groups(cf (&rA)[NV], const pf2 &l, cf *wrow, const cf *cw) {
+    if constexpr (J < NV) {
+        if constexpr (((LU_LEVELS.cols[LV] >> J) & 3u) != 0u) {
+            st4(&wrow[J], rA[J], rA[J + 1]);
+            wave_lds_sync();
+            cf u[2];
+            ld4(&cw[J], u[0], u[1]);
+#pragma unroll
+            for (int q = 0; q < 2; q++) {
+                const pf2 v = pcmsub(pf2{rA[J + q].x, rA[J + q].y}, l, pf2{u[q].x, u[q].y});
+                rA[J + q] = cmk(v.x, v.y);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        lvl_groups<LV, J + 2>(rA, l, wrow, cw);
+    }
+}
+// returns false when the level met a rare condition (nothing is changed then)
+template <int LV>
+__device__ __forceinline__ bool lu_level(cf (&rA)[NV], cf &rB, int &rowid, uint32_t &pat, int lane, int r, int hb,
+                                         PivF &my, cf *scr, unsigned long long &elig_m HC_LU_WORK_ARG) {
+    constexpr int CNT = lu_level_count(LV), I0 = lu_level_member(LV, 0);
+    constexpr uint32_t ROWS = LU_LEVELS.rows[LV];
+    HC_ISA_MARK_I("lu_search", I0);
+    pf2 c = {0.0f, 0.0f};
+    uint32_t bnd = 0u;
+    int cwo = 0;
+    lvl_pick<LV, 0>(rA, c, bnd, cwo);
+    const float v = __builtin_fabsf(c.x) + __builtin_fabsf(c.y);          // :55
+    pf2 oo_s;
+    const pf2 reg_s = recip_fast(c, v, oo_s);
+    const unsigned long long lv_elig = and_halves<ROWS>(elig_m);
+    const bool elig = __builtin_amdgcn_inverse_ballot_w64(lv_elig);
+    const int key = elig ? __float_as_int(v) : -1;
+    // the maximum over the lane's triple: the neighbours one and two lanes up
+    // and down, each only where it lies in the same triple
+    int mx;
+    {
+        const int u1 = dpp_i<DPP_WAVE_SHL1>(key), u2 = dpp_i<DPP_WAVE_SHL1>(u1);
+        const int d1 = dpp_i<DPP_WAVE_SHR1>(key), d2 = dpp_i<DPP_WAVE_SHR1>(d1);
+        const int a = __builtin_amdgcn_inverse_ballot_w64(lu_both(LU_TRI0 | LU_TRI1)) ? u1 : -1;
+        const int b = __builtin_amdgcn_inverse_ballot_w64(lu_both(LU_TRI0)) ? u2 : -1;
+        const int e = __builtin_amdgcn_inverse_ballot_w64(lu_both(LU_TRI1 | LU_TRI2)) ? d1 : -1;
+        const int f = __builtin_amdgcn_inverse_ballot_w64(lu_both(LU_TRI2)) ? d2 : -1;
+        mx = max(max(key, a), max(b, max(e, f)));
+    }
+    // ... and over the partner triple of a 6-row chain
+    constexpr uint32_t UP9 = lu_partner_rows(LV, 9), DN9 = lu_partner_rows(LV, -9), UP6 = lu_partner_rows(LV, 6),
+                       DN6 = lu_partner_rows(LV, -6);
+    static_assert((UP9 | DN9 | UP6 | DN6 | lu_partner_rows(LV, 0)) == (1u << NV) - 1u, "partner triples 6 or 9 lanes away");
+    if constexpr ((UP9 | DN9 | UP6 | DN6) != 0u) {
+        int pl = lane;
+        if constexpr (UP9 != 0u) pl = __builtin_amdgcn_inverse_ballot_w64(lu_both(UP9)) ? lane + 9 : pl;
+        if constexpr (DN9 != 0u) pl = __builtin_amdgcn_inverse_ballot_w64(lu_both(DN9)) ? lane - 9 : pl;
+        if constexpr (UP6 != 0u) pl = __builtin_amdgcn_inverse_ballot_w64(lu_both(UP6)) ? lane + 6 : pl;
+        if constexpr (DN6 != 0u) pl = __builtin_amdgcn_inverse_ballot_w64(lu_both(DN6)) ? lane - 6 : pl;
+        mx = max(mx, __builtin_amdgcn_ds_bpermute(pl << 2, mx));
+    }
+    // one maximum per chain and half, every one in the fast reciprocal range
+    // (a lane outside the level's rows matches its own key: masked off)
+    const unsigned long long m = and_halves<ROWS>(__builtin_amdgcn_ballot_w64(key == mx));
+    const unsigned long long bad = and_halves<ROWS>(__builtin_amdgcn_ballot_w64(!rcp_fast_bits(mx)));
+    if (__builtin_expect((__builtin_popcountll(m) != 2 * CNT) | (bad != 0ull), 0)) return false;
+    const bool is_piv = __builtin_amdgcn_inverse_ballot_w64(m);
+    HC_ISA_MARK_I("lu_store", I0);
+    const cf *cw = scr + (cwo - 2 * r);
+    cf *wrow = is_piv ? const_cast<cf *>(cw) : scr;
+    st4(&wrow[0], cmk(reg_s.x, reg_s.y), rB);
+    wave_lds_sync();
+    HC_ISA_MARK_I("lu_rcp", I0);
+    cf reg, sB0;
+    ld4(&cw[0], reg, sB0);
+    if (is_piv) my.oo = oo_s;
+    asm volatile("" : "+v"(my.oo));
+    lvl_relabel<LV, 0>(rowid, m, hb);
+    HC_ISA_MARK_I("lu_update", I0);
+#ifdef HC_DIAG_LUWORK
+    {   // the level's column pairs x the eligible rows below the pivots (wave-uniform)
+        int pairs = 0;
+        for (int j = 0; j < NV; j += 2) pairs += ((LU_LEVELS.cols[LV] >> j) & 3u) != 0u;
+        lu_work_acc.acc += 2ull * (unsigned long long)pairs *
+                           (unsigned long long)__builtin_popcountll(lv_elig & lu_work_acc.mask & ~m);
+        lu_work_acc.groups += (unsigned long long)pairs;
+    }
+#endif
+    if (elig) {
+        HC_ISA_MARK_I("lu_mult", I0);
+        const pf2 lq = pcmul(c, pf2{reg.x, reg.y});
+        const pf2 lp = {is_piv ? 0.0f : lq.x, is_piv ? 0.0f : lq.y};
+        const pf2 bp = pcmsub(pf2{rB.x, rB.y}, lp, pf2{sB0.x, sB0.y});
+        rB = cmk(bp.x, bp.y);
+        pat |= (pat & lu_member_cols(LV)) != 0u ? bnd : 0u;
+        lvl_groups<LV, 0>(rA, lp, wrow, cw);
+    }
+    elig_m &= ~m;
+    return true;
+}
+
 // One pivot step: the pivot search, then lu_step_body.  !DENSE: a pivot
 // outside the fast reciprocal range sets `redo` (the solve goes on with
-// garbage, the caller discards it and solves densely).
-template <int I, bool DENSE, int LAT, bool STRUCT>
+// garbage, the caller discards it and solves densely).  FUSE: the fused steps
+// run as their level at the level's first member (lu_level), and a rare
+// condition there sets `redo` and ends the forward elimination.
+template <int I, bool DENSE, int LAT, bool STRUCT, bool FUSE = false>
 __device__ __forceinline__ void lu_forward(cf (&rA)[NV], cf &rB, int &rowid, uint32_t &pat, int lane, int r, int hb,
                                            bool row_lane, PivF &my, LUBuf &L, cf *scr, bool &redo,
                                            unsigned long long elig_m HC_LU_WORK_ARG) {
-    if constexpr (I < NV) {
+    if constexpr (FUSE && I < NV && lu_step_fused(I < NV ? I : 0)) {
+        constexpr int LV = LU_LEVELS.level[I];
+        if constexpr (lu_level_member(LV, 0) == I) {
+            if (!lu_level<LV>(rA, rB, rowid, pat, lane, r, hb, my, scr, elig_m HC_LU_WORK_PASS)) {
+#ifdef HC_DIAG_LUWORK
+                lu_work_acc.rare++;
+                lu_work_acc.rare_fusable = 1ull;
+#endif
+                redo = true;
+                return;
+            }
+        }
+        lu_forward<I + 1, DENSE, LAT, STRUCT, FUSE>(rA, rB, rowid, pat, lane, r, hb, row_lane, my, L, scr, redo,
+                                                    elig_m HC_LU_WORK_PASS);
+    } else if constexpr (I < NV) {
         HC_ISA_MARK_I("lu_search", I);
         const float v = __builtin_fabsf(rA[I].x) + __builtin_fabsf(rA[I].y);          // :55
         // 1 / own candidate as cuCdivf(1, a_rI) (:66, :84), off the step's critical path:
@@ -702,6 +1020,10 @@ __device__ __forceinline__ void lu_forward(cf (&rA)[NV], cf &rB, int &rowid, uin
             HC_ISA_MARK_I("lu_rare", I);
 #ifdef HC_DIAG_LUWORK
             lu_work_acc.rare++;
+            if constexpr (!DENSE) {
+                if (lane == 0) atomicAdd(&g_diag_luwork[DIAG_LUWORK_RARE_AT + I], 1ull);
+                if (lu_step_fusable(I)) lu_work_acc.rare_fusable = 1ull;
+            }
 #endif
             // rare: NaN at position I wins (:57-64); exact ties: first position wins
             const bool isn = v != v;
@@ -757,8 +1079,8 @@ __device__ __forceinline__ void lu_forward(cf (&rA)[NV], cf &rB, int &rowid, uin
         HC_ISA_MARK_I("lu_pattern", I);
         lu_step_body<I, DENSE, LAT, STRUCT>(rA, rB, rowid, pat, my, L, scr, is_piv, pl0, pl1, reg_s, oo_s,
                                             elig HC_LU_WORK_PASS);
-        lu_forward<I + 1, DENSE, LAT, STRUCT>(rA, rB, rowid, pat, lane, r, hb, row_lane, my, L, scr, redo,
-                                              elig_m & ~piv_m HC_LU_WORK_PASS);
+        lu_forward<I + 1, DENSE, LAT, STRUCT, FUSE>(rA, rB, rowid, pat, lane, r, hb, row_lane, my, L, scr, redo,
+                                                    elig_m & ~piv_m HC_LU_WORK_PASS);
     }
 }
 
@@ -815,15 +1137,20 @@ __device__ __forceinline__ void lu_backward(const cf (&rA)[NV], cf &rB, int rowi
 // rows (row r writes column group J at scratch[2r + J]); the caller's data
 // there is lost.
 constexpr int LU_SCRATCH_CF = 2 * 31 + 32;   // 94: lane r's window scratch[2r .. 2r + 31]
+static_assert(LU_CHAIN_WIN0 == LU_SCRATCH_CF, "the chains' windows start behind the rows' windows");
 // ENTCHK: the caller has made the finiteness check on the entries it gathered
 // the rows from (eval_hx_terms_abs) and passes the wave-uniform verdict in
 // ent_bad; the row loop below is left out.
-template <bool DENSE, int LAT = 0, bool STRUCT = false, bool ENTCHK = false>
+// FUSE (the throughput tracker's solve: !DENSE, LAT == 0, STRUCT): the fusable
+// steps run level by level (lu_level); scratch then has LU_SCRATCH_FUSED_CF
+// entries, and a rare condition inside a level reports `redo` as well.
+template <bool DENSE, int LAT = 0, bool STRUCT = false, bool ENTCHK = false, bool FUSE = false>
 __device__ __forceinline__ cf lu_solve(cf (&rA)[NV], cf rB, int lane, uint32_t pattern, LUBuf &L, cf *scratch,
                                       bool &redo, unsigned long long count_mask = ~0ull, bool ent_bad = false);
-template <bool DENSE, int LAT, bool STRUCT, bool ENTCHK>
+template <bool DENSE, int LAT, bool STRUCT, bool ENTCHK, bool FUSE>
 __device__ __forceinline__ cf lu_solve(cf (&rA)[NV], cf rB, int lane, uint32_t pattern, LUBuf &L, cf *scratch,
                                       bool &redo, unsigned long long count_mask, bool ent_bad) {
+    static_assert(!FUSE || (!DENSE && LAT == 0 && STRUCT), "the fused levels belong to the throughput tracker's solve");
     (void)count_mask;   // diagnostic builds (HC_DIAG_LUWORK): lanes whose executed work is counted
     const int r = lane & 31, hb = lane & 32;
     const bool row_lane = r < NV;
@@ -858,9 +1185,9 @@ __device__ __forceinline__ cf lu_solve(cf (&rA)[NV], cf rB, int lane, uint32_t p
     uint32_t pat = row_lane ? pattern : 0u;
     PivF my{pf2{0.0f, 0.0f}};
 #ifdef HC_DIAG_LUWORK
-    LuWork lu_work_acc{0ull, count_mask, 0ull, 0ull, 0ull};
-    lu_forward<0, DENSE, LAT, STRUCT>(rA, rB, rowid, pat, lane, r, hb, row_lane, my, L, scratch + 2 * r, redo,
-                                      __builtin_amdgcn_ballot_w64(row_lane), lu_work_acc);
+    LuWork lu_work_acc{0ull, count_mask, 0ull, 0ull, 0ull, 0ull};
+    lu_forward<0, DENSE, LAT, STRUCT, FUSE>(rA, rB, rowid, pat, lane, r, hb, row_lane, my, L, scratch + 2 * r, redo,
+                                            __builtin_amdgcn_ballot_w64(row_lane), lu_work_acc);
     const unsigned long long solves = (unsigned long long)__builtin_popcountll(count_mask & __builtin_amdgcn_ballot_w64(row_lane)) / NV;
     if (lane == 0 && !DENSE && !redo) {   // sparse solves that completed, and their work
         atomicAdd(&g_diag_luwork[0], lu_work_acc.acc);
@@ -870,10 +1197,14 @@ __device__ __forceinline__ cf lu_solve(cf (&rA)[NV], cf rB, int lane, uint32_t p
         atomicAdd(&g_diag_luwork[5], lu_work_acc.rare);
     }
     if (lane == 0 && DENSE) atomicAdd(&g_diag_luwork[2], solves);   // dense (re-)solves
+    if (lane == 0 && !DENSE) atomicAdd(&g_diag_luwork[DIAG_LUWORK_RARE_FUSABLE], lu_work_acc.rare_fusable);
 #else
-    lu_forward<0, DENSE, LAT, STRUCT>(rA, rB, rowid, pat, lane, r, hb, row_lane, my, L, scratch + 2 * r, redo,
-                                      __builtin_amdgcn_ballot_w64(row_lane));
+    lu_forward<0, DENSE, LAT, STRUCT, FUSE>(rA, rB, rowid, pat, lane, r, hb, row_lane, my, L, scratch + 2 * r, redo,
+                                            __builtin_amdgcn_ballot_w64(row_lane));
 #endif
+    if constexpr (FUSE) {   // (wave-uniform: the caller solves the system again)
+        if (__builtin_expect(redo, 0)) return cmk(0.0f, 0.0f);
+    }
 #ifdef HC_DIAG_PHASES
     // diagnostic build: the forward / back-substitution boundary of this wave's
     // solve (s_memtime), read by k_track after the solve (g_diag_lu_mid)

@@ -25,6 +25,9 @@
     // (The variant builds that measured the four parts apart are not kept; DESIGN.md section 3.6
     // says how each ABSTAB site below was switched.)
     constexpr bool ABSTAB = !ABORT && !ARCH && LULAT == 0;
+    // the LU's independent pivot steps fused level by level (hc_lu.hpp lu_level): the
+    // headline kernel only; its structure-agnostic twin has no levels to fuse
+    constexpr bool LUFUSE = ABSTAB && LUSTRUCT;
     __shared__ cf s_sp[NPP];
     __shared__ SlotLDS s_slot[2 * WAVES_PER_WG];
     Workspace *ws = a.ws;
@@ -561,11 +564,11 @@
         LUBuf &LB = *reinterpret_cast<LUBuf *>(S.lu);
         // the LU's scratch: the dH/dx entry block, dead once gathered into rA
         // (a dense re-solve evaluates dH/dx again)
-        static_assert(ENT_CAP >= LU_SCRATCH_CF && offsetof(SlotLDS, ent) % 16 == 0, "LU scratch in SlotLDS::ent");
+        static_assert(ENT_CAP - 1 >= LU_SCRATCH_FUSED_CF && offsetof(SlotLDS, ent) % 16 == 0, "LU scratch in SlotLDS::ent");
 #ifdef HC_DIAG_LUWORK
-        cf k = lu_solve<false, LULAT, LUSTRUCT, ABSTAB>(rA, rB, lane_v, row_pat, LB, S.ent, redo, __ballot(act), ent_bad);   // :188 / :224
+        cf k = lu_solve<false, LULAT, LUSTRUCT, ABSTAB, LUFUSE>(rA, rB, lane_v, row_pat, LB, S.ent, redo, __ballot(act), ent_bad);   // :188 / :224
 #else
-        cf k = lu_solve<false, LULAT, LUSTRUCT, ABSTAB>(rA, rB, lane_v, row_pat, LB, S.ent, redo, ~0ull, ent_bad);           // :188 / :224
+        cf k = lu_solve<false, LULAT, LUSTRUCT, ABSTAB, LUFUSE>(rA, rB, lane_v, row_pat, LB, S.ent, redo, ~0ull, ent_bad);           // :188 / :224
 #endif
         HC_ISA_MARK("ctl_redo");
         if (__builtin_expect(redo, 0)) {

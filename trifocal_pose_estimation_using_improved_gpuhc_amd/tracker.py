@@ -449,6 +449,20 @@ def cgesv_batched(A: np.ndarray, b: np.ndarray, device="cuda:0") -> np.ndarray:
     return xt.cpu().numpy()
 
 
+def cgesv_struct_batched(A: np.ndarray, b: np.ndarray, device="cuda:0") -> np.ndarray:
+    """The throughput tracker's structure-specialised solve of n 30x30 complex
+    systems (layout of cgesv_batched).  Raises HCError (HC_ERROR_INVALID_VALUE)
+    when an entry outside the compiled-in structure is non-zero."""
+    dev = _require_gpu(device)
+    At = torch.from_numpy(np.ascontiguousarray(A, np.float32)).to(dev)
+    bt = torch.from_numpy(np.ascontiguousarray(b, np.float32)).to(dev)
+    xt = torch.empty_like(bt)
+    _abi.call("hc_cgesv_30x30_struct_batched", At.shape[0], _abi.ptr(At), _abi.ptr(bt), _abi.ptr(xt),
+              _abi.ptr(torch.cuda.current_stream(dev)))
+    torch.cuda.synchronize(dev)
+    return xt.cpu().numpy()
+
+
 def eval_batched(unified: np.ndarray, x: np.ndarray, p: np.ndarray, d: np.ndarray, device="cuda:0"):
     """Batched dH/dx, dH/dt, H at (x, p) with the tracker's compacted tables."""
     dev = _require_gpu(device)
