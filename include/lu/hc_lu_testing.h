@@ -1,5 +1,5 @@
-/* hc_lu_testing.h -- test hooks of the tracker LU's fused levels
-   (csrc/hc_lu.hpp), beside include/hc_trifocal_testing.h, whose hc_lu_candidates
+/* hc_lu_testing.h -- test hooks of the tracker LU (csrc/hc_lu.hpp): its fused
+   levels, and each of its instantiations alone; beside include/hc_trifocal_testing.h, whose hc_lu_candidates
    and hc_lu_struct_pattern they go with.  No reference counterpart. */
 #ifndef HC_LU_TESTING_H
 #define HC_LU_TESTING_H
@@ -25,6 +25,34 @@ int hc_lu_step_level(int step);
    are checked. */
 hcStatus hc_cgesv_30x30_struct_batched(int n, const hcComplex *A, const hcComplex *b, hcComplex *x,
                                        hcStream stream);
+
+/* The instantiations of the tracker's sparse solve, lu_solve<false, LAT,
+   STRUCT, ENTCHK, FUSE> (csrc/hc_lu.hpp), by the kernels that run them.  A
+   "twin" is the structure-agnostic solve of the kernel named before it, which
+   tracks a table whose structure is not the compiled-in one (e.g. the same
+   system with its equations permuted). */
+typedef enum {
+    HC_LU_VARIANT_THROUGHPUT = 0,      /* k_track<false, ...>:      <0, true, true, true>  (hc_cgesv_30x30_struct_batched) */
+    HC_LU_VARIANT_THROUGHPUT_TWIN = 1, /*                           <0, false, true, false> */
+    HC_LU_VARIANT_ABORT = 2,           /* abort, grouped and gated: <HC_LU_LATB_COLS, true, false, false> */
+    HC_LU_VARIANT_ABORT_TWIN = 3,      /*                           <HC_LU_LATB_COLS, false, false, false> */
+    HC_LU_VARIANT_SMALL = 4,           /* k_track_small:            <HC_SMALL_LAT, true, false, false> */
+    HC_LU_VARIANT_SMALL_TWIN = 5,      /*                           <HC_SMALL_LAT, false, false, false> */
+    HC_LU_VARIANT_ARCHIVED = 6,        /* archived PH / PH_CodeOpt / P2C: <0, true, false, false> */
+    HC_LU_VARIANT_ARCHIVED_TWIN = 7,   /*                           <0, false, false, false> (hc_cgesv_30x30_batched's) */
+    HC_LU_VARIANT_COUNT = 8
+} hcLuVariant;
+
+/* One of those solves alone, in the layout of hc_cgesv_30x30_batched, with the
+   tracker's fallback: the dense solve of the same system where the sparse one
+   asks for it.  The variants with the problem's structure (the even ones) take
+   their row patterns from hc_lu_struct_pattern and return
+   HC_ERROR_INVALID_VALUE, with x untouched, when an entry outside the patterns
+   is non-zero (NaN included); they block until the inputs are checked.  The
+   twins take a row's pattern from its non-zero entries and accept any matrix.
+   HC_ERROR_INVALID_VALUE for a variant outside hcLuVariant. */
+hcStatus hc_cgesv_30x30_variant_batched(int variant, int n, const hcComplex *A, const hcComplex *b, hcComplex *x,
+                                        hcStream stream);
 
 #ifdef __cplusplus
 }

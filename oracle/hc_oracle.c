@@ -288,7 +288,8 @@ void orc_eval_h(const int *dHdt, const float *xf, const float *pf, float *b) {
 /* Thread r owns original row r (rA[r][*], rB[r]); rowid[r] is its logical */
 /* position; pivoting relabels positions instead of moving rows.           */
 /* ====================================================================== */
-static void cgesv_gpu(cf rA[NV][NV], cf *rB, cf *xout) {
+/* trace (optional): ORC_LU_TRACE_WORDS ints per pivot step, see hc_oracle.h.  */
+static void cgesv_gpu_traced(cf rA[NV][NV], cf *rB, cf *xout, int *trace) {
     int rowid[NV];
     float dsx[NV];
     cf sx[NV], sB[NV];
@@ -302,6 +303,12 @@ static void cgesv_gpu(cf rA[NV][NV], cf *rB, cf *xout) {
         const float update = zero ? 0.0f : 1.0f;                                            /* :68 */
         int pl = -1, ql = -1;
         for (int r = 0; r < NV; r++) { if (rowid[r] == mid) pl = r; if (rowid[r] == i) ql = r; }
+        if (trace) {
+            int *t = trace + i * ORC_LU_TRACE_WORDS, bits;
+            memcpy(&bits, &mx, sizeof bits);
+            t[0] = pl; t[1] = bits; t[2] = 0; t[3] = 0; t[4] = dsx[i] != dsx[i];
+            for (int j = i; j < NV; j++) { t[2] += dsx[j] == mx; t[3] += dsx[j] != dsx[j]; }
+        }
         for (int j = i; j < NV; j++) sx[j] = cscale(rA[pl][j], update);                     /* :73-76 */
         const cf sB0 = rB[pl];                                                              /* :77 */
         rowid[pl] = i;                                                                      /* :72 */
@@ -324,13 +331,15 @@ static void cgesv_gpu(cf rA[NV][NV], cf *rB, cf *xout) {
     }
     for (int i = 0; i < NV; i++) xout[i] = sB[i];
 }
+static void cgesv_gpu(cf rA[NV][NV], cf *rB, cf *xout) { cgesv_gpu_traced(rA, rB, xout, NULL); }
 
-void orc_cgesv_gpu(float *Af, const float *bf, float *xf) {
+void orc_cgesv_gpu_trace(float *Af, const float *bf, float *xf, int *trace) {
     cf A[NV][NV], b[NV], x[NV];
     for (int r = 0; r < NV; r++) { for (int c = 0; c < NV; c++) A[r][c] = ld(Af, r * NV + c); b[r] = ld(bf, r); }
-    cgesv_gpu(A, b, x);
+    cgesv_gpu_traced(A, b, x, trace);
     for (int r = 0; r < NV; r++) { st(xf, r, x[r]); for (int c = 0; c < NV; c++) st(Af, r * NV + c, A[r][c]); }
 }
+void orc_cgesv_gpu(float *Af, const float *bf, float *xf) { orc_cgesv_gpu_trace(Af, bf, xf, NULL); }
 
 /* ====================================================================== */
 /* GPU tracker -- gpu-kernels/kernel_GPUHC_..._PH_CodeOpt_TrunPaths.cu:45-290 */

@@ -63,6 +63,16 @@ void orc_eval_h(const int *dHdt, const float *x, const float *p, float *b /* 30*
 /* register-resident LU of dev-cgesv-batched-small.cuh (GPU semantics).
    A row-major 30x30 complex (destroyed), b in, x out (30 complex). */
 void orc_cgesv_gpu(float *A, const float *b, float *x);
+/* The same solve (one body), which also records what each pivot step's search
+   saw: trace[ORC_LU_TRACE_WORDS * i + k] for step i holds
+     0  the original row chosen as the pivot row,
+     1  the bits of the winning key mx = |re| + |im| (:57-64),
+     2  how many eligible positions (i .. 29) hold a key equal to mx,
+     3  how many eligible positions hold a NaN key,
+     4  1 when position i itself holds the NaN (which then wins), else 0.
+   trace may be NULL. */
+#define ORC_LU_TRACE_WORDS 5
+void orc_cgesv_gpu_trace(float *A, const float *b, float *x, int *trace /* 30 * ORC_LU_TRACE_WORDS */);
 /* LAPACK cgesv (getrf + getrs) semantics used by CPU-HC. A column-major.
    Returns info (0 = ok; >0 singular, B untouched as in LAPACK cgesv). */
 int orc_cgesv_lapack(float *A_colmajor, float *B);

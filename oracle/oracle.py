@@ -135,6 +135,23 @@ def cgesv_gpu(A, b):
     return x
 
 
+LU_TRACE_DTYPE = np.dtype([("row", "<i4"), ("key_bits", "<i4"), ("equal", "<i4"), ("nans", "<i4"),
+                           ("nan_at_step", "<i4")])
+
+
+def cgesv_gpu_trace(A, b):
+    """cgesv_gpu (the same C body) and what each pivot step's search saw: a
+    30-record array of the pivot's original row, the bits of the winning key,
+    the eligible positions whose key equals it, the eligible positions whose key
+    is NaN, and whether the step's own position holds the NaN."""
+    A = np.ascontiguousarray(A, np.float32).copy()
+    b = np.ascontiguousarray(b, np.float32)
+    x = np.zeros((NV, 2), np.float32)
+    trace = np.zeros(NV, LU_TRACE_DTYPE)
+    lib().orc_cgesv_gpu_trace(_p(A), _p(b), _p(x), _p(trace))
+    return x, trace
+
+
 def cgesv_lapack(A_rowmajor, b):
     A = np.ascontiguousarray(np.transpose(A_rowmajor, (1, 0, 2)), np.float32).copy()  # col-major
     B = np.ascontiguousarray(b, np.float32).copy()

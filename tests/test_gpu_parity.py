@@ -11,24 +11,10 @@ from checks import (KERNEL_BY_SIZE, SMALL_ALWAYS, SMALL_NEVER, assert_bit_identi
                     assert_matches_oracle, assert_untouched, found_ids, golden, golden_passing, launch_mode,
                     ring_counters, run_cli, scaled_samples, tracked)
 from conftest import same
+from lu_cases import edge_case_systems, extreme_scale_systems
+from lu_cases import jacobians_from_path as _jacobians_from_path
 
 pytestmark = pytest.mark.gpu
-
-
-def _jacobians_from_path(problem, oracle, tgt, dif, n=64, seed=1):
-    """Realistic (x, p, d) points: start solutions pushed along t with random noise."""
-    rng = np.random.default_rng(seed)
-    xs, ps, ds = [], [], []
-    for i in range(n):
-        k = int(rng.integers(0, 312))
-        s = int(rng.integers(0, tgt.shape[0]))
-        x = problem.start_sols[k].copy()
-        x[:30] += (rng.standard_normal((30, 2)) * 10 ** rng.uniform(-4, -1)).astype(np.float32)
-        t = float(np.float32(rng.uniform(0, 1)))
-        xs.append(x)
-        ps.append(oracle.param_homotopy(t, problem.start_params, tgt[s]))
-        ds.append(dif[s])
-    return np.stack(xs), np.stack(ps), np.stack(ds)
 
 
 def test_eval_matches_oracle(problem, oracle, samples100):
@@ -66,15 +52,8 @@ def test_cgesv_edge_cases(oracle):
     """Random dense, exact ties in the pivot column, a zero column (zero pivot)
     and a NaN entry: the kernel follows dev-cgesv-batched-small.cuh semantics."""
     from trifocal_pose_estimation_using_improved_gpuhc_amd.tracker import cgesv_batched
-    rng = np.random.default_rng(11)
-    n = 64
-    A = rng.standard_normal((n, 30, 30, 2)).astype(np.float32)
-    b = rng.standard_normal((n, 30, 2)).astype(np.float32)
-    A[1, :, 0, :] = 1.0              # every row ties in column 0
-    A[2, :, :, :] = np.round(A[2])   # many exact ties throughout
-    A[3, :, 5, :] = 0.0              # zero column -> zero pivot at step 5
-    A[4, 7, 3, 0] = np.nan           # NaN in the matrix
-    A[5, :, :, :] = 0.0              # fully singular
+    A, b = edge_case_systems()
+    n = A.shape[0]
     xg = cgesv_batched(A, b)
     for i in range(n):
         xr = oracle.cgesv_gpu(A[i], b[i])
@@ -93,29 +72,7 @@ def test_cgesv_extreme_scales(problem, oracle, samples100):
     infinity, NaN at the pivot position, denormals, and structurally sparse
     tracker Jacobians at those scales -- bit-exact against the oracle."""
     from trifocal_pose_estimation_using_improved_gpuhc_amd.tracker import cgesv_batched
-    tgt, dif, _ = samples100
-    X, P, D = _jacobians_from_path(problem, oracle, tgt, dif, n=8, seed=5)
-    J = np.stack([oracle.eval_hx(problem.dHdx_index, X[i], P[i]) for i in range(8)])
-    bJ = np.stack([oracle.eval_ht(problem.dHdt_index, X[i], P[i], D[i]) for i in range(8)])
-    rng = np.random.default_rng(12)
-    As, bs = [], []
-    for scale in (2.0 ** -100, 2.0 ** -60, 2.0 ** 60, 2.0 ** 90, 2.0 ** 121):
-        for i in range(4):
-            As.append((J[i] * np.float32(scale)).astype(np.float32))
-            bs.append(bJ[i])
-    A = rng.standard_normal((6, 30, 30, 2)).astype(np.float32)
-    A[0, 4, 4, :] = np.float32(2.0 ** -95)        # tiny diagonal, large elsewhere in column
-    A[0, :, 4, :] *= np.float32(2.0 ** -100)      # whole column tiny -> tiny pivot
-    A[1, 2, 7, 0] = np.inf                        # an infinity
-    A[2, :, :, :] = np.diag(np.full(30, np.nan, np.float32))[..., None]   # NaN on the diagonal...
-    A[2, :, :, :] += rng.standard_normal((30, 30, 2)).astype(np.float32)  # ...plus finite noise
-    A[3, :, :, :] *= np.float32(1e-40)            # denormals
-    A[4, 9, 9, :] = np.float32(2.0 ** 125)        # one huge entry
-    A[5, :, 0, :] = 0.0
-    A[5, 3, 0, :] = np.float32(2.0 ** -126)       # smallest normal as the only pivot candidate
-    As.extend(A)
-    bs.extend(rng.standard_normal((6, 30, 2)).astype(np.float32))
-    As, bs = np.stack(As), np.stack(bs)
+    As, bs = extreme_scale_systems(problem, oracle, samples100)
     xg = cgesv_batched(As, bs)
     for i in range(As.shape[0]):
         xr = oracle.cgesv_gpu(As[i], bs[i])

@@ -103,7 +103,12 @@ def test_lu_signature_table_matches_the_header_and_the_library(lib):
     src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "lu", "hc_lu_testing.h")).read(), flags=re.S)
     protos = {name: (" ".join(ret.split()), [" ".join(p.split()) for p in params.split(",")])
               for ret, name, params in re.findall(r"^([A-Za-z_][\w\s\*]*?)\b(hc_\w+)\s*\(([^()]*)\)", src, flags=re.M)}
-    assert set(protos) == set(_abi.LU_DECLARED_SYMBOLS) and len(protos) == 2
+    assert set(protos) == set(_abi.LU_DECLARED_SYMBOLS) and len(protos) == 3
+    assert len(_abi.LU_SIGNATURES) == 3, "a name is listed twice"
+    # hcLuVariant against _abi.LU_VARIANTS: the same names with the same numbers
+    enum = dict((n.lower(), int(v)) for n, v in re.findall(r"\bHC_LU_VARIANT_(\w+)\s*=\s*(\d+)", src))
+    assert enum.pop("count") == len(_abi.LU_VARIANTS) == 8
+    assert enum == {name: k for k, name in enumerate(_abi.LU_VARIANTS)}
     returns = {"int": C.c_int, "hcStatus": C.c_int}
     for s in _abi.LU_SIGNATURES:
         ret, params = protos[s.name]
@@ -122,3 +127,9 @@ def test_lu_signature_table_matches_the_header_and_the_library(lib):
     assert lib.hc_cgesv_30x30_struct_batched(-1, None, None, None, None) == 1
     assert lib.hc_cgesv_30x30_struct_batched(4, None, None, None, None) == 1
     assert lib.hc_cgesv_30x30_struct_batched(0, None, None, None, None) == 0
+    for v in range(8):
+        assert lib.hc_cgesv_30x30_variant_batched(v, -1, None, None, None, None) == 1
+        assert lib.hc_cgesv_30x30_variant_batched(v, 4, None, None, None, None) == 1
+        assert lib.hc_cgesv_30x30_variant_batched(v, 0, None, None, None, None) == 0
+    for v in (-1, 8, 1 << 20):     # an unknown variant is refused, whatever the rest
+        assert lib.hc_cgesv_30x30_variant_batched(v, 0, None, None, None, None) == 1

@@ -265,7 +265,12 @@ TOPK_DECLARED_SYMBOLS = tuple(s.name for s in TOPK_SIGNATURES)
 LU_SIGNATURES = (
     Sig("hc_lu_step_level", _i, (_i,), True),
     Sig("hc_cgesv_30x30_struct_batched", _ST, (_i, _p, _p, _p, _p), True),
+    Sig("hc_cgesv_30x30_variant_batched", _ST, (_i, _i, _p, _p, _p, _p), True),
 )
+# hcLuVariant, in the header's order: the instantiations of the tracker's sparse
+# solve by the kernels that run them (odd: the structure-agnostic twins)
+LU_VARIANTS = ("throughput", "throughput_twin", "abort", "abort_twin", "small", "small_twin", "archived",
+               "archived_twin")
 LU_DECLARED_SYMBOLS = tuple(s.name for s in LU_SIGNATURES)
 
 _lib = None

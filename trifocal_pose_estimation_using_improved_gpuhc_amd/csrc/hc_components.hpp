@@ -37,13 +37,17 @@ __global__ void __launch_bounds__(WG_THREADS) k_cgesv(int n, const cf *__restric
     if (ok) X[(size_t)sys * NV + r] = x;
 }
 
-// The throughput tracker's solve alone: lu_solve with the template arguments of
-// hc_track_body.inc where ABSTAB holds (sparse, the problem's structure, the
-// caller's finiteness verdict), row patterns from LU_STRUCT_PAT, and on `redo`
-// the tracker's fallback: the system loaded again and solved densely.  Every
-// entry outside LU_STRUCT_PAT must be zero: k_cgesv_struct_check sets *bad
-// otherwise, and the host launches the solve only when it stays 0
-// (hc_cgesv_30x30_struct_batched).
+// Any of the tracker's solves alone (include/lu/hc_lu_testing.h,
+// hc_cgesv_30x30_variant_batched): lu_solve<false, LAT, STRUCT, ENTCHK, FUSE>
+// with the template arguments one of the tracking kernels passes
+// (hc_track_body.inc), and on `redo` the tracker's fallback: the system loaded
+// again and solved densely.  STRUCT: the row patterns are LU_STRUCT_PAT, and
+// every entry outside them must be zero: k_cgesv_struct_check sets *bad
+// otherwise, and the host launches the solve only when it stays 0.  !STRUCT
+// (the twins that track a table of another structure): a row's pattern is its
+// non-zero entries, as in k_cgesv, and any matrix is accepted.  ENTCHK: the
+// finiteness verdict is taken here, on the entries' sums of squares, as
+// eval_hx_terms_abs takes it.  <0, true, true, true> is the throughput tracker's.
 __global__ void __launch_bounds__(WG_THREADS) k_cgesv_struct_check(int n, const cf *__restrict__ A,
                                                                    unsigned *__restrict__ bad) {
     const size_t i = (size_t)blockIdx.x * WG_THREADS + threadIdx.x;   // one thread per row
@@ -57,29 +61,37 @@ __global__ void __launch_bounds__(WG_THREADS) k_cgesv_struct_check(int n, const 
     }
     if (out) *bad = 1u;
 }
-__global__ void __launch_bounds__(WG_THREADS) k_cgesv_struct(int n, const cf *__restrict__ A,
-                                                             const cf *__restrict__ B, cf *__restrict__ X) {
+template <int LAT, bool STRUCT, bool ENTCHK, bool FUSE>
+__global__ void __launch_bounds__(WG_THREADS) k_cgesv_variant(int n, const cf *__restrict__ A,
+                                                              const cf *__restrict__ B, cf *__restrict__ X) {
     __shared__ LUBuf s_lu[2 * WAVES_PER_WG];
-    __shared__ __attribute__((aligned(16))) cf s_scr[2 * WAVES_PER_WG][LU_SCRATCH_FUSED_CF];
+    __shared__ __attribute__((aligned(16))) cf s_scr[2 * WAVES_PER_WG][FUSE ? LU_SCRATCH_FUSED_CF : LU_SCRATCH_CF];
     const int lane = lane_id();
     const int r = lane & 31;
     const int sys = (blockIdx.x * WAVES_PER_WG + threadIdx.x / WAVE) * 2 + (lane >> 5);
     const bool ok = sys < n && r < NV;
     cf rA[NV];
+    uint32_t nz = 0;
     pf2 sq = {0.0f, 0.0f};   // the entries' sums of squares, as eval_hx_terms_abs takes them
 #pragma unroll
     for (int c = 0; c < NV; c++) {
         rA[c] = ok ? A[((size_t)sys * NV + r) * NV + c] : cmk(0.0f, 0.0f);
-        sq.x = __builtin_fmaf(rA[c].x, rA[c].x, sq.x);
-        sq.y = __builtin_fmaf(rA[c].y, rA[c].y, sq.y);
+        if constexpr (!STRUCT) {
+            if (rA[c].x != 0.0f || rA[c].y != 0.0f) nz |= 1u << c;   // NaN counts as non-zero
+        }
+        if constexpr (ENTCHK) {
+            sq.x = __builtin_fmaf(rA[c].x, rA[c].x, sq.x);
+            sq.y = __builtin_fmaf(rA[c].y, rA[c].y, sq.y);
+        }
     }
-    const bool ent_bad = __ballot(!(sq.x + sq.y < __builtin_inff())) != 0ull;
-    const uint32_t pat = r < NV ? LU_STRUCT_PAT[r] : 0u;
+    bool ent_bad = false;
+    if constexpr (ENTCHK) ent_bad = __ballot(!(sq.x + sq.y < __builtin_inff())) != 0ull;
+    const uint32_t pat = STRUCT ? (r < NV ? LU_STRUCT_PAT[r] : 0u) : nz;
     const cf rB = ok ? B[(size_t)sys * NV + r] : cmk(0.0f, 0.0f);
     LUBuf &LB = s_lu[(threadIdx.x / WAVE) * 2 + (lane >> 5)];
     cf *scr = s_scr[(threadIdx.x / WAVE) * 2 + (lane >> 5)];
     bool redo;
-    cf x = lu_solve<false, 0, true, true, true>(rA, rB, lane, pat, LB, scr, redo, __ballot(sys < n), ent_bad);
+    cf x = lu_solve<false, LAT, STRUCT, ENTCHK, FUSE>(rA, rB, lane, pat, LB, scr, redo, __ballot(sys < n), ent_bad);
     if (__builtin_expect(redo, 0)) {
 #pragma unroll
         for (int c = 0; c < NV; c++) rA[c] = ok ? A[((size_t)sys * NV + r) * NV + c] : cmk(0.0f, 0.0f);

@@ -307,6 +307,38 @@ static int diag_read(const T &sym, unsigned long long *out, int reset, const T *
     return (init ? hipMemcpy(p, init, sizeof(T), hipMemcpyHostToDevice) : hipMemset(p, 0, sizeof(T))) == hipSuccess ? 0 : -1;
 }
 
+// tests only (include/lu/hc_lu_testing.h): one of the tracker's solves alone.
+// The template arguments are those of hc_track_body.inc for the kernels that
+// run the variant, from the same macros.  Blocks where the variant has the
+// problem's structure: the structure check's verdict is read back before the
+// solve is launched.
+template <int LAT, bool STRUCT, bool ENTCHK, bool FUSE>
+static hcStatus launch_cgesv_variant(int n, const hcComplex *A, const hcComplex *b, hcComplex *x, hipStream_t s) {
+    if (STRUCT) {
+        unsigned *bad = nullptr, h_bad = 0u;
+        if ((g_last_hip_error = hipMalloc((void **)&bad, sizeof(unsigned))) != hipSuccess) return HC_ERROR_DEVICE;
+        hipError_t e = hipMemsetAsync(bad, 0, sizeof(unsigned), s);
+        if (e == hipSuccess) {
+            const size_t rows = (size_t)n * NV;
+            hipLaunchKernelGGL(k_cgesv_struct_check, dim3((unsigned)((rows + WG_THREADS - 1) / WG_THREADS)),
+                               dim3(WG_THREADS), 0, s, n, (const cf *)A, bad);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(&h_bad, bad, sizeof(unsigned), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        (void)hipFree(bad);
+        if (e != hipSuccess) {
+            g_last_hip_error = e;
+            return HC_ERROR_LAUNCH;
+        }
+        if (h_bad != 0u) return HC_ERROR_INVALID_VALUE;
+    }
+    const int per = 2 * WAVES_PER_WG;
+    hipLaunchKernelGGL((k_cgesv_variant<LAT, STRUCT, ENTCHK, FUSE>), dim3((n + per - 1) / per), dim3(WG_THREADS), 0, s,
+                       n, (const cf *)A, (const cf *)b, (cf *)x);
+    return launch_status(HC_ERROR_LAUNCH);
+}
+
 }  // namespace hc
 
 extern "C" {
@@ -422,35 +454,29 @@ hcStatus hc_cgesv_30x30_batched(int n, const hcComplex *A, const hcComplex *b, h
     return hc::launch_status(HC_ERROR_LAUNCH);
 }
 
-// tests only (include/lu/hc_lu_testing.h): the throughput tracker's solve on
-// systems within the compiled-in structure.  Blocks: the structure check's
-// verdict is read back before the solve is launched.
-hcStatus hc_cgesv_30x30_struct_batched(int n, const hcComplex *A, const hcComplex *b, hcComplex *x, hcStream stream) {
+// tests only (include/lu/hc_lu_testing.h): launch_cgesv_variant above
+hcStatus hc_cgesv_30x30_variant_batched(int variant, int n, const hcComplex *A, const hcComplex *b, hcComplex *x,
+                                        hcStream stream) {
+    if (variant < 0 || variant >= HC_LU_VARIANT_COUNT) return HC_ERROR_INVALID_VALUE;
     if (n < 0 || (n > 0 && (!A || !b || !x))) return HC_ERROR_INVALID_VALUE;
     if (n == 0) return HC_SUCCESS;
     hipStream_t s = (hipStream_t)stream;
     (void)hipGetLastError();
-    unsigned *bad = nullptr, h_bad = 0u;
-    if ((hc::g_last_hip_error = hipMalloc((void **)&bad, sizeof(unsigned))) != hipSuccess) return HC_ERROR_DEVICE;
-    hipError_t e = hipMemsetAsync(bad, 0, sizeof(unsigned), s);
-    if (e == hipSuccess) {
-        const size_t rows = (size_t)n * hc::NV;
-        hipLaunchKernelGGL(hc::k_cgesv_struct_check, dim3((unsigned)((rows + hc::WG_THREADS - 1) / hc::WG_THREADS)),
-                           dim3(hc::WG_THREADS), 0, s, n, (const hc::cf *)A, bad);
-        e = hipGetLastError();
+    switch (variant) {   //                                  <LAT, STRUCT, ENTCHK, FUSE>
+    case HC_LU_VARIANT_THROUGHPUT:      return hc::launch_cgesv_variant<0, true, true, true>(n, A, b, x, s);
+    case HC_LU_VARIANT_THROUGHPUT_TWIN: return hc::launch_cgesv_variant<0, false, true, false>(n, A, b, x, s);
+    case HC_LU_VARIANT_ABORT:           return hc::launch_cgesv_variant<HC_LU_LATB_COLS, true, false, false>(n, A, b, x, s);
+    case HC_LU_VARIANT_ABORT_TWIN:      return hc::launch_cgesv_variant<HC_LU_LATB_COLS, false, false, false>(n, A, b, x, s);
+    case HC_LU_VARIANT_SMALL:           return hc::launch_cgesv_variant<HC_SMALL_LAT, true, false, false>(n, A, b, x, s);
+    case HC_LU_VARIANT_SMALL_TWIN:      return hc::launch_cgesv_variant<HC_SMALL_LAT, false, false, false>(n, A, b, x, s);
+    case HC_LU_VARIANT_ARCHIVED:        return hc::launch_cgesv_variant<0, true, false, false>(n, A, b, x, s);
+    case HC_LU_VARIANT_ARCHIVED_TWIN:   return hc::launch_cgesv_variant<0, false, false, false>(n, A, b, x, s);
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(&h_bad, bad, sizeof(unsigned), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(bad);
-    if (e != hipSuccess) {
-        hc::g_last_hip_error = e;
-        return HC_ERROR_LAUNCH;
-    }
-    if (h_bad != 0u) return HC_ERROR_INVALID_VALUE;
-    const int per = 2 * hc::WAVES_PER_WG;
-    hipLaunchKernelGGL(hc::k_cgesv_struct, dim3((n + per - 1) / per), dim3(hc::WG_THREADS), 0, s, n,
-                       (const hc::cf *)A, (const hc::cf *)b, (hc::cf *)x);
-    return hc::launch_status(HC_ERROR_LAUNCH);
+    return HC_ERROR_INVALID_VALUE;
+}
+
+hcStatus hc_cgesv_30x30_struct_batched(int n, const hcComplex *A, const hcComplex *b, hcComplex *x, hcStream stream) {
+    return hc_cgesv_30x30_variant_batched(HC_LU_VARIANT_THROUGHPUT, n, A, b, x, stream);
 }
 
 hcStatus hc_trifocal_eval_batched(int n, const int32_t *unified_index, const hcComplex *x, const hcComplex *p,

@@ -463,6 +463,24 @@ def cgesv_struct_batched(A: np.ndarray, b: np.ndarray, device="cuda:0") -> np.nd
     return xt.cpu().numpy()
 
 
+def cgesv_variant_batched(variant, A: np.ndarray, b: np.ndarray, device="cuda:0") -> np.ndarray:
+    """One of the tracker's sparse solves alone (hcLuVariant: its number, or its
+    name in _abi.LU_VARIANTS) on n 30x30 complex systems (layout of
+    cgesv_batched).  Raises HCError (HC_ERROR_INVALID_VALUE) for an unknown
+    variant and, in the variants with the compiled-in structure, when an entry
+    outside it is non-zero."""
+    dev = _require_gpu(device)
+    if isinstance(variant, str):
+        variant = _abi.LU_VARIANTS.index(variant)
+    At = torch.from_numpy(np.ascontiguousarray(A, np.float32)).to(dev)
+    bt = torch.from_numpy(np.ascontiguousarray(b, np.float32)).to(dev)
+    xt = torch.empty_like(bt)
+    _abi.call("hc_cgesv_30x30_variant_batched", int(variant), At.shape[0], _abi.ptr(At), _abi.ptr(bt), _abi.ptr(xt),
+              _abi.ptr(torch.cuda.current_stream(dev)))
+    torch.cuda.synchronize(dev)
+    return xt.cpu().numpy()
+
+
 def eval_batched(unified: np.ndarray, x: np.ndarray, p: np.ndarray, d: np.ndarray, device="cuda:0"):
     """Batched dH/dx, dH/dt, H at (x, p) with the tracker's compacted tables."""
     dev = _require_gpu(device)
