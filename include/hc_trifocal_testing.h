@@ -46,7 +46,7 @@ void hc_trifocal_set_retry_reuse(int on);
 hcStatus hc_trifocal_ring_check_test(void *workspace, size_t workspace_bytes, unsigned head, unsigned tail,
                                      unsigned avail, hcStream stream);
 
-/* The tracker LU's compiled-in structure (hc_lu.hpp): row `row`'s structural
+/* The tracker LU's compiled-in structure (hc_lu_struct.hpp): row `row`'s structural
    pattern of trifocal_2op1p_30x30's dH/dx (bit c: entry (row, c) has terms),
    and the class of column group `group` of pivot step `step` (groups of 2
    after a leading single column when step + 1 is odd): 0 tested, 1 dead (the

@@ -1,5 +1,5 @@
 /* hc_lu_testing.h -- test hooks of the tracker LU (csrc/hc_lu.hpp): its fused
-   levels, and each of its instantiations alone; beside include/hc_trifocal_testing.h, whose hc_lu_candidates
+   levels (csrc/hc_lu_struct.hpp LU_LEVELS, csrc/hc_lu_levels.hpp), and each of its instantiations alone; beside include/hc_trifocal_testing.h, whose hc_lu_candidates
    and hc_lu_struct_pattern they go with.  No reference counterpart. */
 #ifndef HC_LU_TESTING_H
 #define HC_LU_TESTING_H
@@ -26,20 +26,24 @@ int hc_lu_step_level(int step);
 hcStatus hc_cgesv_30x30_struct_batched(int n, const hcComplex *A, const hcComplex *b, hcComplex *x,
                                        hcStream stream);
 
-/* The instantiations of the tracker's sparse solve, lu_solve<false, LAT,
-   STRUCT, ENTCHK, FUSE> (csrc/hc_lu.hpp), by the kernels that run them.  A
-   "twin" is the structure-agnostic solve of the kernel named before it, which
-   tracks a table whose structure is not the compiled-in one (e.g. the same
-   system with its equations permuted). */
+/* The instantiations of the tracker's sparse solve (csrc/hc_lu.hpp lu_solve),
+   by the kernels that run them: each variant names a tracking kernel's
+   parameters (csrc/hc_track.hpp: ABORT, ARCH, LULAT, LUS), and lu_mode() of
+   hc_lu.hpp, which the tracking kernels read as well, gives the solve's
+   template arguments from them.  A "twin" (LUS = false) is the
+   structure-agnostic solve of the kernel named before it, which tracks a table
+   whose structure is not the compiled-in one (e.g. the same system with its
+   equations permuted). */
 typedef enum {
-    HC_LU_VARIANT_THROUGHPUT = 0,      /* k_track<false, ...>:      <0, true, true, true>  (hc_cgesv_30x30_struct_batched) */
-    HC_LU_VARIANT_THROUGHPUT_TWIN = 1, /*                           <0, false, true, false> */
-    HC_LU_VARIANT_ABORT = 2,           /* abort, grouped and gated: <HC_LU_LATB_COLS, true, false, false> */
-    HC_LU_VARIANT_ABORT_TWIN = 3,      /*                           <HC_LU_LATB_COLS, false, false, false> */
-    HC_LU_VARIANT_SMALL = 4,           /* k_track_small:            <HC_SMALL_LAT, true, false, false> */
-    HC_LU_VARIANT_SMALL_TWIN = 5,      /*                           <HC_SMALL_LAT, false, false, false> */
-    HC_LU_VARIANT_ARCHIVED = 6,        /* archived PH / PH_CodeOpt / P2C: <0, true, false, false> */
-    HC_LU_VARIANT_ARCHIVED_TWIN = 7,   /*                           <0, false, false, false> (hc_cgesv_30x30_batched's) */
+    HC_LU_VARIANT_THROUGHPUT = 0,      /* k_track<false, ...>: no abort, not archived, LULAT 0; the fused levels
+                                          (hc_cgesv_30x30_struct_batched) */
+    HC_LU_VARIANT_THROUGHPUT_TWIN = 1,
+    HC_LU_VARIANT_ABORT = 2,           /* abort, grouped and gated: ABORT, LULAT HC_LU_LATB_COLS */
+    HC_LU_VARIANT_ABORT_TWIN = 3,
+    HC_LU_VARIANT_SMALL = 4,           /* k_track_small: LULAT HC_SMALL_LAT */
+    HC_LU_VARIANT_SMALL_TWIN = 5,
+    HC_LU_VARIANT_ARCHIVED = 6,        /* archived PH / PH_CodeOpt / P2C: ARCH, LULAT 0 */
+    HC_LU_VARIANT_ARCHIVED_TWIN = 7,   /* (hc_cgesv_30x30_batched's solve) */
     HC_LU_VARIANT_COUNT = 8
 } hcLuVariant;
 

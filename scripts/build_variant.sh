@@ -13,6 +13,8 @@
 # entries) and -DHC_EV_TAHEAD (profiles/r13a_ab_abs_tables.jsonl, r13c_ab_leave_one_out.jsonl).  The
 # sources with these two switches are in no commit; DESIGN.md section 3.6 ("How the variants were
 # built") describes them site by site.
+# v10.10's LU_FUSE_LEVELS (the fused levels of the sparse LU as a mask: 0, 1, 3, 7 of the four) is
+# settled at all four; the partial-level variants live in commit 74bcdb5.
 set -e
 cd "$(dirname "$0")/../trifocal_pose_estimation_using_improved_gpuhc_amd/csrc"
 N=$1; shift

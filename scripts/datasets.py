@@ -3,7 +3,7 @@
 
 What was fitted on which data: the dequeue order (csrc/hc_track_order.inc) on
 the per-track costs of synthcurves datasets 001 and 002; the LU's always-live
-column groups (hc_lu.hpp LU_ALWAYS) on the group liveness of 000/001/002; every
+column groups (hc_lu_struct.hpp LU_ALWAYS) on the group liveness of 000/001/002; every
 time-to-first-pose figure before round 6 on dataset 000.  Datasets 003 (the
 CLI's round 3: srand(3)), 010, 050 and 099 were never used for any fitting.
 

@@ -4,7 +4,7 @@
 Needs the HC_DIAG_LIVE build (scripts/build_variant.sh live -DHC_DIAG_LIVE,
 loaded through HC_TRIFOCAL_LIB).  One config-2 launch (or --dataset / --seed);
 every eighth workgroup counts, per pivot step I and column group K of the
-sparse solve (hc_lu.hpp LuChunks<2>), the wave-solves whose group test found
+sparse solve (hc_lu_struct.hpp LuChunks), the wave-solves whose group test found
 the group live.  Prints one JSON object: live[I][K] as a fraction of the
 sampled wave-solves, and the groups live in at least 0.99 / 0.999 of them.
 """

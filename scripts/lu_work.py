@@ -34,7 +34,7 @@ def main():
     fn = L.hc_diag_luwork
     fn.argtypes = [C.POINTER(C.c_ulonglong), C.c_int]
     fn.restype = C.c_int
-    out = (C.c_ulonglong * 42)()   # DIAG_LUWORK_WORDS (csrc/hc_lu.hpp)
+    out = (C.c_ulonglong * 42)()   # DIAG_LUWORK_WORDS (csrc/hc_lu_diag.hpp)
     dev = torch.device("cuda:0")
     problem = load_problem()
     argv = sys.argv[1:]

@@ -22,7 +22,7 @@ CLASSES = ("valu", "valu_readlane", "salu", "lds", "branch", "nop", "waitcnt", "
 
 
 def group_tests_per_solve(ch=2, nv=30):
-    """Column groups the sparse LU tests over a solve (hc_lu.hpp LuChunks<2>)."""
+    """Column groups the sparse LU tests over a solve (hc_lu_struct.hpp LuChunks)."""
     n = 0
     for i in range(nv - 1):
         single = 1 if ((i + 1) & 1) and (i + 1 < nv) else 0
@@ -51,7 +51,7 @@ def _group_classes():
 
 
 def always_groups():
-    """Column groups the tracker's LU runs without a test (hc_lu.hpp, class 2)."""
+    """Column groups the tracker's LU runs without a test (hc_lu_struct.hpp, class 2)."""
     return sum(1 for c in _group_classes() if c == 2)
 
 

@@ -1,4 +1,4 @@
-"""GPU tests of the tracker LU's fused levels (hc_lu.hpp lu_level): the
+"""GPU tests of the tracker LU's fused levels (hc_lu_levels.hpp lu_level): the
 throughput tracker's solve alone (hc_cgesv_30x30_struct_batched) against the
 oracle's LU, system by system, on inputs that reach every exit of a fused
 level, and the throughput kernel against the oracle's tracker.

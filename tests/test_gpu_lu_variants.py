@@ -1,7 +1,7 @@
 """GPU tests of every instantiation of the tracker's sparse solve alone
 (hc_cgesv_30x30_variant_batched, include/lu/hc_lu_testing.h: lu_solve<false,
-LAT, STRUCT, ENTCHK, FUSE> with the template arguments of the kernels that run
-it) against the oracle's LU, system by system, on inputs built to leave the
+LAT, STRUCT, ENTCHK, FUSE> with the template arguments hc_lu.hpp's lu_mode gives
+the kernels that run it) against the oracle's LU, system by system, on inputs built to leave the
 common path at every pivot step (tests/lu_cases.py; what they cover is
 accounted on the CPU, tests/test_lu_cases_host.py).  No tracker launch.
 

@@ -1,4 +1,4 @@
-"""CPU tests of the tracker LU's independent pivot steps (hc_lu.hpp, LU_LEVELS).
+"""CPU tests of the tracker LU's independent pivot steps (hc_lu_struct.hpp, LU_LEVELS).
 
 A pivot step reads and writes only its candidate rows, so two steps with
 disjoint candidate sets commute exactly.  The library derives, at compile

@@ -1,4 +1,4 @@
-"""CPU tests of the tracker LU's column-group classes (hc_lu.hpp, round 5).
+"""CPU tests of the tracker LU's column-group classes (hc_lu_struct.hpp, round 5).
 
 The sparse LU tests, per pivot step, whether a column group can be non-zero
 in a pivot row of the wave.  For trifocal_2op1p_30x30 the library compiles in

@@ -39,8 +39,8 @@ __global__ void __launch_bounds__(WG_THREADS) k_cgesv(int n, const cf *__restric
 
 // Any of the tracker's solves alone (include/lu/hc_lu_testing.h,
 // hc_cgesv_30x30_variant_batched): lu_solve<false, LAT, STRUCT, ENTCHK, FUSE>
-// with the template arguments one of the tracking kernels passes
-// (hc_track_body.inc), and on `redo` the tracker's fallback: the system loaded
+// with the template arguments one of the tracking kernels passes (lu_mode,
+// hc_lu.hpp; the host side derives them from the kernel's parameters), and on `redo` the tracker's fallback: the system loaded
 // again and solved densely.  STRUCT: the row patterns are LU_STRUCT_PAT, and
 // every entry outside them must be zero: k_cgesv_struct_check sets *bad
 // otherwise, and the host launches the solve only when it stays 0.  !STRUCT

@@ -308,13 +308,14 @@ static int diag_read(const T &sym, unsigned long long *out, int reset, const T *
 }
 
 // tests only (include/lu/hc_lu_testing.h): one of the tracker's solves alone.
-// The template arguments are those of hc_track_body.inc for the kernels that
-// run the variant, from the same macros.  Blocks where the variant has the
-// problem's structure: the structure check's verdict is read back before the
-// solve is launched.
-template <int LAT, bool STRUCT, bool ENTCHK, bool FUSE>
+// The template parameters are what a tracking kernel that runs the variant
+// knows (hc_track.hpp), and lu_mode (hc_lu.hpp) gives the solve from them, as
+// in hc_track_body.inc.  Blocks where the variant has the problem's structure:
+// the structure check's verdict is read back before the solve is launched.
+template <bool ABORT, bool ARCH, int LULAT, bool LUS>
 static hcStatus launch_cgesv_variant(int n, const hcComplex *A, const hcComplex *b, hcComplex *x, hipStream_t s) {
-    if (STRUCT) {
+    constexpr LuMode M = lu_mode(ABORT, ARCH, LULAT, LUS);
+    if (M.strct) {
         unsigned *bad = nullptr, h_bad = 0u;
         if ((g_last_hip_error = hipMalloc((void **)&bad, sizeof(unsigned))) != hipSuccess) return HC_ERROR_DEVICE;
         hipError_t e = hipMemsetAsync(bad, 0, sizeof(unsigned), s);
@@ -334,7 +335,7 @@ static hcStatus launch_cgesv_variant(int n, const hcComplex *A, const hcComplex 
         if (h_bad != 0u) return HC_ERROR_INVALID_VALUE;
     }
     const int per = 2 * WAVES_PER_WG;
-    hipLaunchKernelGGL((k_cgesv_variant<LAT, STRUCT, ENTCHK, FUSE>), dim3((n + per - 1) / per), dim3(WG_THREADS), 0, s,
+    hipLaunchKernelGGL((k_cgesv_variant<M.lat, M.strct, M.entchk, M.fuse>), dim3((n + per - 1) / per), dim3(WG_THREADS), 0, s,
                        n, (const cf *)A, (const cf *)b, (cf *)x);
     return launch_status(HC_ERROR_LAUNCH);
 }
@@ -462,15 +463,15 @@ hcStatus hc_cgesv_30x30_variant_batched(int variant, int n, const hcComplex *A, 
     if (n == 0) return HC_SUCCESS;
     hipStream_t s = (hipStream_t)stream;
     (void)hipGetLastError();
-    switch (variant) {   //                                  <LAT, STRUCT, ENTCHK, FUSE>
-    case HC_LU_VARIANT_THROUGHPUT:      return hc::launch_cgesv_variant<0, true, true, true>(n, A, b, x, s);
-    case HC_LU_VARIANT_THROUGHPUT_TWIN: return hc::launch_cgesv_variant<0, false, true, false>(n, A, b, x, s);
-    case HC_LU_VARIANT_ABORT:           return hc::launch_cgesv_variant<HC_LU_LATB_COLS, true, false, false>(n, A, b, x, s);
-    case HC_LU_VARIANT_ABORT_TWIN:      return hc::launch_cgesv_variant<HC_LU_LATB_COLS, false, false, false>(n, A, b, x, s);
-    case HC_LU_VARIANT_SMALL:           return hc::launch_cgesv_variant<HC_SMALL_LAT, true, false, false>(n, A, b, x, s);
-    case HC_LU_VARIANT_SMALL_TWIN:      return hc::launch_cgesv_variant<HC_SMALL_LAT, false, false, false>(n, A, b, x, s);
-    case HC_LU_VARIANT_ARCHIVED:        return hc::launch_cgesv_variant<0, true, false, false>(n, A, b, x, s);
-    case HC_LU_VARIANT_ARCHIVED_TWIN:   return hc::launch_cgesv_variant<0, false, false, false>(n, A, b, x, s);
+    switch (variant) {   // a kernel that runs it (hc_track.hpp):  <ABORT, ARCH, LULAT, LUS>
+    case HC_LU_VARIANT_THROUGHPUT:      return hc::launch_cgesv_variant<false, false, 0, true>(n, A, b, x, s);
+    case HC_LU_VARIANT_THROUGHPUT_TWIN: return hc::launch_cgesv_variant<false, false, 0, false>(n, A, b, x, s);
+    case HC_LU_VARIANT_ABORT:           return hc::launch_cgesv_variant<true, false, HC_LU_LATB_COLS, true>(n, A, b, x, s);
+    case HC_LU_VARIANT_ABORT_TWIN:      return hc::launch_cgesv_variant<true, false, HC_LU_LATB_COLS, false>(n, A, b, x, s);
+    case HC_LU_VARIANT_SMALL:           return hc::launch_cgesv_variant<false, false, HC_SMALL_LAT, true>(n, A, b, x, s);
+    case HC_LU_VARIANT_SMALL_TWIN:      return hc::launch_cgesv_variant<false, false, HC_SMALL_LAT, false>(n, A, b, x, s);
+    case HC_LU_VARIANT_ARCHIVED:        return hc::launch_cgesv_variant<false, true, 0, true>(n, A, b, x, s);
+    case HC_LU_VARIANT_ARCHIVED_TWIN:   return hc::launch_cgesv_variant<false, true, 0, false>(n, A, b, x, s);
     }
     return HC_ERROR_INVALID_VALUE;
 }
@@ -597,7 +598,7 @@ hcStatus hc_shared_flag_close(uint32_t *flag, int opened) {
 int hc_trifocal_abi_version(void) { return HC_TRIFOCAL_ABI_VERSION; }
 
 // tests only (include/hc_trifocal_testing.h): the tracker LU's structural
-// patterns and column-group classes (hc_lu.hpp)
+// patterns and column-group classes (hc_lu_struct.hpp)
 unsigned hc_lu_struct_pattern(int row) { return row >= 0 && row < hc::NV ? hc::LU_STRUCT_PAT[row] : 0u; }
 unsigned hc_lu_candidates(int step) { return step >= 0 && step < hc::NV ? hc::LU_BOUND.cand[step] : 0u; }
 int hc_lu_search_span(int step) { return step >= 0 && step < hc::NV ? hc::lu_search_span(step) : -1; }

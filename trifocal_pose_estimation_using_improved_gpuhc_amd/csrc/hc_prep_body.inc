@@ -287,7 +287,7 @@
         }
         T->pat[r] = pat;
         // the tracker's LU skips the column groups this problem's structure
-        // can never fill (hc_lu.hpp LU_STRUCT_PAT); the evaluations take any
+        // can never fill (hc_lu_struct.hpp LU_STRUCT_PAT); the evaluations take any
         // structure, the tracker only one within it
         if (r < NV && (pat & ~LU_STRUCT_PAT[r]) != 0u) atomicOr(&s_nostruct, 1);
         for (int q = 0; q < HX_NSLOT / 2; q++) T->hxd[q][r] = s_dst[q][r];

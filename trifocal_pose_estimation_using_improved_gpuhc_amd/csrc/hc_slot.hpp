@@ -39,7 +39,7 @@ struct alignas(16) SlotLDS {
     cf ent[ENT_CAP]; // dH/dx entries, packed (k_prep_tables); p(t) and the diff params are staged
                      // in its first 68 entries while the prefixes are built.  The sparse LU
                      // overwrites ent[0 .. LU_SCRATCH_CF) with its store windows, and with its
-                     // fused levels ent[0 .. LU_SCRATCH_FUSED_CF) (hc_lu.hpp): after
+                     // fused levels ent[0 .. LU_SCRATCH_FUSED_CF) (hc_lu_struct.hpp): after
                      // a solve only the structural zero at ENT_CAP - 1 is intact
     cf lu[32];       // the LU's pivot-row buffer (hc_lu.hpp LUBuf)
     cf tp[TP_CAP];   // prefix table T: (c * p[a]) * p[b] per (c, a, b) triple (dH/dx and H terms)

@@ -65,7 +65,7 @@ __device__ unsigned long long g_diag_phase[13];
 // run time); a separate instantiation so the headline kernel carries neither
 // switch and the two show up under their own names in a kernel trace.
 // LUS: the LU's column groups classed by this problem's dH/dx structure
-// (hc_lu.hpp LU_STRUCT_PAT / LU_BOUND: never-fillable groups untested,
+// (hc_lu_struct.hpp LU_STRUCT_PAT / LU_BOUND: never-fillable groups untested,
 // always-live groups unconditional, narrowed pivot search).  Every launch
 // enqueues both instantiations; k_prep_tables decides on the device which one
 // tracks (EvalTables::lu_struct) and the other returns at once, so a table of

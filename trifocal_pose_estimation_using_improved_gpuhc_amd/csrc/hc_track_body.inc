@@ -14,20 +14,23 @@
 //   hc_score.hpp   score_half, JointCounts, score_joint_half
 //   hc_track.hpp   PH_*, HC_ABORT_PRIO_DIV, the HC_DIAG_* globals
 //   hc_device.hpp, hc_slot.hpp, hc_eval.hpp, hc_lu.hpp, hc_pose_device.hpp
-//                  the arithmetic, SlotLDS, the evaluations, lu_solve, scenes
+//                  the arithmetic, SlotLDS, the evaluations, lu_mode / lu_solve, scenes
 // kernel_GPUHC_trifocal_pose_PH_CodeOpt_TrunPaths (..._TrunPaths.cu:45-290) and,
 // with ABORT, ..._TrunPaths_TrunRANSAC (..._TrunRANSAC.cu:45-327).
-    constexpr bool LUSTRUCT = LUS;
+    // the sparse solve this kernel runs (hc_lu.hpp lu_mode: the one place that says so)
+    constexpr LuMode LUM = lu_mode(ABORT, ARCH, LULAT, LUS);
+    constexpr bool LUSTRUCT = LUM.strct;
     // The throughput tracking kernel reads its evaluations' operand addresses
     // complete, from the slot-absolute tables (hc_eval.hpp AbsTables), and checks
-    // finiteness on the dH/dx entries instead of the gathered rows (hc_lu.hpp
-    // ENTCHK).  The latency-critical kernels keep the L1-resident packed tables.
+    // finiteness on the dH/dx entries instead of the gathered rows (the solve's
+    // ENTCHK, which is therefore this flag).  The latency-critical kernels keep the
+    // L1-resident packed tables.
     // (The variant builds that measured the four parts apart are not kept; DESIGN.md section 3.6
     // says how each ABSTAB site below was switched.)
-    constexpr bool ABSTAB = !ABORT && !ARCH && LULAT == 0;
-    // the LU's independent pivot steps fused level by level (hc_lu.hpp lu_level): the
-    // headline kernel only; its structure-agnostic twin has no levels to fuse
-    constexpr bool LUFUSE = ABSTAB && LUSTRUCT;
+    constexpr bool ABSTAB = LUM.entchk;
+    // the LU's independent pivot steps fused level by level (hc_lu_levels.hpp): the
+    // headline kernel only; false here gives its unfused solve
+    constexpr bool LUFUSE = LUM.fuse;
     __shared__ cf s_sp[NPP];
     __shared__ SlotLDS s_slot[2 * WAVES_PER_WG];
     Workspace *ws = a.ws;
@@ -565,11 +568,8 @@
         // the LU's scratch: the dH/dx entry block, dead once gathered into rA
         // (a dense re-solve evaluates dH/dx again)
         static_assert(ENT_CAP - 1 >= LU_SCRATCH_FUSED_CF && offsetof(SlotLDS, ent) % 16 == 0, "LU scratch in SlotLDS::ent");
-#ifdef HC_DIAG_LUWORK
-        cf k = lu_solve<false, LULAT, LUSTRUCT, ABSTAB, LUFUSE>(rA, rB, lane_v, row_pat, LB, S.ent, redo, __ballot(act), ent_bad);   // :188 / :224
-#else
-        cf k = lu_solve<false, LULAT, LUSTRUCT, ABSTAB, LUFUSE>(rA, rB, lane_v, row_pat, LB, S.ent, redo, ~0ull, ent_bad);           // :188 / :224
-#endif
+        cf k = lu_solve<false, LUM.lat, LUSTRUCT, ABSTAB, LUFUSE>(rA, rB, lane_v, row_pat, LB, S.ent, redo,
+                                                                  HC_LU_COUNT(__ballot(act)), ent_bad);   // :188 / :224
         HC_ISA_MARK("ctl_redo");
         if (__builtin_expect(redo, 0)) {
             // a system the sparse solve cannot take exactly (an entry not provably
@@ -608,11 +608,7 @@
                 gather_hx(rA, &s_rowc[0][0], S, r_r);
             }
             wave_lds_sync();
-#ifdef HC_DIAG_LUWORK
-            k = lu_solve<true>(rA, rb, lane_v, row_pat, LB, S.ent, redo, __ballot(act_r));
-#else
-            k = lu_solve<true>(rA, rb, lane_v, row_pat, LB, S.ent, redo);
-#endif
+            k = lu_solve<true>(rA, rb, lane_v, row_pat, LB, S.ent, redo, HC_LU_COUNT(__ballot(act_r)));
         }
         wave_lds_sync();
 #ifdef HC_DIAG_PHASES
