@@ -20,6 +20,23 @@
  *     never changed; re-entrant across devices/streams;
  *   - errors are returned as hcStatus, never exit();
  *   - result index space is the reference's: batch id b = sample*312 + track.
+ *
+ * What a caller that records these calls in a graph must know (the rule above
+ * holds for every prototype with an hcStream parameter in include/, except the
+ * test hooks whose comments say that they block; tests/test_gpu_graph_replay.py
+ * replays each of them):
+ *   - a launch resets its own state on the device at every replay (control
+ *     block, table hash check, ring and its epoch, timestamps, selection keys);
+ *     the caller's resets -- the start solutions copied into tracks, the zeroed
+ *     found / group_found / group_found_ticks, the -1 of
+ *     trifocal_sols_batch_index and joint_inliers -- belong inside the graph;
+ *   - the sizes (N, the edgel counts E, k), the pointers and hcTrackSettings
+ *     are part of the recording: between replays only buffer contents change;
+ *   - the testing hooks hc_trifocal_set_small_launch, hc_trifocal_set_ring_test
+ *     and hc_trifocal_set_retry_reuse are read when a launch is recorded, not
+ *     when it is replayed;
+ *   - the blocking readers (hc_trifocal_workspace_status, hc_trifocal_read_timings,
+ *     hc_trifocal_read_timestamps) stay outside a capture.
  */
 #ifndef HC_TRIFOCAL_H
 #define HC_TRIFOCAL_H

@@ -231,6 +231,28 @@ __global__ void __launch_bounds__(256) k_pose_inlier_mask(const hcTrifocalSelect
     }
 }
 
+// The zeroed selections every launch sequence below starts from (their keys and
+// counts are atomics' targets).  A kernel of this library, not hipMemsetAsync:
+// recorded in a graph, the runtime's memset node filled a selection with stale
+// bytes at a later replay (tests/test_gpu_graph_replay.py), while a kernel node
+// carries all it needs in its own arguments.
+__global__ void __launch_bounds__(256) k_zero_words(uint32_t *__restrict__ p, unsigned n) {
+    for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) p[i] = 0u;
+}
+
+template <typename S>
+hcStatus zero_selections(S *sels, size_t count, hipStream_t s) {
+    static_assert(sizeof(S) % sizeof(uint32_t) == 0 && alignof(S) >= alignof(uint32_t), "whole 32-bit words");
+    const size_t words = count * (sizeof(S) / sizeof(uint32_t));
+    if (words == 0) return HC_SUCCESS;
+    if (words > 0xFFFFFFFFull) return HC_ERROR_INVALID_VALUE;
+    const size_t blocks = (words + 255) / 256;
+    hipLaunchKernelGGL(k_zero_words, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, s,
+                       reinterpret_cast<uint32_t *>(sels), (unsigned)words);
+    if ((g_last_hip_error = hipGetLastError()) != hipSuccess) return HC_ERROR_LAUNCH;
+    return HC_SUCCESS;
+}
+
 // grid of the one-wave-per-path kernels: up to 32 waves per CU, 4 per block
 inline hcStatus path_grid(int num_paths, int &blocks) {
     int dev = 0, cus = 256;
@@ -249,8 +271,8 @@ template <bool JOINT, bool GROUPED>
 hcStatus launch_pose_support(const PoseArgs<JOINT> &a, hcStream stream) {
     hipStream_t s = (hipStream_t)stream;
     (void)hipGetLastError();
-    if ((g_last_hip_error = hipMemsetAsync(a.sels, 0, sizeof(Selection<JOINT>) * (size_t)a.num_sel, s)) != hipSuccess)
-        return HC_ERROR_LAUNCH;
+    const hcStatus zs = zero_selections(a.sels, (size_t)a.num_sel, s);
+    if (zs != HC_SUCCESS) return zs;
     if (a.num_paths > 0) {
         int blocks = 0;
         const hcStatus st = path_grid(a.num_paths, blocks);
@@ -738,8 +760,8 @@ hcStatus launch_pose_topk(const TopkArgs &a, hcStream stream) {
     hipStream_t s = (hipStream_t)stream;
     const int slots = a.num_groups * a.k;
     (void)hipGetLastError();
-    if ((g_last_hip_error = hipMemsetAsync(a.cand, 0, sizeof(hcTrifocalSelection) * (size_t)slots, s)) != hipSuccess)
-        return HC_ERROR_LAUNCH;
+    const hcStatus zs = zero_selections(a.cand, (size_t)slots, s);
+    if (zs != HC_SUCCESS) return zs;
     if (a.num_paths > 0) {
         const int want = (a.num_paths + 255) / 256;
         hipLaunchKernelGGL(k_pose_topk<GROUPED>, dim3(want < 2048 ? want : 2048), dim3(256), 0, s, a);

@@ -260,7 +260,11 @@ class DeviceTracker:
         time_slicing (tracking launches): suspend and resume paths at step
         boundaries so every path starts early (hc_trifocal_workspace_size_for;
         bit-identical results).  The default workspace grows to the size that
-        enables it; a caller's workspace enables it if it is large enough."""
+        enables it; a caller's workspace enables it if it is large enough.
+        Growing the default workspace synchronises the device, so a launch that
+        is recorded in a graph (torch.cuda.graph) must pass its own workspace,
+        already sized: new_workspace(num_samples), or new_workspace() to run
+        without slicing (tests/test_gpu_graph_replay.py)."""
         if num_samples is None:
             num_samples = target.shape[0] - sample_offset
         if num_samples < 0 or sample_offset < 0 or sample_offset + num_samples > target.shape[0] or \
