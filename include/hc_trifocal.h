@@ -223,7 +223,8 @@ hcStatus hc_trifocal_2op1p_30x30_track_abort_grouped(const hcTrackArgs *args, co
  * the triplet's edgels. */
 typedef struct {
     float    min_joint_ratio;   /* > 0, finite; a value > 1 never passes */
-    int32_t  pad;
+    int32_t  pad;               /* HC_GATE_ADAPTIVE (adaptive/hc_trifocal_adaptive.h): this gate
+                                   is the head of an hcAdaptiveGate; any other value: ignored */
     int32_t *joint_inliers;     /* optional, 312*N ints, caller sets -1: the joint
                                    count of every scored path */
 } hcJointGate;                  /* 16 bytes */

@@ -27,6 +27,10 @@
 #             (scripts/gated_stop.py [TRIALS]) -> TAG_gated.json
 #   gated_ab  the launches that existed before the gated one (scripts/gated_stop.py --existing) on builds
 #             NAME=lib/libX.so ... (package-relative), alternately, 2 rounds -> TAG_gated_existing.jsonl
+#   adaptive  the gated launch's adaptive sample limit against a fixed budget and the ratio gate, config-5 protocol
+#             (scripts/adaptive_stop.py [TRIALS]) -> TAG_adaptive.json
+#   adaptive_ab  config 2, one sample and the gated launch on the noisy 300-sample data (scripts/adaptive_stop.py
+#             --existing) on builds NAME=lib/libX.so ... (package-relative), alternately, 2 rounds -> TAG_adaptive_existing.jsonl
 #   p2c       the ablation ladder from the archived P2C tracker up: P2C, PH, PH_CodeOpt and the headline launch
 #             alternately on config 2 (scripts/ablation_p2c.py [--reps R]) -> TAG_ablation_p2c.json
 #   validate  tests,luwork,bench,profile,datasets
@@ -111,6 +115,17 @@ for k,v in sorted(g.items()): print(k, v)" ;;
     refine) run refine 600 python scripts/refine_pose.py "$@" > $O/${T}_refine.json; rc=$?; tail -c 1500 $O/${T}_refine.json ;;
     topk) run topk 600 python scripts/topk_refine.py "$@" > $O/${T}_topk.json; rc=$?; tail -c 1500 $O/${T}_topk.json ;;
     gated) run gated 900 python scripts/gated_stop.py "$@" > $O/${T}_gated.json; rc=$?; tail -c 600 $O/${T}_gated.json ;;
+    adaptive) run adaptive 900 python scripts/adaptive_stop.py "$@" > $O/${T}_adaptive.json; rc=$?; tail -c 600 $O/${T}_adaptive.json ;;
+    adaptive_ab)
+      rc=0
+      for rd in 0 1; do
+        for kv in "$@"; do
+          HC_TRIFOCAL_LIB=$P/${kv#*=} run existing_${kv%%=*} 200 python scripts/adaptive_stop.py --existing > $O/${T}_tmp.json; rc=$?
+          [ $rc -eq 0 ] || break 2
+          python -c "import json; d=json.load(open('$O/${T}_tmp.json')); d.update(build='${kv%%=*}', round=$rd); print(json.dumps(d))" >> $O/${T}_adaptive_existing.jsonl
+        done
+      done
+      [ -f $O/${T}_adaptive_existing.jsonl ] && cat $O/${T}_adaptive_existing.jsonl ;;
     p2c) run p2c 300 python scripts/ablation_p2c.py --out $O/${T}_ablation_p2c.json "$@"; rc=$? ;;
     gated_ab)
       rc=0

@@ -8,9 +8,9 @@ The boundary is described once: the ctypes mirrors of the argument structs and
 SIGNATURES, one (name, restype, argtypes, optional) entry per declared function.
 lib() binds the table, DECLARED_SYMBOLS is its names, and tests/test_abi_host.py
 holds both against the headers (layouts through the C compiler, signatures
-against the prototypes).  The three headers in directories of their own
-(include/p2c, include/refine, include/topk) have tables of their own,
-P2C_SIGNATURES, REFINE_SIGNATURES and TOPK_SIGNATURES, checked the same way.  Callers go through two helpers: ptr(x), the c_void_p
+against the prototypes).  The headers in directories of their own
+(include/p2c, include/refine, include/topk, include/adaptive) have tables of their own,
+P2C_SIGNATURES, REFINE_SIGNATURES, TOPK_SIGNATURES and ADAPTIVE_SIGNATURES, checked the same way.  Callers go through two helpers: ptr(x), the c_void_p
 of a tensor, array or stream, and call(name, *args), which raises HCError on a
 status other than HC_SUCCESS.
 """
@@ -120,6 +120,19 @@ class hcJointGate(C.Structure):
     _fields_ = [("min_joint_ratio", C.c_float),
                 ("pad", C.c_int32),
                 ("joint_inliers", C.c_void_p)]
+
+
+HC_GATE_ADAPTIVE = 0x41445031   # include/adaptive/hc_trifocal_adaptive.h: hcJointGate::pad of an hcAdaptiveGate
+
+
+class hcAdaptiveGate(C.Structure):
+    """include/adaptive/hc_trifocal_adaptive.h: the gate of the gated launch's
+    adaptive mode, 48 bytes; its address is passed as the hcJointGate's."""
+    _fields_ = [("head", hcJointGate),
+                ("need", C.c_void_p),
+                ("need_offset", C.c_void_p),
+                ("sample_ordinal", C.c_void_p),
+                ("group_limit", C.c_void_p)]
 
 
 class hcP2cArgs(C.Structure):
@@ -273,6 +286,14 @@ LU_VARIANTS = ("throughput", "throughput_twin", "abort", "abort_twin", "small", 
                "archived_twin")
 LU_DECLARED_SYMBOLS = tuple(s.name for s in LU_SIGNATURES)
 
+# include/adaptive/hc_trifocal_adaptive.h, the adaptive sample limit's header beside
+# include/hc_trifocal.h: no launch of its own (a mode of the gated one), one host
+# function; its table, bound and checked the same way (tests/test_adaptive_host.py)
+ADAPTIVE_SIGNATURES = (
+    Sig("hc_ransac_need_table", _ST, (_i, C.c_double, _i, _i, _p), True),
+)
+ADAPTIVE_DECLARED_SYMBOLS = tuple(s.name for s in ADAPTIVE_SIGNATURES)
+
 _lib = None
 
 
@@ -288,7 +309,8 @@ def lib() -> C.CDLL:
         # instead of pulling a second HIP/HSA runtime from /opt/rocm.
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
-        for s in SIGNATURES + P2C_SIGNATURES + REFINE_SIGNATURES + TOPK_SIGNATURES + LU_SIGNATURES:
+        for s in SIGNATURES + P2C_SIGNATURES + REFINE_SIGNATURES + TOPK_SIGNATURES + LU_SIGNATURES + \
+                ADAPTIVE_SIGNATURES:
             fn = getattr(L, s.name, None)
             if fn is None:
                 if s.optional:

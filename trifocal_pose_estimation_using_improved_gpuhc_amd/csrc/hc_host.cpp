@@ -10,6 +10,7 @@
 #include "../../include/hc_pose.h"
 #include "../../include/p2c/hc_trifocal_p2c.h"
 #include "../../include/topk/hc_pose_topk.h"
+#include "../../include/adaptive/hc_trifocal_adaptive.h"
 
 #include <cmath>
 #include <cstdio>
@@ -358,6 +359,31 @@ hcStatus hc_p2c_coefficients(int num_samples, const int32_t *coeff_map, const hc
             hx[0] = c0; hx[1] = c1; hx[2] = c2;
             ht[0] = c1; ht[1] = add(c2, c2);
         }
+    }
+    return HC_SUCCESS;
+}
+
+// The adaptive sample limit's table (include/adaptive/hc_trifocal_adaptive.h): the
+// standard RANSAC rule for three edgels per sample, in double; entry c is the number
+// of samples a best hypothesis of c joint inliers still asks for.
+hcStatus hc_ransac_need_table(int num_edgels, double confidence, int min_samples, int max_samples, int32_t *need) {
+    if (num_edgels <= 0 || !(confidence > 0.0 && confidence < 1.0) || min_samples < 1 || max_samples < min_samples ||
+        !need)
+        return HC_ERROR_INVALID_VALUE;
+    const double lp = std::log(1.0 - confidence);
+    for (int c = 0; c <= num_edgels; c++) {
+        const double w = (double)c / (double)num_edgels;
+        const double q = 1.0 - w * w * w;
+        double n;
+        if (q <= 0.0) {
+            n = 0.0;
+        } else if (q >= 1.0) {
+            n = (double)max_samples;
+        } else {
+            n = std::ceil(lp / std::log(q));
+            if (!std::isfinite(n)) n = (double)max_samples;
+        }
+        need[c] = n <= (double)min_samples ? min_samples : n >= (double)max_samples ? max_samples : (int32_t)n;
     }
     return HC_SUCCESS;
 }

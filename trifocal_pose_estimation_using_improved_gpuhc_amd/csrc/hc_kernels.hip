@@ -29,6 +29,7 @@
 #include "../../include/hc_trifocal_testing.h"
 #include "../../include/p2c/hc_trifocal_p2c.h"
 #include "../../include/lu/hc_lu_testing.h"
+#include "../../include/adaptive/hc_trifocal_adaptive.h"
 
 #include <atomic>
 #include <climits>
@@ -127,7 +128,8 @@ struct TrackLaunch {
     TrackMode mode;
     const hcAbortArgs *ab = nullptr;          // Abort
     const hcGroupedAbortArgs *gr = nullptr;   // GroupedAbort, GatedAbort (non-null: checked by the entry point)
-    const hcJointGate *jg = nullptr;          // GatedAbort (validated by its entry point)
+    const hcJointGate *jg = nullptr;          // GatedAbort (validated by its entry point); with pad ==
+                                              // HC_GATE_ADAPTIVE the head of an hcAdaptiveGate
     const hcP2cArgs *p2c = nullptr;           // P2c (non-null, its pointers too: checked by the entry point)
 };
 
@@ -139,7 +141,7 @@ struct TrackLaunch {
 // this function first names them, after the plain kernels: a
 // new kernel is named after all of them, as the P2C pair below.
 struct TrackKernels { const void *lus, *any; };
-static TrackKernels track_kernels(TrackMode mode, bool small) {
+static TrackKernels track_kernels(TrackMode mode, bool small, bool adaptive = false) {
     static const void *const by_mode[2][6] = {
         {(const void *)k_track_gated<true>, (const void *)k_track_grouped<true>,
          (const void *)k_track<true, HC_ABORT_MINW, true>, (const void *)k_track<false, 5, true, true>,
@@ -151,6 +153,9 @@ static TrackKernels track_kernels(TrackMode mode, bool small) {
     if (small) return {(const void *)k_track_small<true>, (const void *)k_track_small<false>};
     // (named last, after the small-launch pair: every older instantiation keeps its place)
     if (mode == TrackMode::P2c) return {(const void *)k_track_p2c<true>, (const void *)k_track_p2c<false>};
+    // (and after those: the gated launch's adaptive mode, hcAdaptiveGate)
+    if (mode == TrackMode::GatedAbort && adaptive)
+        return {(const void *)k_track_adaptive<true>, (const void *)k_track_adaptive<false>};
     return {by_mode[0][(int)mode], by_mode[1][(int)mode]};
 }
 
@@ -180,10 +185,14 @@ static hcStatus launch_track(const hcTrackArgs *t, const TrackLaunch &l, void *w
     const hcAbortArgs *ab = l.mode == TrackMode::Abort ? l.ab : nullptr;
     const hcGroupedAbortArgs *gr = grouped ? l.gr : nullptr;
     const hcP2cArgs *pc = l.mode == TrackMode::P2c ? l.p2c : nullptr;
+    // the gated launch's adaptive mode: the gate is the head of an hcAdaptiveGate
+    const hcAdaptiveGate *ag =
+        gated && l.jg->pad == (int32_t)HC_GATE_ADAPTIVE ? reinterpret_cast<const hcAdaptiveGate *>(l.jg) : nullptr;
     if (!t || t->sub_ransac_iters < 0) return HC_ERROR_INVALID_VALUE;
     if (grouped && (gr->num_groups < 1 || !gr->groups || !gr->sample_group || !gr->group_found ||
                     !gr->trifocal_sols_batch_index))
         return HC_ERROR_INVALID_VALUE;
+    if (ag && (!ag->need || !ag->need_offset || !ag->sample_ordinal || !ag->group_limit)) return HC_ERROR_INVALID_VALUE;
     if (!workspace || wsb < ws_bytes_needed()) return HC_ERROR_WORKSPACE;
     if (t->sub_ransac_iters == 0) return HC_SUCCESS;
     if ((!t->start_sols && !t->start_sols_array) || (!t->tracks && !t->track_array) || !t->converge || !t->infinity)
@@ -237,6 +246,12 @@ static hcStatus launch_track(const hcTrackArgs *t, const TrackLaunch &l, void *w
             k.gate_ratio = l.jg->min_joint_ratio;
             k.joint_inliers = l.jg->joint_inliers;
         }
+        if (ag) {
+            k.need = ag->need;
+            k.need_offset = (const long long *)ag->need_offset;
+            k.sample_ordinal = ag->sample_ordinal;
+            k.group_limit = ag->group_limit;
+        }
     } else if (ab) {
         k.num_edgels = ab->num_triplet_edgels;
         k.inflight_stop = ab->inflight_stop ? 1 : 0;
@@ -268,7 +283,7 @@ static hcStatus launch_track(const hcTrackArgs *t, const TrackLaunch &l, void *w
     if (launch_status(HC_ERROR_LAUNCH) != HC_SUCCESS) return HC_ERROR_LAUNCH;
     // the twin is enqueued after the specialised kernel: exactly one of the two
     // tracks (EvalTables::lu_struct), the other returns at its first load
-    const TrackKernels kern = track_kernels(l.mode, small_launch(l.mode, paths));
+    const TrackKernels kern = track_kernels(l.mode, small_launch(l.mode, paths), ag != nullptr);
     const int grid = grid_for((int)((paths + 1) / 2), kern.lus);
     const int grid_any = grid_for((int)((paths + 1) / 2), kern.any);
     if (grid <= 0 || grid_any <= 0) return HC_ERROR_DEVICE;

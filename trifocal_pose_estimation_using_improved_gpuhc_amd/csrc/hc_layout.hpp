@@ -124,6 +124,13 @@ struct KArgs {
     // gated abort mode (hcJointGate; k_track_gated only)
     float gate_ratio;
     int32_t *joint_inliers;            // or null
+    // adaptive sample limit (hcAdaptiveGate; k_track_adaptive only): a path of sample s of group t is
+    // not tracked once sample_ordinal[s] >= group_limit[t]; a scored path lowers the limit to
+    // need[need_offset[t] + cJ]
+    const int32_t *need;
+    const long long *need_offset;
+    const int32_t *sample_ordinal;
+    unsigned *group_limit;
 };
 // rq layout: counters zeroed by k_prep_tables every launch; meta: the launch
 // epoch, a magic word and the ring entries already cleared (persist)

@@ -1,4 +1,4 @@
-// The tracker kernels: five __global__ wrappers around one textually included
+// The tracker kernels: six __global__ wrappers around one textually included
 // body (hc_track_body.inc; DESIGN.md §3 on why it is no function template).
 #pragma once
 
@@ -41,7 +41,7 @@ __device__ unsigned long long g_diag_phase[13];
 #ifndef HC_SMALL_LAT
 #define HC_SMALL_LAT 16
 #endif
-// The abort kernels (k_track<true, ...>, k_track_grouped, k_track_gated):
+// The abort kernels (k_track<true, ...>, k_track_grouped, k_track_gated, k_track_adaptive):
 // 4 waves/SIMD (the scoring path needs the registers).  Their term tables left
 // the LDS in round 5, where the other waves' LDS traffic was delaying the
 // earliest hypotheses (time to the first pose -2.8 %,
@@ -78,6 +78,7 @@ __global__ void __launch_bounds__(WG_THREADS, MINW) k_track(KArgs a) {
     static_assert(GTAB, "the term tables are read from the workspace");
     constexpr bool GROUPED = false, GATED = false;   // (k_track_grouped, k_track_gated below)
     constexpr bool P2C = false;                      // (k_track_p2c below)
+    constexpr bool ADAPT = false;                    // (k_track_adaptive below)
     // LU (hc_lu.hpp): the abort kernel's time to the first pose is a lone
     // path's latency, so it runs the latency mode (one LDS round trip per pivot
     // step, in batches of HC_LU_LATB_COLS columns); the tracking kernel the
@@ -94,7 +95,7 @@ __global__ void __launch_bounds__(WG_THREADS, MINW) k_track(KArgs a) {
 // HC_SMALL_MINW waves/SIMD and HC_SMALL_LAT columns per LU batch (above).
 template <bool LUS>
 __global__ void __launch_bounds__(WG_THREADS, HC_SMALL_MINW) k_track_small(KArgs a) {
-    constexpr bool ABORT = false, ARCH = false, GROUPED = false, GATED = false, P2C = false;
+    constexpr bool ABORT = false, ARCH = false, GROUPED = false, GATED = false, P2C = false, ADAPT = false;
     constexpr int LULAT = HC_SMALL_LAT;
 #include "hc_track_body.inc"
 }
@@ -108,7 +109,7 @@ __global__ void __launch_bounds__(WG_THREADS, HC_SMALL_MINW) k_track_small(KArgs
 // instantiations keep their code and their names in kernel traces.
 template <bool LUS>
 __global__ void __launch_bounds__(WG_THREADS, HC_ABORT_MINW) k_track_grouped(KArgs a) {
-    constexpr bool ABORT = true, ARCH = false, GROUPED = true, GATED = false, P2C = false;
+    constexpr bool ABORT = true, ARCH = false, GROUPED = true, GATED = false, P2C = false, ADAPT = false;
     constexpr int LULAT = HC_LU_LATB_COLS;
 #include "hc_track_body.inc"
 }
@@ -120,7 +121,7 @@ __global__ void __launch_bounds__(WG_THREADS, HC_ABORT_MINW) k_track_grouped(KAr
 // of its own, so the grouped instantiations keep their code.
 template <bool LUS>
 __global__ void __launch_bounds__(WG_THREADS, HC_ABORT_MINW) k_track_gated(KArgs a) {
-    constexpr bool ABORT = true, ARCH = false, GROUPED = true, GATED = true, P2C = false;
+    constexpr bool ABORT = true, ARCH = false, GROUPED = true, GATED = true, P2C = false, ADAPT = false;
     constexpr int LULAT = HC_LU_LATB_COLS;
 #include "hc_track_body.inc"
 }
@@ -140,8 +141,23 @@ __global__ void __launch_bounds__(WG_THREADS, HC_ABORT_MINW) k_track_gated(KArgs
 // instantiations keep their code.
 template <bool LUS>
 __global__ void __launch_bounds__(WG_THREADS, 5) k_track_p2c(KArgs a) {
-    constexpr bool ABORT = false, ARCH = true, GROUPED = false, GATED = false, P2C = true;
+    constexpr bool ABORT = false, ARCH = true, GROUPED = false, GATED = false, P2C = true, ADAPT = false;
     constexpr int LULAT = 0;
+#include "hc_track_body.inc"
+}
+
+// The gated launch with an adaptive sample limit (include/adaptive/hc_trifocal_adaptive.h,
+// hcAdaptiveGate): k_track_gated's configuration and body with ADAPT on, which adds
+// three pieces: a path is also skipped at dequeue (and, with inflight_stop, stopped
+// at a step boundary) once its sample's ordinal within its triplet has reached the
+// triplet's limit KArgs::group_limit[t], and a scored path lowers that limit to the
+// caller's table entry of its joint count (one agent-scope atomicMin).  Again a
+// kernel of its own, named after all the others, so the existing instantiations
+// keep their code and their names in kernel traces.
+template <bool LUS>
+__global__ void __launch_bounds__(WG_THREADS, HC_ABORT_MINW) k_track_adaptive(KArgs a) {
+    constexpr bool ABORT = true, ARCH = false, GROUPED = true, GATED = true, P2C = false, ADAPT = true;
+    constexpr int LULAT = HC_LU_LATB_COLS;
 #include "hc_track_body.inc"
 }
 

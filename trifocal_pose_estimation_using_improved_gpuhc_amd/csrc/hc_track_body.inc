@@ -1,11 +1,12 @@
-// The body of the tracker kernels k_track, k_track_small, k_track_grouped, k_track_gated and
-// k_track_p2c (hc_track.hpp),
-// included inside each: ABORT, GROUPED, GATED, P2C, ARCH, LUS and LULAT are their
+// The body of the tracker kernels k_track, k_track_small, k_track_grouped, k_track_gated,
+// k_track_p2c and k_track_adaptive (hc_track.hpp),
+// included inside each: ABORT, GROUPED, GATED, P2C, ADAPT, ARCH, LUS and LULAT are their
 // template parameters or constants, `a` their argument block.  GATED
 // (k_track_gated) replaces the scoring block of PH_FINISH and nothing else; P2C
-// (k_track_p2c) the source of the prefix tables and the first step size.
+// (k_track_p2c) the source of the prefix tables and the first step size; ADAPT
+// (k_track_adaptive) adds the sample limit's two tests and its atomicMin.
 // Included textually on purpose (DESIGN.md §3.2): a change here is a codegen
-// change of all fourteen instantiations.  The other names it takes from its
+// change of all sixteen instantiations.  The other names it takes from its
 // surroundings:
 //   hc_layout.hpp  KArgs, Workspace, WG_THREADS, WAVES_PER_WG, PRIO_TENTHS,
 //                  path_of_queue_pos, SLICE_Q, SLICE_QBIG, SUSP_WORDS, RQ_*
@@ -133,6 +134,13 @@
                             in31 = c.c31;
                             if (r == 0) {
                                 if (a.joint_inliers) a.joint_inliers[b] = c.cJ;
+                                if constexpr (ADAPT) {
+                                    // the samples this count still asks for (the caller's table of the
+                                    // triplet): the best hypothesis so far sets the triplet's limit
+                                    __hip_atomic_fetch_min(&a.group_limit[grp],
+                                                           (unsigned)a.need[a.need_offset[grp] + (long long)c.cJ],
+                                                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                                }
                                 if ((double)c.cJ >= (double)a.gate_ratio * (double)g.num_edgels) {
                                     __hip_atomic_store(&a.group_found[grp], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                                     a.batch_index[b] = b;
@@ -243,6 +251,14 @@
                         // the caller: the carry-over of an earlier launch's find)
                         skip = __hip_atomic_load(&a.group_found[a.sample_group[b / NTRK]], __ATOMIC_RELAXED,
                                                  __HIP_MEMORY_SCOPE_AGENT) != 0u;
+                        if constexpr (ADAPT) {
+                            // the triplet's sample limit (lowered by this launch's scored paths, or
+                            // preset by the caller): samples from the limit on are not tracked
+                            const int sq = b / NTRK;
+                            skip = skip || (unsigned)a.sample_ordinal[sq] >=
+                                               __hip_atomic_load(&a.group_limit[a.sample_group[sq]], __ATOMIC_RELAXED,
+                                                                 __HIP_MEMORY_SCOPE_AGENT);
+                        }
                         skip = bcast_half0((int)skip) != 0;
                         if (skip && r == 0) {
                             a.conv[b] = 0;
@@ -464,6 +480,14 @@
                 found_seen = ph == PH_STAGE ? __hip_atomic_load(&a.group_found[a.sample_group[smp_loaded]],
                                                                 __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
                                             : 0u;
+            if constexpr (ADAPT) {
+                // ... or the triplet's sample limit has come down to this path's sample
+                if (a.inflight_stop && ph == PH_STAGE)
+                    found_seen |= (unsigned)a.sample_ordinal[smp_loaded] >=
+                                          __hip_atomic_load(&a.group_limit[a.sample_group[smp_loaded]], __ATOMIC_RELAXED,
+                                                            __HIP_MEMORY_SCOPE_AGENT)
+                                      ? 1u : 0u;
+            }
         } else if (ABORT && a.inflight_stop) {
             found_seen = __hip_atomic_load(&ws->found, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             // (the peer flag's xGMI round trip is hidden by the stage that follows)

@@ -64,7 +64,9 @@ class TripletBatch:
     interleave=True round-robin (sample 0 of every triplet, then sample 1, ...).
 
     target, diff (N, 34, 2), picked (N, 3): the concatenated rows;
-    sample_group (N,) int32; index[t]: the rows of triplet t, in its own order.
+    sample_group (N,) int32; index[t]: the rows of triplet t, in its own order;
+    sample_ordinal (N,) int32: a row's index among its own triplet's rows, in
+    launch order (the adaptive sample limit compares it with the triplet's limit).
     """
 
     def __init__(self, problem: Problem, datas, seeds=0, samples_per_triplet=8, interleave: bool = False,
@@ -97,6 +99,7 @@ class TripletBatch:
             order = [(k, t) for t in range(T) for k in range(counts[t])]
         self.num_samples = len(order)
         self.sample_group = np.array([t for _, t in order], np.int32)
+        self.sample_ordinal = np.array([k for k, _ in order], np.int32)
         self.target = np.ascontiguousarray(np.stack([parts[t][0][k] for k, t in order])) if order else parts[0][0]
         self.diff = np.ascontiguousarray(np.stack([parts[t][1][k] for k, t in order])) if order else parts[0][1]
         self.picked = np.ascontiguousarray(np.stack([parts[t][2][k] for k, t in order])) if order else parts[0][2]
@@ -113,7 +116,7 @@ class TripletBatch:
 
 class DeviceTripletBatch:
     """Device copies of a TripletBatch: target, diff, the concatenated edgels
-    (sum E, 6), K (T, 9), sample_group (N,) int32 and `groups`, the
+    (sum E, 6), K (T, 9), sample_group and sample_ordinal (N,) int32 and `groups`, the
     hcTripletGroup array (T x 24 bytes) whose pointers go into edgels / K."""
 
     def __init__(self, batch: TripletBatch, device):
@@ -129,6 +132,7 @@ class DeviceTripletBatch:
         self.edgels = torch.from_numpy(np.ascontiguousarray(np.concatenate(batch.locations))).to(dev)
         self.K = torch.from_numpy(np.ascontiguousarray(np.stack(batch.Ks))).to(dev)
         self.sample_group = torch.from_numpy(batch.sample_group).to(dev)
+        self.sample_ordinal = torch.from_numpy(batch.sample_ordinal).to(dev)
         self.edgel_offsets = np.concatenate([[0], np.cumsum(batch.edgel_counts[:-1], dtype=np.int64)]).astype(np.int64)
         g = np.zeros(batch.num_groups, GROUP_DTYPE)
         g["locations"] = self.edgels.data_ptr() + self.edgel_offsets * 24     # E x 6 floats per triplet

@@ -44,6 +44,8 @@ class TrackResult:
     found_ticks: torch.Tensor | None = None
     # gated abort mode: (312N,) int32, the joint inlier count of every scored path, -1 elsewhere
     joint_inliers: torch.Tensor | None = None
+    # adaptive sample limit: (T,) int32, in/out: each triplet's limit (its budget on entry of a fresh run)
+    limit: torch.Tensor | None = None
 
     def host(self):
         out = dict(tracks=self.tracks.cpu().numpy(), converge=self.converge.cpu().numpy(),
@@ -59,6 +61,8 @@ class TrackResult:
             out["batch_index"] = self.batch_index.cpu().numpy()
         if self.joint_inliers is not None:
             out["joint_inliers"] = self.joint_inliers.cpu().numpy()
+        if self.limit is not None:
+            out["limit"] = self.limit.cpu().numpy()
         return out
 
 
@@ -71,6 +75,78 @@ def gate_ratio(gate) -> float:
     if not (np.isfinite(v) and v > 0.0):
         raise _abi.HCError(f"gate must be finite and positive as a float32 (got {gate!r})")
     return v
+
+
+def need_table(num_edgels: int, confidence: float, min_samples: int = 1, max_samples: int = 2**31 - 1) -> np.ndarray:
+    """hc_ransac_need_table: the (E + 1,) int32 table of the standard RANSAC
+    rule for three edgels per sample; entry c is the number of samples needed
+    for `confidence` after a hypothesis with c of E joint inliers,
+    ceil(log(1 - p) / log(1 - (c / E)^3)) clamped to [min_samples, max_samples]."""
+    E = int(num_edgels)
+    need = np.empty(max(E, 0) + 1, np.int32)
+    _abi.call("hc_ransac_need_table", E, float(confidence), int(min_samples), int(max_samples), _abi.ptr(need))
+    return need
+
+
+class AdaptiveStop:
+    """The adaptive sample limit of a gated launch (launch_grouped(adaptive=...)):
+    every scored path lowers its triplet's limit to the rule's sample count for
+    its joint inlier count, and samples from the limit on are not tracked.
+
+    confidence in (0, 1); min_samples >= 1; max_samples (default: the triplet's
+    own sample count) caps a table's entries.  tables (optional): one int32
+    array of E_t + 1 entries per triplet that replaces the built tables (another
+    rule, or a test's)."""
+
+    def __init__(self, confidence: float = 0.99, min_samples: int = 1, max_samples: int | None = None, tables=None):
+        if isinstance(confidence, bool) or not isinstance(confidence, (float, np.floating)) or \
+                not 0.0 < float(confidence) < 1.0:
+            raise _abi.HCError(f"AdaptiveStop: confidence must be a float in (0, 1) (got {confidence!r})")
+        for what, v in (("min_samples", min_samples), ("max_samples", max_samples)):
+            if v is None and what == "max_samples":
+                continue
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 1:
+                raise _abi.HCError(f"AdaptiveStop: {what} must be an integer >= 1 (got {v!r})")
+        if max_samples is not None and int(max_samples) < int(min_samples):
+            raise _abi.HCError("AdaptiveStop: max_samples < min_samples")
+        if tables is not None:
+            if isinstance(tables, np.ndarray) or not hasattr(tables, "__len__") or len(tables) < 1:
+                raise _abi.HCError("AdaptiveStop: tables is a list of one array per triplet")
+            tabs = []
+            for t, tab in enumerate(tables):
+                a = np.asarray(tab)
+                if a.ndim != 1 or a.shape[0] < 2 or not np.issubdtype(a.dtype, np.integer) or \
+                        (a < 0).any() or (a > 2**31 - 1).any():
+                    raise _abi.HCError(f"AdaptiveStop: table {t} must hold E + 1 >= 2 non-negative int32 values")
+                tabs.append(np.ascontiguousarray(a, np.int32))
+            tables = tabs
+        self.confidence, self.min_samples = float(confidence), int(min_samples)
+        self.max_samples = None if max_samples is None else int(max_samples)
+        self.tables = tables
+        self._prepared = None   # (batch, need, need_offset): the device copies made for the last batch
+
+    def host_tables(self, edgel_counts, sample_counts) -> list:
+        """The triplets' tables: the caller's, checked against the edgel
+        counts, or hc_ransac_need_table's."""
+        if self.tables is not None:
+            if len(self.tables) != len(edgel_counts) or \
+                    any(t.shape[0] != int(e) + 1 for t, e in zip(self.tables, edgel_counts)):
+                raise _abi.HCError("AdaptiveStop: one table of E + 1 entries per triplet")
+            return self.tables
+        return [need_table(int(e), self.confidence, self.min_samples,
+                           max(self.max_samples if self.max_samples is not None else int(n), self.min_samples))
+                for e, n in zip(edgel_counts, sample_counts)]
+
+    def prepare(self, batch):
+        """(need, need_offset), the device copies of the tables for batch (a
+        multi.DeviceTripletBatch), made once per batch: call it before a launch
+        that is recorded in a graph."""
+        if self._prepared is None or self._prepared[0] is not batch:
+            tabs = self.host_tables(batch.host.edgel_counts, [len(i) for i in batch.host.index])
+            off = np.concatenate([[0], np.cumsum([t.shape[0] for t in tabs[:-1]], dtype=np.int64)]).astype(np.int64)
+            self._prepared = (batch, torch.from_numpy(np.concatenate(tabs)).to(batch.device),
+                              torch.from_numpy(off).to(batch.device))
+        return self._prepared[1], self._prepared[2]
 
 
 class DeviceTracker:
@@ -158,19 +234,25 @@ class DeviceTracker:
         a.stats = r.stats[p0:].data_ptr() if r.stats is not None else None
         return a
 
-    def allocate_grouped(self, batch, stats: bool = True, gate: bool = False) -> TrackResult:
+    def allocate_grouped(self, batch, stats: bool = True, gate: bool = False, adaptive: bool = False) -> TrackResult:
         """Buffers of a grouped launch over batch (a multi.DeviceTripletBatch):
         as allocate(abort=True), with one found word and one tick per triplet;
-        gate: also the per-path joint inlier counts of a gated launch."""
+        gate: also the per-path joint inlier counts of a gated launch;
+        adaptive: those and the triplets' sample limits, set to each triplet's
+        sample count (the budget of a fresh run)."""
+        gate = gate or adaptive
         r = self.allocate(batch.num_samples, stats=stats, abort=True)
         r.found = torch.zeros(batch.num_groups, dtype=torch.int32, device=self.device)
         r.found_ticks = torch.zeros(batch.num_groups, dtype=torch.int64, device=self.device)
         if gate:
             r.joint_inliers = torch.full((batch.num_samples * 312,), -1, dtype=torch.int32, device=self.device)
+        if adaptive:
+            r.limit = torch.from_numpy(np.array([len(i) for i in batch.host.index], np.int32)).to(self.device)
         return r
 
     def launch_grouped(self, batch, r: TrackResult, stream: torch.cuda.Stream | None = None,
-                       workspace: torch.Tensor | None = None, inflight_stop: bool = False, gate=None) -> None:
+                       workspace: torch.Tensor | None = None, inflight_stop: bool = False, gate=None,
+                       adaptive=None) -> None:
         """Enqueue one grouped (multi-triplet) abort-mode run on `stream` (no
         synchronisation): hc_trifocal_2op1p_30x30_track_abort_grouped over all of
         batch's samples (a multi.DeviceTripletBatch) into r (allocate_grouped).
@@ -186,8 +268,20 @@ class DeviceTracker:
         E edgels with the pose-support test, and sets its triplet's flag iff its
         joint count (edgels within 2 px in both views) is at least gate * E.
         r.joint_inliers (allocate_grouped(gate=True)) receives every scored
-        path's joint count, r.stats its two per-view counts."""
+        path's joint count, r.stats its two per-view counts.
+        adaptive (an AdaptiveStop, default None): the gated launch's adaptive
+        mode (include/adaptive/hc_trifocal_adaptive.h); without gate the ratio
+        is 2.0, which never fires.  A path is also skipped once its sample's
+        index within its triplet (batch.sample_ordinal) has reached r.limit[t]
+        (allocate_grouped(adaptive=True); in/out, the carry-over between
+        launches as r.found is), and a scored path lowers r.limit[t] to its
+        triplet's table entry of its joint count."""
         ratio = None if gate is None else gate_ratio(gate)
+        if adaptive is not None:
+            if not isinstance(adaptive, AdaptiveStop):
+                raise _abi.HCError(f"adaptive must be an AdaptiveStop, not {type(adaptive).__name__}")
+            if ratio is None:
+                ratio = 2.0
         if batch.target.device != self.start_sols.device:
             raise _abi.HCError("the batch lives on another device")
         batch.check()   # group ids and edgel counts: the kernels do not validate them
@@ -198,6 +292,8 @@ class DeviceTracker:
         if ratio is not None and (r.joint_inliers is None or r.joint_inliers.numel() < n * 312 or
                                   r.joint_inliers.dtype != torch.int32):
             raise _abi.HCError("a gated launch needs r.joint_inliers (allocate_grouped(gate=True))")
+        if adaptive is not None and (r.limit is None or r.limit.numel() < T or r.limit.dtype != torch.int32):
+            raise _abi.HCError("an adaptive launch needs r.limit (allocate_grouped(adaptive=True))")
         ws_t = self._workspace(workspace)
         a = self._track_args(r, batch.target, batch.diff, 0, n)
         g = _abi.hcGroupedAbortArgs()
@@ -211,31 +307,49 @@ class DeviceTracker:
         s = stream if stream is not None else torch.cuda.current_stream(self.device)
         name, blocks = "hc_trifocal_2op1p_30x30_track_abort_grouped", [C.byref(a), C.byref(g)]
         if ratio is not None:
-            jg = _abi.hcJointGate()
-            jg.min_joint_ratio = ratio
-            jg.joint_inliers = r.joint_inliers.data_ptr()
+            ag = _abi.hcAdaptiveGate()   # its head alone is the plain gated launch's hcJointGate
+            ag.head.min_joint_ratio = ratio
+            ag.head.joint_inliers = r.joint_inliers.data_ptr()
+            if adaptive is not None:
+                need, need_offset = adaptive.prepare(batch)
+                ag.head.pad = _abi.HC_GATE_ADAPTIVE
+                ag.need, ag.need_offset = need.data_ptr(), need_offset.data_ptr()
+                ag.sample_ordinal = batch.sample_ordinal.data_ptr()
+                ag.group_limit = r.limit.data_ptr()
             name = "hc_trifocal_2op1p_30x30_track_abort_gated"
-            blocks.append(C.byref(jg))
+            blocks.append(C.cast(C.pointer(ag), C.POINTER(_abi.hcJointGate)))
         _abi.call(name, *blocks, _abi.ptr(ws_t), self.ws_bytes, _abi.ptr(s))
 
     def track_grouped(self, batch, inflight_stop: bool = False, stats: bool = True, found=None,
-                      gate=None) -> TrackResult:
+                      gate=None, adaptive=None, limit=None) -> TrackResult:
         """Synchronous convenience wrapper of launch_grouped, as track(abort=True):
         batch is a multi.TripletBatch or its device copy.  found (optional, T
         values): the triplets' flags on entry (a set one skips its triplet).
-        gate (a float ratio): the gated launch; the result carries joint_inliers."""
+        gate (a float ratio): the gated launch; the result carries joint_inliers.
+        adaptive (an AdaptiveStop): the adaptive sample limit; the result
+        carries limit, the triplets' final limits.  limit (optional, T values):
+        the limits on entry (default: each triplet's sample count)."""
         if gate is not None:
             gate_ratio(gate)
+        if adaptive is not None and not isinstance(adaptive, AdaptiveStop):
+            raise _abi.HCError(f"adaptive must be an AdaptiveStop, not {type(adaptive).__name__}")
+        if limit is not None and adaptive is None:
+            raise _abi.HCError("limit is the adaptive launch's (pass adaptive=AdaptiveStop(...))")
         if not hasattr(batch, "groups"):
             batch = batch.to(self.device)
-        r = self.allocate_grouped(batch, stats=stats, gate=gate is not None)
+        r = self.allocate_grouped(batch, stats=stats, gate=gate is not None, adaptive=adaptive is not None)
         self.reset_tracks(r)
         if found is not None:
             f = np.ascontiguousarray(found, np.int32).reshape(-1)
             if f.shape[0] != batch.num_groups:
                 raise _abi.HCError("one initial flag per triplet")
             r.found.copy_(torch.from_numpy(f))
-        self.launch_grouped(batch, r, inflight_stop=inflight_stop, gate=gate)
+        if limit is not None:
+            lim = np.ascontiguousarray(limit, np.int64).reshape(-1)
+            if lim.shape[0] != batch.num_groups or (lim < 0).any() or (lim > 2**31 - 1).any():
+                raise _abi.HCError("one initial limit per triplet, each in [0, 2^31)")
+            r.limit.copy_(torch.from_numpy(lim.astype(np.int32)))
+        self.launch_grouped(batch, r, inflight_stop=inflight_stop, gate=gate, adaptive=adaptive)
         torch.cuda.synchronize(self.device)
         self.workspace_status()
         return r
