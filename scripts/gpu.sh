@@ -31,6 +31,11 @@
 #             (scripts/adaptive_stop.py [TRIALS]) -> TAG_adaptive.json
 #   adaptive_ab  config 2, one sample and the gated launch on the noisy 300-sample data (scripts/adaptive_stop.py
 #             --existing) on builds NAME=lib/libX.so ... (package-relative), alternately, 2 rounds -> TAG_adaptive_existing.jsonl
+#   scale     the relative scale fitted by three-view transfer support, config-5 protocol, selection by joint count
+#             against selection by transfer count, and the cost of the scale step (scripts/scale_fit.py [TRIALS [REPS]])
+#             -> TAG_scale.json
+#   scale_ab  the refine calls with the scale mode off (scripts/scale_fit.py --existing) on builds NAME=lib/libX.so ...
+#             (package-relative), alternately, 3 rounds -> TAG_scale_existing.jsonl
 #   p2c       the ablation ladder from the archived P2C tracker up: P2C, PH, PH_CodeOpt and the headline launch
 #             alternately on config 2 (scripts/ablation_p2c.py [--reps R]) -> TAG_ablation_p2c.json
 #   validate  tests,luwork,bench,profile,datasets
@@ -126,6 +131,17 @@ for k,v in sorted(g.items()): print(k, v)" ;;
         done
       done
       [ -f $O/${T}_adaptive_existing.jsonl ] && cat $O/${T}_adaptive_existing.jsonl ;;
+    scale) run scale 900 python scripts/scale_fit.py "$@" > $O/${T}_scale.json; rc=$?; tail -c 600 $O/${T}_scale.json ;;
+    scale_ab)
+      rc=0
+      for rd in 0 1 2; do
+        for kv in "$@"; do
+          HC_TRIFOCAL_LIB=$P/${kv#*=} run existing_${kv%%=*} 200 python scripts/scale_fit.py --existing > $O/${T}_tmp.json; rc=$?
+          [ $rc -eq 0 ] || break 2
+          python -c "import json; d=json.load(open('$O/${T}_tmp.json')); d.update(build='${kv%%=*}', round=$rd); print(json.dumps(d))" >> $O/${T}_scale_existing.jsonl
+        done
+      done
+      [ -f $O/${T}_scale_existing.jsonl ] && cat $O/${T}_scale_existing.jsonl ;;
     p2c) run p2c 300 python scripts/ablation_p2c.py --out $O/${T}_ablation_p2c.json "$@"; rc=$? ;;
     gated_ab)
       rc=0

@@ -10,7 +10,8 @@ lib() binds the table, DECLARED_SYMBOLS is its names, and tests/test_abi_host.py
 holds both against the headers (layouts through the C compiler, signatures
 against the prototypes).  The headers in directories of their own
 (include/p2c, include/refine, include/topk, include/adaptive) have tables of their own,
-P2C_SIGNATURES, REFINE_SIGNATURES, TOPK_SIGNATURES and ADAPTIVE_SIGNATURES, checked the same way.  Callers go through two helpers: ptr(x), the c_void_p
+P2C_SIGNATURES, REFINE_SIGNATURES, TOPK_SIGNATURES and ADAPTIVE_SIGNATURES, checked the same way
+(include/scale declares structs only: the scale fit is a mode of the refine calls).  Callers go through two helpers: ptr(x), the c_void_p
 of a tensor, array or stream, and call(name, *args), which raises HCError on a
 status other than HC_SUCCESS.
 """
@@ -164,6 +165,29 @@ class hcRefineReport(C.Structure):
 
 
 REFINE_REPORT_BYTES = C.sizeof(hcRefineReport)   # 176
+
+# include/scale/hc_pose_scale.h: the scale fit, a mode of the refine calls (no
+# function of its own; its structs are held against the header by
+# tests/test_scale31_host.py)
+HC_REFINE_SCALE31 = 0x53433331   # hcRefineSettings::pad[0] of an hcRefineScaleSettings
+HC_SCALE_ONLY, HC_SCALE_SELECT_BY_TRANSFER = 1, 2   # pad[1]: mode bits
+HC_SCALE_NONE, HC_SCALE_NO_VOTER = 1, 2              # hcScaleReport::status bits
+
+
+class hcScaleReport(C.Structure):
+    """include/scale/hc_pose_scale.h: what one scale fit did, 40 bytes"""
+    _fields_ = [("status", C.c_int32), ("num_voters", C.c_int32), ("voter", C.c_int32),
+                ("transfer_inliers", C.c_int32), ("tested", C.c_int32), ("joint", C.c_int32),
+                ("scale_in", C.c_float), ("scale31", C.c_float), ("key", C.c_uint64)]
+
+
+class hcRefineScaleSettings(C.Structure):
+    """include/scale/hc_pose_scale.h: the settings of the scale mode, 32 bytes;
+    its address is passed as the hcRefineSettings'."""
+    _fields_ = [("head", hcRefineSettings), ("reports", C.c_void_p), ("transfer_mask", C.c_void_p)]
+
+
+SCALE_REPORT_BYTES = C.sizeof(hcScaleReport)   # 40
 
 
 # One entry per function of include/*.h: restype and argtypes as the prototype

@@ -31,11 +31,14 @@
 // k_pose_topk<GROUPED>, k_pose_topk_final and k_pose_topk_select
 // (include/topk/hc_pose_topk.h, described below the refinement) rank the k best
 // joint candidates and select among their refinements.
+// k_scale_vote<GROUPED> and k_scale_final<GROUPED> (include/scale/hc_pose_scale.h,
+// described at the end) fit a refined selection's scale31 by three-view transfer.
 #include <type_traits>
 
 #include "../../include/hc_pose.h"
 #include "../../include/refine/hc_pose_refine.h"
 #include "../../include/topk/hc_pose_topk.h"
+#include "../../include/scale/hc_pose_scale.h"
 #include "hc_device.hpp"
 #include "hc_pose_device.hpp"   // make_pose, reproj_inlier, edgel_views, is_candidate: shared with the gated tracker
 
@@ -772,14 +775,297 @@ hcStatus launch_pose_topk(const TopkArgs &a, hcStream stream) {
     return HC_SUCCESS;
 }
 
-// k refinements per scene, then the selection among them
+// ---- the relative scale by three-view transfer (include/scale/hc_pose_scale.h) ----
+//
+// A mode of the four refine calls: after k_pose_refine (or instead of it, with
+// HC_SCALE_ONLY) every selection's scale31 is fitted by the vote the header
+// describes, |tested| transfer tests per voter.
+//
+// k_scale_vote<GROUPED>: grid (selections, voter tiles), a tile of 64 voters
+// per workgroup of 8 waves.  Lane l of every wave holds voter v = 64 j + l of
+// tile j: it forms the edgel's candidate scale s_v once and keeps it in a
+// register.  The workgroup then stages the edgels in chunks of SV_CHUNK into
+// LDS -- per edgel Y = R31 X, the tested flag and the view-3 pixel, 24 bytes,
+// recomputed by every workgroup (E^2 / 64 edgel evaluations beside E^2 transfer
+// tests: no scratch buffer, so no allocation) -- and wave w walks entries w,
+// w + 8, ... of the chunk: all lanes read the same address (a broadcast), an
+// edgel outside the tested set is skipped by a scalar branch on its flag, and
+// the lane counts T(e, s_v).  The eight waves' counts of a voter are integers
+// summed through LDS (any order gives the same number); wave 0 forms the keys
+// c_v << 32 | v and reduces them by a butterfly over its lanes; one 64-bit
+// atomicMax and one atomicAdd (the voters) per workgroup go to the selection's
+// hcScaleReport, which k_zero_words has zeroed on the same stream.  Splitting
+// the edgels over the waves, not only the voters over the lanes, is what fills
+// the device: a scene of 5117 edgels gives 80 workgroups of 8 waves, where one
+// voter per thread of a 256-thread workgroup gave 80 waves in all and the walk
+// of 3640 tests per lane, a dependent chain of two divisions and a square root
+// each, took 0.9 ms.  A grouped call does not know its triplets' E on the host:
+// its grid has SV_TILES tiles and a workgroup strides over the voter tiles of
+// its own triplet.
+//
+// k_scale_final<GROUPED>: one workgroup per selection.  It decodes the key,
+// re-evaluates T(e, scale31) of every edgel with the same device functions, one
+// wave per 64 edgels -- the ballot is the transfer mask's word -- counts the
+// tested set and the joint inliers, and writes out (src with only scale31
+// replaced) and the report.
+constexpr int SV_THREADS = 512, SV_WAVES = SV_THREADS / WAVE;   // the vote: 64 voters x 8 slices of the edgels
+constexpr int SV_CHUNK = 2048;   // edgels per LDS stage: 48 KiB
+constexpr int SV_TILES = 128;    // grid.y of a grouped call: 8192 voters without a second pass
+constexpr int SF_THREADS = 256, SF_WAVES = SF_THREADS / WAVE;   // the epilogue
+
+struct ScaleArgs {
+    const hcTrifocalSelection *src;   // the poses to fit: the refinement's out, or with HC_SCALE_ONLY its in
+    hcTrifocalSelection *out;         // may be src
+    hcScaleReport *rep;
+    unsigned long long *mask;         // or nullptr; the single call only
+    int E;                            // the scene, or with GROUPED that of groups[selection / per_group]
+    const float *loc;
+    const float *K;
+    const hcTripletGroup *groups;
+    int per_group;
+};
+
 template <bool GROUPED>
-hcStatus launch_refine_topk(const RefineArgs &a, int num_groups, hcTrifocalSelection *best, int32_t *best_rank,
-                            hcStream stream) {
-    const hcStatus st = launch_pose_refine<GROUPED>(a, num_groups * a.per_group, stream);
-    if (st != HC_SUCCESS) return st;
-    hipLaunchKernelGGL(k_pose_topk_select, dim3((num_groups + 63) / 64), dim3(64), 0, (hipStream_t)stream, num_groups,
-                       a.per_group, a.out, best, best_rank);
+__device__ __forceinline__ Scene scale_scene(const ScaleArgs &a, int sel) {
+    if constexpr (GROUPED) {
+        const hcTripletGroup g = a.groups[sel / a.per_group];
+        return load_scene(g.num_edgels, g.locations, g.K);
+    } else {
+        return load_scene(a.E, a.loc, a.K);
+    }
+}
+
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const unsigned long long o = __shfl_xor(v, m);
+        v = o > v ? o : v;
+    }
+    return v;   // the same in every lane
+}
+
+template <bool GROUPED>
+__global__ void __launch_bounds__(SV_THREADS) k_scale_vote(const ScaleArgs a) {
+    __shared__ float4 s_Y[SV_CHUNK];   // Y0 Y1 Y2 | tested (1.0f or 0.0f)
+    __shared__ float2 s_p[SV_CHUNK];   // the view-3 observation in pixels
+    __shared__ int s_c[SV_WAVES][WAVE];
+    const int tid = threadIdx.x, lane = lane_id(), wave = tid / WAVE, sel = blockIdx.x;
+    const Scene sc = scale_scene<GROUPED>(a, sel);
+    const int tiles = (sc.E + WAVE - 1) / WAVE;
+    const hcTrifocalSelection *S = a.src + sel;
+    if ((int)blockIdx.y >= tiles || S->path < 0) return;   // the whole workgroup
+    float R21[9], t21[3], R31[9], t31[3];
+#pragma unroll
+    for (int i = 0; i < 9; i++) { R21[i] = S->R21[i]; R31[i] = S->R31[i]; }
+#pragma unroll
+    for (int i = 0; i < 3; i++) { t21[i] = S->t21[i]; t31[i] = S->t31[i]; }
+    unsigned long long best = 0;   // wave 0 only
+    int nv = 0;
+    for (int tile = blockIdx.y; tile < tiles; tile += gridDim.y) {
+        const int v = tile * WAVE + lane;   // the same 64 voters in every wave
+        float s_v = 0.0f;
+        bool voter = false;
+        if (v < sc.E) {
+            const TransferEdgel te = transfer_edgel(sc, v, R21, t21, R31, t31, s_v);
+            voter = is_voter(te.tested, s_v);
+        }
+        const bool tile_votes = __ballot(voter) != 0;   // the same in every wave
+        int c = 0;
+        for (int c0 = 0; c0 < sc.E; c0 += SV_CHUNK) {
+            const int n = sc.E - c0 < SV_CHUNK ? sc.E - c0 : SV_CHUNK;
+            __syncthreads();   // the previous stage has been walked, the previous tile's counts read
+            for (int i = tid; i < n; i += SV_THREADS) {
+                float s;
+                const TransferEdgel te = transfer_edgel(sc, c0 + i, R21, t21, R31, t31, s);
+                s_Y[i] = make_float4(te.Y0, te.Y1, te.Y2, te.tested ? 1.0f : 0.0f);
+                s_p[i] = make_float2(te.p0, te.p1);
+            }
+            __syncthreads();
+            if (!tile_votes) continue;
+            for (int i = wave; i < n; i += SV_WAVES) {
+                const float4 Y = s_Y[i];
+                if (__builtin_amdgcn_readfirstlane(__float_as_int(Y.w)) == 0) continue;   // not tested: the same for all lanes
+                const float2 p = s_p[i];
+                c += transfer_inlier(Y.x, Y.y, Y.z, p.x, p.y, s_v, t31, sc.K0, sc.K2, sc.K4, sc.K5) ? 1 : 0;
+            }
+        }
+        s_c[wave][lane] = c;
+        __syncthreads();
+        if (wave == 0 && voter) {
+            int cv = 0;
+#pragma unroll
+            for (int w = 0; w < SV_WAVES; w++) cv += s_c[w][lane];
+            nv++;
+            const unsigned long long key = ((unsigned long long)(uint32_t)cv << 32) | (uint32_t)v;
+            best = key > best ? key : best;
+        }
+    }
+    if (wave != 0) return;
+    best = wave_max_u64(best);
+    nv = wave_sum_i(nv);
+    if (lane == 0 && nv > 0) {
+        atomicAdd(&a.rep[sel].num_voters, nv);
+        key_max(&a.rep[sel].key, best);
+    }
+}
+
+template <bool GROUPED>
+__global__ void __launch_bounds__(SF_THREADS) k_scale_final(const ScaleArgs a) {
+    __shared__ int s_cnt[SF_WAVES][2];
+    const int tid = threadIdx.x, lane = lane_id(), wave = tid / WAVE, sel = blockIdx.x;
+    const Scene sc = scale_scene<GROUPED>(a, sel);
+    // every thread reads src and the vote's words here, before the barrier;
+    // thread 0 writes out and the report after it (out may be src)
+    const hcTrifocalSelection keep = a.src[sel];
+    hcScaleReport *rep = a.rep + sel;
+    const int num_voters = rep->num_voters;
+    const uint64_t key = rep->key;
+    const bool have = keep.path >= 0, fitted = have && num_voters > 0 && (uint32_t)key < (uint32_t)sc.E;
+    const int voter = fitted ? (int)(uint32_t)key : -1;
+    float scale = keep.scale31;
+    if (fitted) {
+        (void)transfer_edgel(sc, voter, keep.R21, keep.t21, keep.R31, keep.t31, scale);   // s_v again, the same bits
+    }
+    const int words = (sc.E + WAVE - 1) / WAVE;
+    int tested = 0, joint = 0;
+    for (int w = wave; w < words; w += SF_WAVES) {
+        const int e = w * WAVE + lane;
+        bool in = false;
+        if (have && e < sc.E) {
+            float s;
+            const TransferEdgel te = transfer_edgel(sc, e, keep.R21, keep.t21, keep.R31, keep.t31, s);
+            tested += te.tested ? 1 : 0;
+            joint += te.joint ? 1 : 0;
+            in = fitted && te.tested &&
+                 transfer_inlier(te.Y0, te.Y1, te.Y2, te.p0, te.p1, scale, keep.t31, sc.K0, sc.K2, sc.K4, sc.K5);
+        }
+        const unsigned long long word = __ballot(in);
+        if (a.mask && lane == 0) a.mask[w] = word;
+    }
+    tested = wave_sum_i(tested);
+    joint = wave_sum_i(joint);
+    if (lane == 0) { s_cnt[wave][0] = tested; s_cnt[wave][1] = joint; }
+    __syncthreads();
+    if (tid != 0) return;
+    tested = joint = 0;
+#pragma unroll
+    for (int w = 0; w < SF_WAVES; w++) { tested += s_cnt[w][0]; joint += s_cnt[w][1]; }
+    hcTrifocalSelection o = keep;
+    o.scale31 = scale;
+    a.out[sel] = o;
+    rep->status = !have ? HC_SCALE_NONE : (fitted ? 0 : HC_SCALE_NO_VOTER);
+    rep->num_voters = have ? num_voters : 0;
+    rep->voter = voter;
+    rep->transfer_inliers = fitted ? (int)(key >> 32) : 0;
+    rep->tested = tested;
+    rep->joint = joint;
+    rep->scale_in = keep.scale31;
+    rep->scale31 = scale;
+    rep->key = fitted ? key : 0;
+}
+
+// HC_SCALE_SELECT_BY_TRANSFER: k_pose_topk_select with the transfer key first.
+// One thread per group: among the fitted selections with a path the largest
+// transfer_inliers << 32 | path, among equal keys the larger joint key; "none"
+// with rank -1 as k_pose_topk_select writes it.
+__global__ void __launch_bounds__(64) k_pose_topk_select_transfer(int num_groups, int k,
+                                                                  const hcTrifocalSelection *__restrict__ refined,
+                                                                  const hcScaleReport *__restrict__ reports,
+                                                                  hcTrifocalSelection *__restrict__ best,
+                                                                  int32_t *__restrict__ best_rank) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= num_groups) return;
+    const hcTrifocalSelection *in = refined + (size_t)t * k;
+    const hcScaleReport *rp = reports + (size_t)t * k;
+    int rank = -1;
+    uint64_t tkey = 0, jkey = 0;
+    for (int r = 0; r < k; r++) {
+        if (in[r].path < 0) continue;
+        const uint64_t tk = ((uint64_t)(uint32_t)rp[r].transfer_inliers << 32) | (uint32_t)in[r].path;
+        if (rank < 0 || tk > tkey || (tk == tkey && in[r].key > jkey)) { rank = r; tkey = tk; jkey = in[r].key; }
+    }
+    hcTrifocalSelection o;
+    if (rank >= 0) {
+        o = in[rank];
+    } else {
+        o.num_candidates = in[0].num_candidates;
+        o.path = o.inliers = o.inliers21 = o.inliers31 = -1;
+        o.pad = 0;
+        o.key = 0;
+        for (int i = 0; i < 9; i++) o.R21[i] = o.R31[i] = 0.0f;
+        for (int i = 0; i < 3; i++) o.t21[i] = o.t31[i] = 0.0f;
+        o.scale31 = o.pad2 = 0.0f;
+    }
+    best[t] = o;
+    best_rank[t] = rank;
+}
+
+// What a refine call's settings ask of the scale mode (off: the call as it was).
+struct ScaleMode {
+    bool on = false;
+    int bits = 0;
+    hcScaleReport *reports = nullptr;
+    uint64_t *mask = nullptr;
+};
+
+// settings (a host pointer or nullptr) -> the mode; false when the mode is
+// selected and its fields are not valid for this call
+inline bool scale_mode(const hcRefineSettings *s, bool topk, bool mask_allowed, ScaleMode &m) {
+    if (!s || s->pad[0] != HC_REFINE_SCALE31) return true;
+    const hcRefineScaleSettings *ss = reinterpret_cast<const hcRefineScaleSettings *>(s);
+    m.on = true;
+    m.bits = s->pad[1];
+    m.reports = ss->reports;
+    m.mask = ss->transfer_mask;
+    const int allowed = HC_SCALE_ONLY | (topk ? HC_SCALE_SELECT_BY_TRANSFER : 0);
+    if (!m.reports || (m.bits & ~allowed) != 0) return false;
+    if ((m.bits & HC_SCALE_ONLY) != 0 && s->iterations != 0) return false;
+    if (m.mask && !mask_allowed) return false;
+    return true;
+}
+
+// zeroed reports (the vote's atomics' targets), the vote, the epilogue
+template <bool GROUPED>
+hcStatus launch_scale_fit(const ScaleArgs &a, int num_selections, hcStream stream) {
+    hipStream_t s = (hipStream_t)stream;
+    const hcStatus zs = zero_selections(a.rep, (size_t)num_selections, s);
+    if (zs != HC_SUCCESS) return zs;
+    int tiles = GROUPED ? SV_TILES : (a.E + WAVE - 1) / WAVE;
+    if (tiles > 65535) tiles = 65535;   // grid.y's limit: the workgroups stride over the rest
+    hipLaunchKernelGGL(k_scale_vote<GROUPED>, dim3(num_selections, tiles), dim3(SV_THREADS), 0, s, a);
+    if ((g_last_hip_error = hipGetLastError()) != hipSuccess) return HC_ERROR_LAUNCH;
+    hipLaunchKernelGGL(k_scale_final<GROUPED>, dim3(num_selections), dim3(SF_THREADS), 0, s, a);
+    if ((g_last_hip_error = hipGetLastError()) != hipSuccess) return HC_ERROR_LAUNCH;
+    return HC_SUCCESS;
+}
+
+// A refine call (per_group = 1) or a refine-and-select call (best != nullptr)
+// with its scale mode: the refinement unless HC_SCALE_ONLY, the fit of every
+// selection when the mode is on, then the selection among a group's k.
+template <bool GROUPED>
+hcStatus launch_refine_scaled(const RefineArgs &a, const ScaleMode &m, int num_groups, hcTrifocalSelection *best,
+                              int32_t *best_rank, hcStream stream) {
+    const int n = num_groups * a.per_group;
+    const bool only = m.on && (m.bits & HC_SCALE_ONLY) != 0;
+    if (!only) {
+        const hcStatus st = launch_pose_refine<GROUPED>(a, n, stream);
+        if (st != HC_SUCCESS) return st;
+    } else {
+        (void)hipGetLastError();
+    }
+    if (m.on) {
+        const ScaleArgs sa{only ? a.in : a.out, a.out, m.reports, reinterpret_cast<unsigned long long *>(m.mask),
+                           a.E, a.loc, a.K, a.groups, a.per_group};
+        const hcStatus st = launch_scale_fit<GROUPED>(sa, n, stream);
+        if (st != HC_SUCCESS) return st;
+    }
+    if (!best) return HC_SUCCESS;
+    if (m.on && (m.bits & HC_SCALE_SELECT_BY_TRANSFER) != 0)
+        hipLaunchKernelGGL(k_pose_topk_select_transfer, dim3((num_groups + 63) / 64), dim3(64), 0, (hipStream_t)stream,
+                           num_groups, a.per_group, a.out, m.reports, best, best_rank);
+    else
+        hipLaunchKernelGGL(k_pose_topk_select, dim3((num_groups + 63) / 64), dim3(64), 0, (hipStream_t)stream,
+                           num_groups, a.per_group, a.out, best, best_rank);
     if ((g_last_hip_error = hipGetLastError()) != hipSuccess) return HC_ERROR_LAUNCH;
     return HC_SUCCESS;
 }
@@ -843,10 +1129,12 @@ extern "C" hcStatus hc_trifocal_pose_refine(const hcTrifocalSelection *in, int n
                                             hcTrifocalSelection *out, hcRefineReport *report, hcStream stream) {
     using namespace hc;
     int iterations, min_inliers;
-    if (!in || num_edgels <= 0 || !locations || !K || !out || !refine_settings(settings, iterations, min_inliers))
+    ScaleMode m;
+    if (!in || num_edgels <= 0 || !locations || !K || !out || !refine_settings(settings, iterations, min_inliers) ||
+        !scale_mode(settings, false, true, m))
         return HC_ERROR_INVALID_VALUE;
     const RefineArgs a{in, out, report, num_edgels, locations, K, nullptr, iterations, min_inliers, 1};
-    return launch_pose_refine<false>(a, 1, stream);
+    return launch_refine_scaled<false>(a, m, 1, nullptr, nullptr, stream);
 }
 
 extern "C" hcStatus hc_trifocal_pose_refine_grouped(int num_groups, const hcTripletGroup *groups,
@@ -855,10 +1143,12 @@ extern "C" hcStatus hc_trifocal_pose_refine_grouped(int num_groups, const hcTrip
                                                     hcStream stream) {
     using namespace hc;
     int iterations, min_inliers;
-    if (num_groups <= 0 || !groups || !in || !out || !refine_settings(settings, iterations, min_inliers))
+    ScaleMode m;
+    if (num_groups <= 0 || !groups || !in || !out || !refine_settings(settings, iterations, min_inliers) ||
+        !scale_mode(settings, false, false, m))
         return HC_ERROR_INVALID_VALUE;
     const RefineArgs a{in, out, reports, 0, nullptr, nullptr, groups, iterations, min_inliers, 1};
-    return launch_pose_refine<true>(a, num_groups, stream);
+    return launch_refine_scaled<true>(a, m, num_groups, nullptr, nullptr, stream);
 }
 
 extern "C" hcStatus hc_trifocal_pose_topk_joint(int num_paths, const hcComplex *tracks, const int32_t *inliers, int k,
@@ -890,11 +1180,12 @@ extern "C" hcStatus hc_trifocal_pose_refine_topk(int k, const hcTrifocalSelectio
                                                  int32_t *best_rank, hcStream stream) {
     using namespace hc;
     int iterations, min_inliers;
+    ScaleMode m;
     if (k < 1 || k > HC_TOPK_MAX || !candidates || num_edgels <= 0 || !locations || !K || !refined || !best ||
-        !best_rank || !refine_settings(settings, iterations, min_inliers))
+        !best_rank || !refine_settings(settings, iterations, min_inliers) || !scale_mode(settings, true, false, m))
         return HC_ERROR_INVALID_VALUE;
     const RefineArgs a{candidates, refined, reports, num_edgels, locations, K, nullptr, iterations, min_inliers, k};
-    return launch_refine_topk<false>(a, 1, best, best_rank, stream);
+    return launch_refine_scaled<false>(a, m, 1, best, best_rank, stream);
 }
 
 extern "C" hcStatus hc_trifocal_pose_refine_topk_grouped(int num_groups, const hcTripletGroup *groups, int k,
@@ -905,9 +1196,11 @@ extern "C" hcStatus hc_trifocal_pose_refine_topk_grouped(int num_groups, const h
                                                          hcStream stream) {
     using namespace hc;
     int iterations, min_inliers;
+    ScaleMode m;
     if (num_groups < 1 || num_groups > 0x7FFFFFFF / HC_TOPK_MAX || !groups || k < 1 || k > HC_TOPK_MAX ||
-        !candidates || !refined || !best || !best_rank || !refine_settings(settings, iterations, min_inliers))
+        !candidates || !refined || !best || !best_rank || !refine_settings(settings, iterations, min_inliers) ||
+        !scale_mode(settings, true, false, m))
         return HC_ERROR_INVALID_VALUE;
     const RefineArgs a{candidates, refined, reports, 0, nullptr, nullptr, groups, iterations, min_inliers, k};
-    return launch_refine_topk<true>(a, num_groups, best, best_rank, stream);
+    return launch_refine_scaled<true>(a, m, num_groups, best, best_rank, stream);
 }

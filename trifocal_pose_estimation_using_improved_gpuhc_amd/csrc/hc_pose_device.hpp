@@ -110,6 +110,69 @@ __device__ __forceinline__ bool edgel_view(const Scene &sc, int e, const float *
     return reproj_inlier(g01.x, g01.y, h.x, h.y, R, t, sc.K0, sc.K2, sc.K4, sc.K5);
 }
 
+// ---- three-view transfer (include/scale/hc_pose_scale.h: the operation order
+// is the header's, steps 2 and 3) -----------------------------------------------
+
+// The depth of gamma1 from views 1-2, the value reproj_inlier forms before it
+// reprojects (the same operations on the same floats).
+__device__ __forceinline__ float depth_rho(float g0, float g1, float h0, float h1, const float *R, const float *T) {
+    const float a = ((0.0f + R[2] * h0) + R[5] * h1) + R[8] * 1.0f;
+    float rho = T[2] * a;
+    const float RtT_2 = ((0.0f + R[2] * T[0]) + R[5] * T[1]) + R[8] * T[2];
+    rho -= RtT_2;
+    const float m2 = ((0.0f + R[6] * g0) + R[7] * g1) + R[8] * 1.0f;
+    rho /= (1.0f - m2 * a);
+    return rho;
+}
+
+// What the transfer test needs of one edgel: Y = R31 X of the triangulated
+// point and the view-3 observation in pixels; tested = joint inlier with rho > 0.
+struct TransferEdgel {
+    float Y0, Y1, Y2;
+    float p0, p1;      // q0 K0 + K2, q1 K4 + K5
+    bool joint, tested;
+};
+
+// Step 2 for edgel e; s is the edgel's candidate scale (meaningful when tested).
+__device__ __forceinline__ TransferEdgel transfer_edgel(const Scene &sc, int e, const float *R21, const float *t21,
+                                                        const float *R31, const float *t31, float &s) {
+    TransferEdgel r;
+    bool in21, in31;
+    edgel_views(sc, e, R21, t21, R31, t31, in21, in31);
+    const float2 g = *reinterpret_cast<const float2 *>(sc.loc + (size_t)e * 6);
+    const float2 h = *reinterpret_cast<const float2 *>(sc.loc + (size_t)e * 6 + 2);
+    const float2 q = *reinterpret_cast<const float2 *>(sc.loc + (size_t)e * 6 + 4);
+    const float rho = depth_rho(g.x, g.y, h.x, h.y, R21, t21);
+    const float X0 = rho * g.x, X1 = rho * g.y, X2 = rho;
+    r.Y0 = ((0.0f + R31[0] * X0) + R31[1] * X1) + R31[2] * X2;
+    r.Y1 = ((0.0f + R31[3] * X0) + R31[4] * X1) + R31[5] * X2;
+    r.Y2 = ((0.0f + R31[6] * X0) + R31[7] * X1) + R31[8] * X2;
+    const float a0 = q.y * r.Y2 - 1.0f * r.Y1, a1 = 1.0f * r.Y0 - q.x * r.Y2, a2 = q.x * r.Y1 - q.y * r.Y0;
+    const float b0 = q.y * t31[2] - 1.0f * t31[1], b1 = 1.0f * t31[0] - q.x * t31[2], b2 = q.x * t31[1] - q.y * t31[0];
+    s = -(((a0 * b0 + a1 * b1) + a2 * b2) / ((b0 * b0 + b1 * b1) + b2 * b2));
+    r.p0 = q.x * sc.K0 + sc.K2;
+    r.p1 = q.y * sc.K4 + sc.K5;
+    r.joint = in21 && in31;
+    r.tested = r.joint && rho > 0.0f;
+    return r;
+}
+
+__device__ __forceinline__ bool is_voter(bool tested, float s) { return tested && __builtin_isfinite(s) && s > 0.0f; }
+
+// Step 3, T(e, s) for a tested edgel: within 2 px of the view-3 observation,
+// the error formed as reproj_inlier forms it.
+__device__ __forceinline__ bool transfer_inlier(float Y0, float Y1, float Y2, float p0, float p1, float s,
+                                                const float *t31, float K0, float K2, float K4, float K5) {
+    const float Z0 = Y0 + s * t31[0], Z1 = Y1 + s * t31[1], Z2 = Y2 + s * t31[2];
+    float m0 = Z0 / Z2, m1 = Z1 / Z2;
+    m0 = m0 * K0 + K2;
+    m1 = m1 * K4 + K5;
+    m0 -= p0;
+    m1 -= p1;
+    const float err = __builtin_sqrtf((m0 * m0 + m1 * m1) + 0.0f * 0.0f);
+    return Z2 > 0.0f && err < 2.0f;
+}
+
 // x[0..30] of a converged path: Evaluations.cpp:322-331, |Im x[24..29]| <
 // IMAG_PART_TOL and Re x[0..7] >= 0 (wave-uniform result)
 __device__ __forceinline__ bool is_candidate(const cf *__restrict__ x, int lane) {

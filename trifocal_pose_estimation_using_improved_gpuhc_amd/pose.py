@@ -23,6 +23,12 @@ one launch and select the refined one with the most joint inliers (topk_joint,
 refine_topk, their grouped forms, merge_topk, and select_refined, which chains
 joint support, top-k and refine-and-select on one stream).
 
+Relative scale (not in the reference): a mode of the four refine calls
+(include/scale/hc_pose_scale.h) fits scale31, the length of t31 in units of
+t21, by three-view transfer support after the refinement (fit_scale,
+transfer_mask and select_by_transfer on the refine wrappers; fit_scale31 is the
+scale-only form).
+
 The four pose-support calls (per view / joint, one triplet / grouped) share one
 launcher and one synchronous wrapper (_launch, _run), parameterised by a _Rule.
 Every native call goes through the signature table of _abi: buffers and streams
@@ -284,17 +290,81 @@ def _refine_settings(iterations, min_inliers, what: str) -> _abi.hcRefineSetting
     return s
 
 
+# ---- the scale fit, a mode of the refine calls (include/scale/hc_pose_scale.h) ----
+SCALE_REPORT_BYTES = _abi.SCALE_REPORT_BYTES
+
+
+def scale_report_dict(raw) -> dict:
+    r = _struct_from_raw(_abi.hcScaleReport, SCALE_REPORT_BYTES, raw)
+    return dict(status=r.status, none=bool(r.status & _abi.HC_SCALE_NONE),
+                no_voter=bool(r.status & _abi.HC_SCALE_NO_VOTER), num_voters=r.num_voters, voter=r.voter,
+                transfer_inliers=r.transfer_inliers, tested=r.tested, joint=r.joint,
+                scale_in=np.float32(r.scale_in), scale31=np.float32(r.scale31), key=r.key)
+
+
+def _scale_report_dicts(raw: torch.Tensor, count: int) -> list:
+    rows = raw.cpu().numpy().reshape(count, SCALE_REPORT_BYTES)
+    return [scale_report_dict(r) for r in rows]
+
+
+def _mask_words(words: torch.Tensor) -> np.ndarray:
+    return words.cpu().numpy().view(np.uint64)
+
+
+def _check_scale_flags(what: str, fit_scale, transfer_mask=False, select_by_transfer=False, mask_allowed=True):
+    """The scale keywords of a refine wrapper, checked before anything touches a device."""
+    for v in (fit_scale, transfer_mask, select_by_transfer):
+        if not isinstance(v, (bool, np.bool_)):
+            raise _abi.HCError(f"{what}: fit_scale, transfer_mask and select_by_transfer must be booleans")
+    if not fit_scale and (transfer_mask or select_by_transfer):
+        raise _abi.HCError(f"{what}: transfer_mask and select_by_transfer need fit_scale")
+    if transfer_mask and not mask_allowed:
+        raise _abi.HCError(f"{what}: the transfer mask is written for one scene only, not by the grouped call")
+
+
+def _settings_ptr(settings):
+    """The hcRefineSettings pointer of settings, or of an hcRefineScaleSettings' head."""
+    return C.cast(C.pointer(settings), C.POINTER(_abi.hcRefineSettings))
+
+
+def _scale_mode(settings, count: int, dev, what: str, fit_scale, transfer_mask=False, num_edgels=None,
+                select_by_transfer=False, scale_only=False):
+    """The settings a refine call is given: `settings` itself with the mode off,
+    otherwise an hcRefineScaleSettings with `settings` as its head, count scale
+    reports and, with transfer_mask, the mask's words (new device tensors).
+    Returns (settings, scale reports or None, mask words or None)."""
+    _check_scale_flags(what, fit_scale, transfer_mask, select_by_transfer, num_edgels is not None)
+    if not fit_scale:
+        return settings, None, None
+    ss = _abi.hcRefineScaleSettings()
+    ss.head.iterations, ss.head.min_inliers = (0 if scale_only else settings.iterations), settings.min_inliers
+    ss.head.pad[0] = _abi.HC_REFINE_SCALE31
+    ss.head.pad[1] = (_abi.HC_SCALE_ONLY if scale_only else 0) | \
+        (_abi.HC_SCALE_SELECT_BY_TRANSFER if select_by_transfer else 0)
+    reports = torch.empty(count * SCALE_REPORT_BYTES, dtype=torch.uint8, device=dev)
+    words = torch.empty((num_edgels + 63) // 64, dtype=torch.int64, device=dev) if transfer_mask else None
+    ss.reports = reports.data_ptr()
+    ss.transfer_mask = words.data_ptr() if words is not None else None
+    return ss, reports, words
+
+
 def launch_refine_joint(selection, edgels: torch.Tensor, K: torch.Tensor, iterations: int = 10,
-                        min_inliers: int = 16, stream=None, out: torch.Tensor | None = None):
+                        min_inliers: int = 16, stream=None, out: torch.Tensor | None = None,
+                        fit_scale: bool = False, transfer_mask: bool = False, _scale_only: bool = False):
     """Enqueue hc_trifocal_pose_refine (no sync): the joint selection's pose
     fitted to its joint inliers among the E edgels, the inlier set recomputed at
     every iterate.  selection: the device bytes of an hcTrifocalSelection, or a
     dict / struct (e.g. a merge_joint result), which is uploaded.  out: the
     device bytes to write (may be selection itself); default a new tensor.
     Returns (refined selection (JOINT_SEL_BYTES,) u8, report (REPORT_BYTES,) u8),
-    both on the device."""
+    both on the device.
+    fit_scale: the refined pose's scale31 is fitted by three-view transfer
+    support in the same call (include/scale/hc_pose_scale.h); two more device
+    tensors are returned, the scale report (SCALE_REPORT_BYTES,) u8 and, with
+    transfer_mask, the transfer mask's (E + 63) // 64 int64 words (else None)."""
     what = "refine_joint"
     settings = _refine_settings(iterations, min_inliers, what)
+    _check_scale_flags(what, fit_scale, transfer_mask)
     dev = edgels.device
     selection = _device_selections(selection, dev, 1, what)
     for t in (edgels, K):
@@ -303,30 +373,66 @@ def launch_refine_joint(selection, edgels: torch.Tensor, K: torch.Tensor, iterat
     if out is None:
         out = torch.empty(JOINT_SEL_BYTES, dtype=torch.uint8, device=dev)
     out = _device_selections(out, dev, 1, what)
-    report = torch.empty(REPORT_BYTES, dtype=torch.uint8, device=dev)
+    settings, scale, words = _scale_mode(settings, 1, dev, what, fit_scale, transfer_mask, int(edgels.shape[0]),
+                                         scale_only=_scale_only)
+    report = None if _scale_only else torch.empty(REPORT_BYTES, dtype=torch.uint8, device=dev)
     _abi.call("hc_trifocal_pose_refine", _abi.ptr(selection), int(edgels.shape[0]), _abi.ptr(edgels), _abi.ptr(K),
-              C.byref(settings), _abi.ptr(out), _abi.ptr(report),
+              _settings_ptr(settings), _abi.ptr(out), _abi.ptr(report),
               _abi.ptr(stream if stream is not None else torch.cuda.current_stream(dev)))
-    return out, report
+    return (out, report, scale, words) if fit_scale else (out, report)
+
+
+def _scale_entry(scale: torch.Tensor, words) -> dict:
+    d = scale_report_dict(scale)
+    if words is not None:
+        d["mask"] = _mask_words(words)
+    return d
 
 
 def refine_joint(selection, edgels: torch.Tensor, K: torch.Tensor, iterations: int = 10, min_inliers: int = 16,
-                 return_device_selection: bool = False):
+                 return_device_selection: bool = False, fit_scale: bool = False, transfer_mask: bool = False):
     """Synchronous wrapper: (refined selection dict, report dict), and with
-    return_device_selection also the refined selection's device bytes."""
-    out, report = launch_refine_joint(selection, edgels, K, iterations, min_inliers)
+    return_device_selection also the refined selection's device bytes.  With
+    fit_scale the report dict has a "scale" entry, the scale report as a dict
+    (with transfer_mask also its "mask", the packed uint64 words)."""
+    out, report, *rest = launch_refine_joint(selection, edgels, K, iterations, min_inliers, fit_scale=fit_scale,
+                                             transfer_mask=transfer_mask)
     torch.cuda.synchronize(edgels.device)
-    res = (joint_selection_dict(joint_selection_struct(out)), refine_report_dict(report))
+    rep = refine_report_dict(report)
+    if fit_scale:
+        rep["scale"] = _scale_entry(*rest)
+    res = (joint_selection_dict(joint_selection_struct(out)), rep)
     return (*res, out) if return_device_selection else res
 
 
-def launch_refine_joint_grouped(selections, batch, iterations: int = 10, min_inliers: int = 16, stream=None):
+def launch_fit_scale31(selection, edgels: torch.Tensor, K: torch.Tensor, transfer_mask: bool = False, stream=None,
+                       out: torch.Tensor | None = None):
+    """Enqueue the scale fit alone (hc_trifocal_pose_refine with HC_SCALE_ONLY,
+    no sync): no Gauss-Newton step, the selection comes back with only scale31
+    replaced.  Returns device tensors (selection, scale report, mask words or None)."""
+    o, _, scale, words = launch_refine_joint(selection, edgels, K, stream=stream, out=out, fit_scale=True,
+                                             transfer_mask=transfer_mask, _scale_only=True)
+    return o, scale, words
+
+
+def fit_scale31(selection, edgels: torch.Tensor, K: torch.Tensor, transfer_mask: bool = False):
+    """The scale-only form, synchronous: (selection dict, scale report dict)."""
+    out, scale, words = launch_fit_scale31(selection, edgels, K, transfer_mask)
+    torch.cuda.synchronize(edgels.device)
+    return joint_selection_dict(joint_selection_struct(out)), _scale_entry(scale, words)
+
+
+def launch_refine_joint_grouped(selections, batch, iterations: int = 10, min_inliers: int = 16, stream=None,
+                                fit_scale: bool = False, transfer_mask: bool = False):
     """Enqueue hc_trifocal_pose_refine_grouped (no sync): selection t refined on
     triplet t of batch (a multi.DeviceTripletBatch).  selections: T selections
     as device bytes, or a list of dicts / structs, which is uploaded.  Returns
-    (selections (T * JOINT_SEL_BYTES,) u8, reports (T * REPORT_BYTES,) u8)."""
+    (selections (T * JOINT_SEL_BYTES,) u8, reports (T * REPORT_BYTES,) u8), and
+    with fit_scale also the scale reports (T * SCALE_REPORT_BYTES,) u8.  The
+    grouped call writes no transfer mask: transfer_mask is refused."""
     what = "refine_joint_grouped"
     settings = _refine_settings(iterations, min_inliers, what)
+    _check_scale_flags(what, fit_scale, transfer_mask, mask_allowed=False)
     dev = batch.device
     T = batch.num_groups
     if not isinstance(selections, torch.Tensor) and len(selections) != T:
@@ -335,26 +441,33 @@ def launch_refine_joint_grouped(selections, batch, iterations: int = 10, min_inl
     batch.check()   # edgel counts: the kernel does not validate them
     out = torch.empty(T * JOINT_SEL_BYTES, dtype=torch.uint8, device=dev)
     reports = torch.empty(T * REPORT_BYTES, dtype=torch.uint8, device=dev)
-    _abi.call("hc_trifocal_pose_refine_grouped", T, _abi.ptr(batch.groups), _abi.ptr(selections), C.byref(settings),
-              _abi.ptr(out), _abi.ptr(reports),
+    settings, scale, _ = _scale_mode(settings, T, dev, what, fit_scale, transfer_mask)
+    _abi.call("hc_trifocal_pose_refine_grouped", T, _abi.ptr(batch.groups), _abi.ptr(selections),
+              _settings_ptr(settings), _abi.ptr(out), _abi.ptr(reports),
               _abi.ptr(stream if stream is not None else torch.cuda.current_stream(dev)))
-    return out, reports
+    return (out, reports, scale) if fit_scale else (out, reports)
 
 
-def refine_joint_grouped(selections, batch, iterations: int = 10, min_inliers: int = 16, device=None):
+def refine_joint_grouped(selections, batch, iterations: int = 10, min_inliers: int = 16, device=None,
+                         fit_scale: bool = False, transfer_mask: bool = False):
     """Synchronous wrapper: ([refined selection dict] * T, [report dict] * T).
     batch: a multi.TripletBatch (copied to device, or to the selections' device)
-    or a multi.DeviceTripletBatch."""
+    or a multi.DeviceTripletBatch.  With fit_scale every report dict has a
+    "scale" entry."""
     if not hasattr(batch, "groups"):
         if device is None:
             device = selections.device if isinstance(selections, torch.Tensor) else "cuda:0"
         batch = batch.to(device)
-    out, reports = launch_refine_joint_grouped(selections, batch, iterations, min_inliers)
+    out, reports, *rest = launch_refine_joint_grouped(selections, batch, iterations, min_inliers, fit_scale=fit_scale,
+                                                      transfer_mask=transfer_mask)
     torch.cuda.synchronize(batch.device)
     T = batch.num_groups
     sels = out.cpu().numpy().reshape(T, JOINT_SEL_BYTES)
-    reps = reports.cpu().numpy().reshape(T, REPORT_BYTES)
-    return ([joint_selection_dict(joint_selection_struct(r)) for r in sels], [refine_report_dict(r) for r in reps])
+    reps = [refine_report_dict(r) for r in reports.cpu().numpy().reshape(T, REPORT_BYTES)]
+    if fit_scale:
+        for r, s in zip(reps, _scale_report_dicts(rest[0], T)):
+            r["scale"] = s
+    return [joint_selection_dict(joint_selection_struct(r)) for r in sels], reps
 
 
 def merge_joint(parts: list, path_offsets: list) -> dict:
@@ -452,11 +565,16 @@ def topk_joint_grouped(tracks: torch.Tensor, inliers: torch.Tensor, batch, k: in
     return [d[t * k:(t + 1) * k] for t in range(batch.num_groups)]
 
 
-def _launch_refine_topk(what, candidates, k, scene, iterations, min_inliers, stream, refined):
-    """scene: (edgels, K) or a multi.DeviceTripletBatch."""
+def _launch_refine_topk(what, candidates, k, scene, iterations, min_inliers, stream, refined, fit_scale=False,
+                        transfer_mask=False, select_by_transfer=False):
+    """scene: (edgels, K) or a multi.DeviceTripletBatch.  With fit_scale the
+    returned tuple has a fifth tensor, the T * k scale reports, and, when
+    transfer_mask is set, a sixth: the transfer mask of best (the single-scene
+    call only), written by a scale-only fit of best on the same stream."""
     k = _check_k(k, what)
     settings = _refine_settings(iterations, min_inliers, what)
     grouped = not isinstance(scene, tuple)
+    _check_scale_flags(what, fit_scale, transfer_mask, select_by_transfer, not grouped)
     dev = scene.device if grouped else scene[0].device
     T = scene.num_groups if grouped else 1
     if not isinstance(candidates, torch.Tensor) and len(candidates) != T * k:
@@ -468,19 +586,26 @@ def _launch_refine_topk(what, candidates, k, scene, iterations, min_inliers, str
     reports = torch.empty(T * k * REPORT_BYTES, dtype=torch.uint8, device=dev)
     best = torch.empty(T * JOINT_SEL_BYTES, dtype=torch.uint8, device=dev)
     best_rank = torch.empty(T, dtype=torch.int32, device=dev)
+    settings, scale, _ = _scale_mode(settings, T * k, dev, what, fit_scale, select_by_transfer=select_by_transfer)
     s = _abi.ptr(stream if stream is not None else torch.cuda.current_stream(dev))
     out = (_abi.ptr(refined), _abi.ptr(reports), _abi.ptr(best), _abi.ptr(best_rank), s)
     if grouped:
         scene.check()   # edgel counts: the kernel does not validate them
         _abi.call("hc_trifocal_pose_refine_topk_grouped", T, _abi.ptr(scene.groups), k, _abi.ptr(candidates),
-                  C.byref(settings), *out)
+                  _settings_ptr(settings), *out)
     else:
         for t in scene:
             if not t.is_cuda or not t.is_contiguous() or t.device != dev:
                 raise _abi.HCError(f"{what}: buffers must be contiguous tensors on one device")
         _abi.call("hc_trifocal_pose_refine_topk", k, _abi.ptr(candidates), int(scene[0].shape[0]), _abi.ptr(scene[0]),
-                  _abi.ptr(scene[1]), C.byref(settings), *out)
-    return best, best_rank, refined, reports
+                  _abi.ptr(scene[1]), _settings_ptr(settings), *out)
+    if not fit_scale:
+        return best, best_rank, refined, reports
+    if not transfer_mask:
+        return best, best_rank, refined, reports, scale
+    # the same pose gives the same vote: best keeps its bytes, and the mask is its own
+    _, _, words = launch_fit_scale31(best, scene[0], scene[1], transfer_mask=True, stream=stream, out=best)
+    return best, best_rank, refined, reports, scale, words
 
 
 def _topk_count(candidates, what: str) -> int:
@@ -493,7 +618,8 @@ def _topk_count(candidates, what: str) -> int:
 
 
 def launch_refine_topk(candidates, edgels: torch.Tensor, K: torch.Tensor, iterations: int = 10, min_inliers: int = 16,
-                       stream=None, refined: torch.Tensor | None = None):
+                       stream=None, refined: torch.Tensor | None = None, fit_scale: bool = False,
+                       transfer_mask: bool = False, select_by_transfer: bool = False):
     """Enqueue hc_trifocal_pose_refine_topk (no sync): every candidate refined
     on the E edgels as launch_refine_joint refines it, in one launch, and the
     refined selection with the most joint inliers (ties -> the larger batch id)
@@ -501,53 +627,75 @@ def launch_refine_topk(candidates, edgels: torch.Tensor, K: torch.Tensor, iterat
     of launch_topk_joint: k is their number), or a list of k dicts / structs,
     which is uploaded.  refined: the device bytes to write (may be candidates).
     Returns device tensors (best (JOINT_SEL_BYTES,) u8, best_rank (1,) i32,
-    refined (k * JOINT_SEL_BYTES,) u8, reports (k * REPORT_BYTES,) u8)."""
+    refined (k * JOINT_SEL_BYTES,) u8, reports (k * REPORT_BYTES,) u8).
+    fit_scale: the scale31 of all k refined selections is fitted by three-view
+    transfer support (include/scale/hc_pose_scale.h) and a fifth tensor, the k
+    scale reports (k * SCALE_REPORT_BYTES,) u8, is returned; best is chosen as
+    without it, or with select_by_transfer by the largest transfer_inliers << 32
+    | path.  transfer_mask: a sixth tensor, the transfer mask's words of best."""
     what = "refine_topk"
     _refine_settings(iterations, min_inliers, what)
     return _launch_refine_topk(what, candidates, _topk_count(candidates, what), (edgels, K), iterations, min_inliers,
-                               stream, refined)
+                               stream, refined, fit_scale, transfer_mask, select_by_transfer)
 
 
-def _refine_topk_dicts(best, best_rank, refined, reports, T, k):
+def _refine_topk_dicts(best, best_rank, refined, reports, T, k, scale=None, words=None):
     sels = _selection_dicts(refined, T * k)
-    reps = reports.cpu().numpy().reshape(T * k, REPORT_BYTES)
+    reps = [refine_report_dict(r) for r in reports.cpu().numpy().reshape(T * k, REPORT_BYTES)]
+    if scale is not None:
+        for r, sc in zip(reps, _scale_report_dicts(scale, T * k)):
+            r["scale"] = sc
     ranks = best_rank.cpu().numpy()
-    return [dict(best=b, best_rank=int(ranks[t]), refined=sels[t * k:(t + 1) * k],
-                 reports=[refine_report_dict(r) for r in reps[t * k:(t + 1) * k]])
-            for t, b in enumerate(_selection_dicts(best, T))]
+    out = [dict(best=b, best_rank=int(ranks[t]), refined=sels[t * k:(t + 1) * k], reports=reps[t * k:(t + 1) * k])
+           for t, b in enumerate(_selection_dicts(best, T))]
+    if words is not None:
+        out[0]["transfer_mask"] = _mask_words(words)
+    return out
 
 
-def refine_topk(candidates, edgels: torch.Tensor, K: torch.Tensor, iterations: int = 10, min_inliers: int = 16):
-    """Synchronous wrapper: (best dict, best_rank, [refined dict] * k, [report dict] * k)."""
-    out = launch_refine_topk(candidates, edgels, K, iterations, min_inliers)
+def refine_topk(candidates, edgels: torch.Tensor, K: torch.Tensor, iterations: int = 10, min_inliers: int = 16,
+                fit_scale: bool = False, transfer_mask: bool = False, select_by_transfer: bool = False):
+    """Synchronous wrapper: (best dict, best_rank, [refined dict] * k, [report dict] * k).
+    With fit_scale every report dict has a "scale" entry; with transfer_mask
+    best's entry (reports[best_rank]["scale"]) also has "mask", the packed words."""
+    out = launch_refine_topk(candidates, edgels, K, iterations, min_inliers, fit_scale=fit_scale,
+                             transfer_mask=transfer_mask, select_by_transfer=select_by_transfer)
     torch.cuda.synchronize(edgels.device)
-    d = _refine_topk_dicts(*out, 1, _topk_count(candidates, "refine_topk"))[0]
+    d = _refine_topk_dicts(*out[:4], 1, _topk_count(candidates, "refine_topk"), *out[4:])[0]
+    if "transfer_mask" in d and d["best_rank"] >= 0:
+        d["reports"][d["best_rank"]]["scale"]["mask"] = d["transfer_mask"]
     return d["best"], d["best_rank"], d["refined"], d["reports"]
 
 
 def launch_refine_topk_grouped(candidates, batch, k: int, iterations: int = 10, min_inliers: int = 16, stream=None,
-                               refined: torch.Tensor | None = None):
+                               refined: torch.Tensor | None = None, fit_scale: bool = False,
+                               transfer_mask: bool = False, select_by_transfer: bool = False):
     """Enqueue hc_trifocal_pose_refine_topk_grouped (no sync): candidates
     [t * k + r] refined on triplet t of batch (a multi.DeviceTripletBatch), one
     selection per triplet.  Returns (best (T * JOINT_SEL_BYTES,) u8, best_rank
-    (T,) i32, refined, reports)."""
+    (T,) i32, refined, reports), and with fit_scale also the T * k scale reports
+    (select_by_transfer as in launch_refine_topk; transfer_mask is refused)."""
     _check_k(k, "refine_topk_grouped")
-    return _launch_refine_topk("refine_topk_grouped", candidates, k, batch, iterations, min_inliers, stream, refined)
+    return _launch_refine_topk("refine_topk_grouped", candidates, k, batch, iterations, min_inliers, stream, refined,
+                               fit_scale, transfer_mask, select_by_transfer)
 
 
-def refine_topk_grouped(candidates, batch, k: int, iterations: int = 10, min_inliers: int = 16, device=None):
+def refine_topk_grouped(candidates, batch, k: int, iterations: int = 10, min_inliers: int = 16, device=None,
+                        fit_scale: bool = False, transfer_mask: bool = False, select_by_transfer: bool = False):
     """Synchronous wrapper: per triplet a dict(best, best_rank, refined, reports)
     of dicts.  batch: a multi.TripletBatch (copied to device, or to the
-    candidates' device) or a multi.DeviceTripletBatch."""
+    candidates' device) or a multi.DeviceTripletBatch.  With fit_scale every
+    report dict has a "scale" entry."""
     _check_k(k, "refine_topk_grouped")
     _refine_settings(iterations, min_inliers, "refine_topk_grouped")
     if not hasattr(batch, "groups"):
         if device is None:
             device = candidates.device if isinstance(candidates, torch.Tensor) else "cuda:0"
         batch = batch.to(device)
-    out = launch_refine_topk_grouped(candidates, batch, k, iterations, min_inliers)
+    out = launch_refine_topk_grouped(candidates, batch, k, iterations, min_inliers, fit_scale=fit_scale,
+                                     transfer_mask=transfer_mask, select_by_transfer=select_by_transfer)
     torch.cuda.synchronize(batch.device)
-    return _refine_topk_dicts(*out, batch.num_groups, k)
+    return _refine_topk_dicts(*out[:4], batch.num_groups, k, *out[4:])
 
 
 def merge_topk(parts: list, path_offsets: list, k: int) -> list:
@@ -575,15 +723,20 @@ def merge_topk(parts: list, path_offsets: list, k: int) -> list:
 
 
 def select_refined(tracks: torch.Tensor, converge: torch.Tensor, edgels: torch.Tensor, K: torch.Tensor, k: int = 8,
-                   iterations: int = 10, min_inliers: int = 16, stream=None):
+                   iterations: int = 10, min_inliers: int = 16, stream=None, fit_scale: bool = False,
+                   transfer_mask: bool = False, select_by_transfer: bool = False):
     """Joint pose support, the k best candidates, their refinement and the
     selection among the refined ones, enqueued on one stream with a single
     synchronisation at the end.  Returns (best dict, info); info: joint (the
     joint call's winner, = candidate 0), best_rank, candidates and refined
-    ([dict] * k), refined_inliers ([int] * k, -1 for a "none" rank) and reports."""
+    ([dict] * k), refined_inliers ([int] * k, -1 for a "none" rank) and reports.
+    With fit_scale every report has a "scale" entry and info has scale, best's
+    own (None without a best; with transfer_mask it holds "mask");
+    select_by_transfer as in launch_refine_topk."""
     what = "select_refined"
     k = _check_k(k, what)
     _refine_settings(iterations, min_inliers, what)
+    _check_scale_flags(what, fit_scale, transfer_mask, select_by_transfer)
     dev = tracks.device
     n = converge.numel()
     inl = torch.empty((n, 3), dtype=torch.int32, device=dev)
@@ -591,12 +744,19 @@ def select_refined(tracks: torch.Tensor, converge: torch.Tensor, edgels: torch.T
     stream = stream if stream is not None else torch.cuda.current_stream(dev)
     launch_pose_support_joint(tracks, converge, edgels, K, inl, sel, stream)
     cand = launch_topk_joint(tracks, inl, k, stream=stream)
-    out = launch_refine_topk(cand, edgels, K, iterations, min_inliers, stream)
+    out = launch_refine_topk(cand, edgels, K, iterations, min_inliers, stream, fit_scale=fit_scale,
+                             transfer_mask=transfer_mask, select_by_transfer=select_by_transfer)
     stream.synchronize()
-    d = _refine_topk_dicts(*out, 1, k)[0]
+    d = _refine_topk_dicts(*out[:4], 1, k, *out[4:])[0]
     info = dict(joint=joint_selection_dict(joint_selection_struct(sel)), best_rank=d["best_rank"],
                 candidates=_selection_dicts(cand, k), refined=d["refined"],
                 refined_inliers=[r["inliers"] for r in d["refined"]], reports=d["reports"])
+    if fit_scale:
+        info["scale"] = None
+        if d["best_rank"] >= 0:
+            info["scale"] = dict(d["reports"][d["best_rank"]]["scale"])
+            if "transfer_mask" in d:
+                info["scale"]["mask"] = d["transfer_mask"]
     return d["best"], info
 
 
