@@ -36,6 +36,11 @@
 #             -> TAG_scale.json
 #   scale_ab  the refine calls with the scale mode off (scripts/scale_fit.py --existing) on builds NAME=lib/libX.so ...
 #             (package-relative), alternately, 3 rounds -> TAG_scale_existing.jsonl
+#   threeview the three-view refinement after the two-view refinement and the scale vote, config-5 protocol: verdicts,
+#             rotation residuals, scale error and transfer inliers without and with the stage, and its cost
+#             (scripts/threeview_fit.py [TRIALS [REPS]]) -> TAG_threeview.json
+#   threeview_ab  the refine calls with the modes off (scripts/threeview_fit.py --existing) on builds NAME=lib/libX.so ...
+#             (package-relative), alternately, 3 rounds -> TAG_threeview_existing.jsonl; config 2 and one sample: the ab step
 #   p2c       the ablation ladder from the archived P2C tracker up: P2C, PH, PH_CodeOpt and the headline launch
 #             alternately on config 2 (scripts/ablation_p2c.py [--reps R]) -> TAG_ablation_p2c.json
 #   validate  tests,luwork,bench,profile,datasets
@@ -142,6 +147,17 @@ for k,v in sorted(g.items()): print(k, v)" ;;
         done
       done
       [ -f $O/${T}_scale_existing.jsonl ] && cat $O/${T}_scale_existing.jsonl ;;
+    threeview) run threeview 900 python scripts/threeview_fit.py "$@" > $O/${T}_threeview.json; rc=$?; tail -c 600 $O/${T}_threeview.json ;;
+    threeview_ab)
+      rc=0
+      for rd in 0 1 2; do
+        for kv in "$@"; do
+          HC_TRIFOCAL_LIB=$P/${kv#*=} run existing_${kv%%=*} 200 python scripts/threeview_fit.py --existing > $O/${T}_tmp.json; rc=$?
+          [ $rc -eq 0 ] || break 2
+          python -c "import json; d=json.load(open('$O/${T}_tmp.json')); d.update(build='${kv%%=*}', round=$rd); print(json.dumps(d))" >> $O/${T}_threeview_existing.jsonl
+        done
+      done
+      [ -f $O/${T}_threeview_existing.jsonl ] && cat $O/${T}_threeview_existing.jsonl ;;
     p2c) run p2c 300 python scripts/ablation_p2c.py --out $O/${T}_ablation_p2c.json "$@"; rc=$? ;;
     gated_ab)
       rc=0

@@ -11,7 +11,7 @@ holds both against the headers (layouts through the C compiler, signatures
 against the prototypes).  The headers in directories of their own
 (include/p2c, include/refine, include/topk, include/adaptive) have tables of their own,
 P2C_SIGNATURES, REFINE_SIGNATURES, TOPK_SIGNATURES and ADAPTIVE_SIGNATURES, checked the same way
-(include/scale declares structs only: the scale fit is a mode of the refine calls).  Callers go through two helpers: ptr(x), the c_void_p
+(include/scale and include/threeview declare structs only: the scale fit and the three-view refinement are modes of the refine calls).  Callers go through two helpers: ptr(x), the c_void_p
 of a tensor, array or stream, and call(name, *args), which raises HCError on a
 status other than HC_SUCCESS.
 """
@@ -188,6 +188,37 @@ class hcRefineScaleSettings(C.Structure):
 
 
 SCALE_REPORT_BYTES = C.sizeof(hcScaleReport)   # 40
+
+# include/threeview/hc_pose_threeview.h: the three-view refinement, a further mode
+# of the refine calls (no function of its own; its structs and the table below
+# are held against the header by tests/test_threeview_host.py)
+HC_REFINE_THREEVIEW = 0x54563331          # hcRefineSettings::pad[0] of an hcRefineThreeViewSettings
+HC_THREEVIEW_SELECT_BY_TRANSFER = 2       # pad[1]: mode bits
+HC_THREEVIEW_NONE, HC_THREEVIEW_TOO_FEW, HC_THREEVIEW_SINGULAR, HC_THREEVIEW_SKIPPED = 1, 2, 4, 8   # status bits
+THREEVIEW_CONSTANTS = {"HC_REFINE_THREEVIEW": HC_REFINE_THREEVIEW,
+                       "HC_THREEVIEW_SELECT_BY_TRANSFER": HC_THREEVIEW_SELECT_BY_TRANSFER,
+                       "HC_THREEVIEW_NONE": HC_THREEVIEW_NONE, "HC_THREEVIEW_TOO_FEW": HC_THREEVIEW_TOO_FEW,
+                       "HC_THREEVIEW_SINGULAR": HC_THREEVIEW_SINGULAR, "HC_THREEVIEW_SKIPPED": HC_THREEVIEW_SKIPPED}
+
+
+class hcThreeViewReport(C.Structure):
+    """include/threeview/hc_pose_threeview.h: what one three-view refinement did, 328 bytes"""
+    _fields_ = [("status", C.c_int32), ("iterations_run", C.c_int32), ("best_iteration", C.c_int32),
+                ("transfer_history", C.c_int32 * (HC_REFINE_MAX_ITERATIONS + 1)),
+                ("joint_history", C.c_int32 * (HC_REFINE_MAX_ITERATIONS + 1)),
+                ("fit_set", C.c_int32), ("transfer_inliers", C.c_int32),
+                ("scale_in", C.c_float), ("scale_out", C.c_float), ("pad", C.c_int32),
+                ("rms_px_in", C.c_double * 2), ("rms_px_out", C.c_double * 2)]
+
+
+class hcRefineThreeViewSettings(C.Structure):
+    """include/threeview/hc_pose_threeview.h: the settings of the three-view mode,
+    48 bytes; its address is passed as the hcRefineSettings'."""
+    _fields_ = [("head", hcRefineSettings), ("scale_reports", C.c_void_p), ("reports", C.c_void_p),
+                ("transfer_mask", C.c_void_p), ("iterations3", C.c_int32), ("pad", C.c_int32)]
+
+
+THREEVIEW_REPORT_BYTES = C.sizeof(hcThreeViewReport)   # 328
 
 
 # One entry per function of include/*.h: restype and argtypes as the prototype

@@ -32,13 +32,16 @@
 // (include/topk/hc_pose_topk.h, described below the refinement) rank the k best
 // joint candidates and select among their refinements.
 // k_scale_vote<GROUPED> and k_scale_final<GROUPED> (include/scale/hc_pose_scale.h,
-// described at the end) fit a refined selection's scale31 by three-view transfer.
+// described below the top-k) fit a refined selection's scale31 by three-view transfer.
+// k_pose_refine3<GROUPED> (include/threeview/hc_pose_threeview.h, described at the
+// end) then refines both views and the scale jointly on the three-view transfer.
 #include <type_traits>
 
 #include "../../include/hc_pose.h"
 #include "../../include/refine/hc_pose_refine.h"
 #include "../../include/topk/hc_pose_topk.h"
 #include "../../include/scale/hc_pose_scale.h"
+#include "../../include/threeview/hc_pose_threeview.h"
 #include "hc_device.hpp"
 #include "hc_pose_device.hpp"   // make_pose, reproj_inlier, edgel_views, is_candidate: shared with the gated tracker
 
@@ -1070,6 +1073,451 @@ hcStatus launch_refine_scaled(const RefineArgs &a, const ScaleMode &m, int num_g
     return HC_SUCCESS;
 }
 
+// ---- the three-view refinement (include/threeview/hc_pose_threeview.h) --------
+//
+// The third stage of a refine call: after k_pose_refine and the scale fit,
+// k_pose_refine3<GROUPED> refines both views and the scale jointly, in place on
+// the selections the fit has written.  One workgroup of 256 threads per
+// selection, the whole Gauss-Newton loop in one launch, laid out as
+// k_pose_refine: an iterate is one pass over the edgels, thread i takes edgels
+// i, i + 256, ...; it counts each with edgel_views, transfer_edgel and
+// transfer_inlier on the state rounded to float (the functions the vote and the
+// masks use) and, for an edgel of the fit set, adds the four residual rows and
+// their derivatives along the eleven local directions, in double at the double
+// state, to its 79 sums (66 of A, 11 of g, the squared error of each row pair).
+// The sums go through a butterfly over the wave's lanes, then through LDS over
+// the four waves as (w0 + w1) + (w2 + w3).  Wave 0 solves the 11 x 11 system, a
+// row per lane (refine3_solve), and lanes 0, 1 and 2 write view 2's, view 3's
+// and the scale's new state to LDS.  Nothing waits on another
+// workgroup.  After the loop the four waves write the transfer mask of the best
+// iterate, one ballot per word.
+constexpr int R3_THREADS = 256, R3_WAVES = R3_THREADS / WAVE;
+constexpr int R3_N = 11, R3_A = R3_N * (R3_N + 1) / 2;
+constexpr int R3_SUMS = R3_A + R3_N + 2;   // A | g | sum r'r of the view-2 rows, of the transfer rows
+
+struct Refine3Args {
+    hcTrifocalSelection *sels;      // stage 2's out, refined in place
+    const hcScaleReport *scale;     // stage 2's reports: a status other than 0 skips the stage
+    hcThreeViewReport *rep;
+    unsigned long long *mask;       // or nullptr; the single call only
+    int E;                          // the scene, or with GROUPED that of groups[blockIdx.x / per_group]
+    const float *loc;
+    const float *K;
+    const hcTripletGroup *groups;
+    int iterations, min_inliers;
+    int per_group;
+};
+
+// One edgel of the fit set: rows 0, 1 are view_accumulate's residual and its
+// derivatives along view 2's five directions; rows 2, 3 the pixel error of
+// Z = R31 (rho gamma1) + s t31 against (q0, q1), along all eleven: view 2's
+// through rho alone (dZ = R31 gamma1 drho), w3 = e_i (dZ = e_i x Y), u3 (dZ =
+// s b), sigma (dZ = s t31).
+__device__ __forceinline__ void threeview_accumulate(double g0, double g1, double h0, double h1, double q0, double q1,
+                                                     const double *R, const double *t, const double *b,
+                                                     const double *R3, const double *t3, const double *b3, double s,
+                                                     double K0, double K2, double K4, double K5, double *acc) {
+    const double c[3] = {R[2], R[5], R[8]};
+    const double a = (c[0] * h0 + c[1] * h1) + c[2];
+    const double ct = (c[0] * t[0] + c[1] * t[1]) + c[2] * t[2];
+    const double m[3] = {(R[0] * g0 + R[1] * g1) + R[2], (R[3] * g0 + R[4] * g1) + R[5], (R[6] * g0 + R[7] * g1) + R[8]};
+    const double den = 1.0 - m[2] * a;
+    const double rho = (t[2] * a - ct) / den;
+    const double q[3] = {m[0] * rho + t[0], m[1] * rho + t[1], m[2] * rho + t[2]};
+    const double x = q[0] / q[2], y = q[1] / q[2];
+    const double r0 = (x * K0 + K2) - (h0 * K0 + K2), r1 = (y * K4 + K5) - (h1 * K4 + K5);
+    const double iden = 1.0 / den, iq2 = 1.0 / q[2];
+    const double M3[3] = {(R3[0] * g0 + R3[1] * g1) + R3[2], (R3[3] * g0 + R3[4] * g1) + R3[5],
+                          (R3[6] * g0 + R3[7] * g1) + R3[8]};
+    const double Y[3] = {M3[0] * rho, M3[1] * rho, M3[2] * rho};
+    const double Z[3] = {Y[0] + s * t3[0], Y[1] + s * t3[1], Y[2] + s * t3[2]};
+    const double iz = 1.0 / Z[2];
+    const double xz = Z[0] * iz, yz = Z[1] * iz;
+    const double r2 = ((Z[0] / Z[2]) * K0 + K2) - (q0 * K0 + K2), r3 = ((Z[1] / Z[2]) * K4 + K5) - (q1 * K4 + K5);
+    double J0[5], J1[5], T0[R3_N], T1[R3_N];
+#pragma unroll
+    for (int d = 0; d < 5; d++) {
+        double dc[3] = {0.0, 0.0, 0.0}, dm[3] = {0.0, 0.0, 0.0}, dt[3] = {0.0, 0.0, 0.0};
+        if (d == 0) { dc[1] = -c[2]; dc[2] = c[1]; dm[1] = -m[2]; dm[2] = m[1]; }
+        else if (d == 1) { dc[0] = c[2]; dc[2] = -c[0]; dm[0] = m[2]; dm[2] = -m[0]; }
+        else if (d == 2) { dc[0] = -c[1]; dc[1] = c[0]; dm[0] = -m[1]; dm[1] = m[0]; }
+        else { dt[0] = b[3 * (d - 3)]; dt[1] = b[3 * (d - 3) + 1]; dt[2] = b[3 * (d - 3) + 2]; }
+        const double da = (dc[0] * h0 + dc[1] * h1) + dc[2];
+        const double dct = ((dc[0] * t[0] + dc[1] * t[1]) + dc[2] * t[2]) + ((c[0] * dt[0] + c[1] * dt[1]) + c[2] * dt[2]);
+        const double dnum = (dt[2] * a + t[2] * da) - dct;
+        const double dden = -(dm[2] * a + m[2] * da);
+        const double drho = (dnum - rho * dden) * iden;
+        const double dq0 = (dm[0] * rho + m[0] * drho) + dt[0];
+        const double dq1 = (dm[1] * rho + m[1] * drho) + dt[1];
+        const double dq2 = (dm[2] * rho + m[2] * drho) + dt[2];
+        J0[d] = K0 * ((dq0 - x * dq2) * iq2);
+        J1[d] = K4 * ((dq1 - y * dq2) * iq2);
+        T0[d] = K0 * (((M3[0] - xz * M3[2]) * drho) * iz);
+        T1[d] = K4 * (((M3[1] - yz * M3[2]) * drho) * iz);
+    }
+#pragma unroll
+    for (int d = 5; d < R3_N; d++) {
+        double dZ[3];
+        if (d == 5) { dZ[0] = 0.0; dZ[1] = -Y[2]; dZ[2] = Y[1]; }
+        else if (d == 6) { dZ[0] = Y[2]; dZ[1] = 0.0; dZ[2] = -Y[0]; }
+        else if (d == 7) { dZ[0] = -Y[1]; dZ[1] = Y[0]; dZ[2] = 0.0; }
+        else if (d < 10) { dZ[0] = s * b3[3 * (d - 8)]; dZ[1] = s * b3[3 * (d - 8) + 1]; dZ[2] = s * b3[3 * (d - 8) + 2]; }
+        else { dZ[0] = s * t3[0]; dZ[1] = s * t3[1]; dZ[2] = s * t3[2]; }
+        T0[d] = K0 * ((dZ[0] - xz * dZ[2]) * iz);
+        T1[d] = K4 * ((dZ[1] - yz * dZ[2]) * iz);
+    }
+    int n = 0;
+#pragma unroll
+    for (int i = 0; i < R3_N; i++)
+#pragma unroll
+        for (int j = i; j < R3_N; j++) {
+            double v = T0[i] * T0[j] + T1[i] * T1[j];
+            if (j < 5) v += J0[i] * J0[j] + J1[i] * J1[j];
+            acc[n++] += v;
+        }
+#pragma unroll
+    for (int i = 0; i < R3_N; i++) {
+        double v = T0[i] * r2 + T1[i] * r3;
+        if (i < 5) v += J0[i] * r0 + J1[i] * r1;
+        acc[R3_A + i] += v;
+    }
+    acc[R3_A + R3_N] += r0 * r0 + r1 * r1;
+    acc[R3_A + R3_N + 1] += r2 * r2 + r3 * r3;
+}
+
+// Entry (i, j), i <= j, of the packed upper triangle (row by row).
+__host__ __device__ constexpr int r3_at(int i, int j) { return i * R3_N - i * (i - 1) / 2 + (j - i); }
+
+// refine_solve at size 11, by the 64 lanes of one wave: (A + 1e-9 diag A) d = -g
+// by Cholesky, the operations of refine_solve in its order.  Lane i < 11 owns
+// row i of A and of the factor L (the lanes above repeat row 10, unused); what a
+// step needs of another row comes by a shuffle from a fixed lane: the pivot of
+// column j and L[j][0..j-1] from lane j.  The substitutions run in every lane on
+// broadcast entries, so d comes out the same in all of them.  tot(n) is total n
+// of the workgroup's sums.  False when a pivot is not positive or a value is not
+// finite; the same in every lane.
+template <typename Tot>
+__device__ __forceinline__ bool refine3_solve(Tot tot, int lane, double *d) {
+    const int row = lane < R3_N ? lane : R3_N - 1;
+    double M[R3_N], L[R3_N], g[R3_N], y[R3_N];
+    bool fin = true;
+#pragma unroll
+    for (int j = 0; j < R3_N; j++) {
+        M[j] = tot(row <= j ? row * R3_N - row * (row - 1) / 2 + (j - row) : j * R3_N - j * (j - 1) / 2 + (row - j));
+        if (j == row) M[j] = M[j] + 1e-9 * M[j];
+        g[j] = tot(R3_A + j);
+        fin = fin && __builtin_isfinite(M[j]) && __builtin_isfinite(g[j]);
+        L[j] = 0.0;
+    }
+    bool ok = __ballot(!fin) == 0;
+#pragma unroll
+    for (int j = 0; j < R3_N; j++) {
+        double v = M[j];
+#pragma unroll
+        for (int k = 0; k < j; k++) v -= L[k] * __shfl(L[k], j);   // lane j: M[j][j] - sum L[j][k]^2
+        const double p = __shfl(v, j);
+        ok = ok && p > 0.0;
+        const double ljj = __builtin_sqrt(p);
+        L[j] = row == j ? ljj : v / ljj;   // rows above j hold no entry of this column: never read
+    }
+#pragma unroll
+    for (int i = 0; i < R3_N; i++) {
+        double v = -g[i];
+#pragma unroll
+        for (int k = 0; k < i; k++) v -= __shfl(L[k], i) * y[k];
+        y[i] = v / __shfl(L[i], i);
+    }
+#pragma unroll
+    for (int i = R3_N - 1; i >= 0; i--) {
+        double v = y[i];
+#pragma unroll
+        for (int k = i + 1; k < R3_N; k++) v -= __shfl(L[i], k) * d[k];
+        d[i] = v / __shfl(L[i], i);
+        ok = ok && __builtin_isfinite(d[i]);
+    }
+    return ok;
+}
+
+template <bool GROUPED>
+__global__ void __launch_bounds__(R3_THREADS) k_pose_refine3(const Refine3Args a) {
+    __shared__ double s_sum[R3_WAVES][R3_SUMS];
+    __shared__ double s_state[2][12];   // per view R | t, the double state
+    __shared__ double s_scale;          // s
+    __shared__ float s_best[25];        // the best iterate's scored floats: R21 | t21 | R31 | t31 | s
+    __shared__ int s_cnt[R3_WAVES][5];
+    __shared__ int s_singular;
+    const int tid = threadIdx.x, lane = lane_id(), wave = tid / WAVE, sel = blockIdx.x;
+    Scene sc;
+    if constexpr (GROUPED) {
+        const hcTripletGroup g = a.groups[sel / a.per_group];
+        sc = load_scene(g.num_edgels, g.locations, g.K);
+    } else {
+        sc = load_scene(a.E, a.loc, a.K);
+    }
+    const int words = (sc.E + WAVE - 1) / WAVE;
+    // every thread reads the selection here, before the first barrier; thread 0
+    // writes it after the last one
+    const hcTrifocalSelection keep = a.sels[sel];
+    hcThreeViewReport *rep = a.rep + sel;
+    if (keep.path < 0 || a.scale[sel].status != 0) {   // stage 2 fitted nothing: its output stands
+        if (a.mask)
+            for (int w = tid; w < words; w += R3_THREADS) a.mask[w] = 0ull;
+        if (tid == 0) {
+            rep->status = HC_THREEVIEW_SKIPPED | (keep.path < 0 ? HC_THREEVIEW_NONE : 0);
+            rep->iterations_run = rep->best_iteration = 0;
+            for (int i = 0; i <= HC_REFINE_MAX_ITERATIONS; i++) rep->transfer_history[i] = rep->joint_history[i] = -1;
+            rep->fit_set = rep->transfer_inliers = 0;
+            rep->scale_in = rep->scale_out = keep.scale31;
+            rep->pad = 0;
+            rep->rms_px_in[0] = rep->rms_px_in[1] = rep->rms_px_out[0] = rep->rms_px_out[1] = 0.0;
+        }
+        return;
+    }
+    if (tid == 0) {
+#pragma unroll
+        for (int i = 0; i < 9; i++) { s_state[0][i] = (double)keep.R21[i]; s_state[1][i] = (double)keep.R31[i]; }
+#pragma unroll
+        for (int i = 0; i < 3; i++) { s_state[0][9 + i] = (double)keep.t21[i]; s_state[1][9 + i] = (double)keep.t31[i]; }
+        s_scale = (double)keep.scale31;
+    }
+    __syncthreads();
+    const double K0 = (double)sc.K0, K2 = (double)sc.K2, K4 = (double)sc.K4, K5 = (double)sc.K5;
+    int status = 0, k = 0, bestT = -1, bestF = 0, bestJ = 0, best21 = 0, best31 = 0, bestK = 0;
+    double rms_in[2] = {0.0, 0.0}, rms_out[2] = {0.0, 0.0};
+    for (;;) {
+        double R[18], T[6], B[12];
+        float Rf[18], Tf[6];
+#pragma unroll
+        for (int i = 0; i < 9; i++) { R[i] = s_state[0][i]; R[9 + i] = s_state[1][i]; }
+#pragma unroll
+        for (int i = 0; i < 3; i++) { T[i] = s_state[0][9 + i]; T[3 + i] = s_state[1][9 + i]; }
+        const double s = s_scale;
+        const float sf = (float)s;
+#pragma unroll
+        for (int i = 0; i < 18; i++) Rf[i] = (float)R[i];
+#pragma unroll
+        for (int i = 0; i < 6; i++) Tf[i] = (float)T[i];
+        tangent_basis(T, B);
+        tangent_basis(T + 3, B + 6);
+        double acc[R3_SUMS];
+#pragma unroll
+        for (int i = 0; i < R3_SUMS; i++) acc[i] = 0.0;
+        int c21 = 0, c31 = 0, cJ = 0, cF = 0, cT = 0;
+        for (int e = tid; e < sc.E; e += R3_THREADS) {
+            bool in21, in31;
+            edgel_views(sc, e, Rf, Tf, Rf + 9, Tf + 3, in21, in31);
+            float se;
+            const TransferEdgel te = transfer_edgel(sc, e, Rf, Tf, Rf + 9, Tf + 3, se);
+            const float Z2 = te.Y2 + sf * Tf[5];   // transfer_inlier's own Z2
+            const bool inF = te.tested && Z2 > 0.0f;
+            const bool inT = inF && transfer_inlier(te.Y0, te.Y1, te.Y2, te.p0, te.p1, sf, Tf + 3, sc.K0, sc.K2, sc.K4, sc.K5);
+            c21 += in21 ? 1 : 0;
+            c31 += in31 ? 1 : 0;
+            cJ += te.joint ? 1 : 0;
+            cF += inF ? 1 : 0;
+            cT += inT ? 1 : 0;
+            if (inF) {
+                const float *p = sc.loc + (size_t)e * 6;
+                threeview_accumulate((double)p[0], (double)p[1], (double)p[2], (double)p[3], (double)p[4], (double)p[5],
+                                     R, T, B, R + 9, T + 3, B + 6, s, K0, K2, K4, K5, acc);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < R3_SUMS; i++) acc[i] = wave_sum_d(acc[i]);
+        c21 = wave_sum_i(c21);
+        c31 = wave_sum_i(c31);
+        cJ = wave_sum_i(cJ);
+        cF = wave_sum_i(cF);
+        cT = wave_sum_i(cT);
+        if (lane == 0) {
+#pragma unroll
+            for (int i = 0; i < R3_SUMS; i++) s_sum[wave][i] = acc[i];
+            s_cnt[wave][0] = cJ;
+            s_cnt[wave][1] = c21;
+            s_cnt[wave][2] = c31;
+            s_cnt[wave][3] = cF;
+            s_cnt[wave][4] = cT;
+        }
+        __syncthreads();
+        // the totals, the same in every thread
+        cJ = (s_cnt[0][0] + s_cnt[1][0]) + (s_cnt[2][0] + s_cnt[3][0]);
+        c21 = (s_cnt[0][1] + s_cnt[1][1]) + (s_cnt[2][1] + s_cnt[3][1]);
+        c31 = (s_cnt[0][2] + s_cnt[1][2]) + (s_cnt[2][2] + s_cnt[3][2]);
+        cF = (s_cnt[0][3] + s_cnt[1][3]) + (s_cnt[2][3] + s_cnt[3][3]);
+        cT = (s_cnt[0][4] + s_cnt[1][4]) + (s_cnt[2][4] + s_cnt[3][4]);
+        double rms[2];
+#pragma unroll
+        for (int v = 0; v < 2; v++) {
+            const int i = R3_A + R3_N + v;
+            const double sse = (s_sum[0][i] + s_sum[1][i]) + (s_sum[2][i] + s_sum[3][i]);
+            rms[v] = cF > 0 ? __builtin_sqrt(sse / (double)cF) : 0.0;
+        }
+        if (k == 0) { rms_in[0] = rms[0]; rms_in[1] = rms[1]; }
+        if (tid == 0) { rep->transfer_history[k] = cT; rep->joint_history[k] = cJ; }
+        if (cT >= bestT) {   // a tie goes to the later iterate
+            bestT = cT; bestF = cF; bestJ = cJ; best21 = c21; best31 = c31; bestK = k;
+            rms_out[0] = rms[0]; rms_out[1] = rms[1];
+            if (tid == 0) {
+#pragma unroll
+                for (int i = 0; i < 9; i++) { s_best[i] = Rf[i]; s_best[12 + i] = Rf[9 + i]; }
+#pragma unroll
+                for (int i = 0; i < 3; i++) { s_best[9 + i] = Tf[i]; s_best[21 + i] = Tf[3 + i]; }
+                s_best[24] = sf;
+            }
+        }
+        if (cF < a.min_inliers) { status |= HC_THREEVIEW_TOO_FEW; break; }
+        if (k == a.iterations) break;
+        if (wave == 0) {   // the whole wave: the solve shuffles between its lanes
+            double d[R3_N];
+            const bool ok = refine3_solve(
+                [&](int n) { return (s_sum[0][n] + s_sum[1][n]) + (s_sum[2][n] + s_sum[3][n]); }, lane, d);
+            if (lane == 0) s_singular = ok ? 0 : 1;
+            if (ok) {
+                if (lane == 0) refine_apply(s_state[0], d);
+                if (lane == 1) refine_apply(s_state[1], d + 5);
+                if (lane == 2) s_scale = s * exp(d[10]);
+            }
+        }
+        __syncthreads();
+        if (s_singular) { status |= HC_THREEVIEW_SINGULAR; break; }
+        k++;
+    }
+    __syncthreads();   // thread 0's last write of s_best
+    if (a.mask) {
+        float Rf[18], Tf[6];
+#pragma unroll
+        for (int i = 0; i < 9; i++) { Rf[i] = s_best[i]; Rf[9 + i] = s_best[12 + i]; }
+#pragma unroll
+        for (int i = 0; i < 3; i++) { Tf[i] = s_best[9 + i]; Tf[3 + i] = s_best[21 + i]; }
+        const float sf = s_best[24];
+        for (int w = wave; w < words; w += R3_WAVES) {
+            const int e = w * WAVE + lane;
+            bool in = false;
+            if (e < sc.E) {
+                float se;
+                const TransferEdgel te = transfer_edgel(sc, e, Rf, Tf, Rf + 9, Tf + 3, se);
+                in = te.tested && transfer_inlier(te.Y0, te.Y1, te.Y2, te.p0, te.p1, sf, Tf + 3, sc.K0, sc.K2, sc.K4, sc.K5);
+            }
+            const unsigned long long word = __ballot(in);
+            if (lane == 0) a.mask[w] = word;
+        }
+    }
+    if (tid != 0) return;
+    if (bestK > 0) {   // otherwise the values it came in with, bit for bit
+        hcTrifocalSelection o = keep;
+        o.inliers = bestJ;
+        o.inliers21 = best21;
+        o.inliers31 = best31;
+        o.key = ((uint64_t)(uint32_t)bestJ << 32) | (uint32_t)keep.path;
+#pragma unroll
+        for (int i = 0; i < 9; i++) { o.R21[i] = s_best[i]; o.R31[i] = s_best[12 + i]; }
+#pragma unroll
+        for (int i = 0; i < 3; i++) { o.t21[i] = s_best[9 + i]; o.t31[i] = s_best[21 + i]; }
+        o.scale31 = s_best[24];
+        a.sels[sel] = o;
+    }
+    rep->status = status;
+    rep->iterations_run = k;
+    rep->best_iteration = bestK;
+    for (int i = k + 1; i <= HC_REFINE_MAX_ITERATIONS; i++) rep->transfer_history[i] = rep->joint_history[i] = -1;
+    rep->fit_set = bestF;
+    rep->transfer_inliers = bestT;
+    rep->scale_in = keep.scale31;
+    rep->scale_out = s_best[24];
+    rep->pad = 0;
+    rep->rms_px_in[0] = rms_in[0]; rep->rms_px_in[1] = rms_in[1];
+    rep->rms_px_out[0] = rms_out[0]; rep->rms_px_out[1] = rms_out[1];
+}
+
+// HC_THREEVIEW_SELECT_BY_TRANSFER: k_pose_topk_select_transfer with the
+// three-view reports' final transfer counts.
+__global__ void __launch_bounds__(64) k_pose_topk_select_transfer3(int num_groups, int k,
+                                                                   const hcTrifocalSelection *__restrict__ refined,
+                                                                   const hcThreeViewReport *__restrict__ reports,
+                                                                   hcTrifocalSelection *__restrict__ best,
+                                                                   int32_t *__restrict__ best_rank) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= num_groups) return;
+    const hcTrifocalSelection *in = refined + (size_t)t * k;
+    const hcThreeViewReport *rp = reports + (size_t)t * k;
+    int rank = -1;
+    uint64_t tkey = 0, jkey = 0;
+    for (int r = 0; r < k; r++) {
+        if (in[r].path < 0) continue;
+        const uint64_t tk = ((uint64_t)(uint32_t)rp[r].transfer_inliers << 32) | (uint32_t)in[r].path;
+        if (rank < 0 || tk > tkey || (tk == tkey && in[r].key > jkey)) { rank = r; tkey = tk; jkey = in[r].key; }
+    }
+    hcTrifocalSelection o;
+    if (rank >= 0) {
+        o = in[rank];
+    } else {
+        o.num_candidates = in[0].num_candidates;
+        o.path = o.inliers = o.inliers21 = o.inliers31 = -1;
+        o.pad = 0;
+        o.key = 0;
+        for (int i = 0; i < 9; i++) o.R21[i] = o.R31[i] = 0.0f;
+        for (int i = 0; i < 3; i++) o.t21[i] = o.t31[i] = 0.0f;
+        o.scale31 = o.pad2 = 0.0f;
+    }
+    best[t] = o;
+    best_rank[t] = rank;
+}
+
+// What a refine call's settings ask of the three-view mode (off: the call as it was).
+struct ThreeViewMode {
+    bool on = false;
+    int bits = 0, iterations = 10;
+    hcScaleReport *scale_reports = nullptr;
+    hcThreeViewReport *reports = nullptr;
+    uint64_t *mask = nullptr;
+};
+
+// settings (a host pointer or nullptr) -> the mode; false when the mode is
+// selected and its fields are not valid for this call
+inline bool threeview_mode(const hcRefineSettings *s, bool topk, bool mask_allowed, ThreeViewMode &m) {
+    if (!s || s->pad[0] != HC_REFINE_THREEVIEW) return true;
+    const hcRefineThreeViewSettings *ts = reinterpret_cast<const hcRefineThreeViewSettings *>(s);
+    m.on = true;
+    m.bits = s->pad[1];
+    m.scale_reports = ts->scale_reports;
+    m.reports = ts->reports;
+    m.mask = ts->transfer_mask;
+    if (!m.scale_reports || !m.reports || (m.bits & ~(topk ? HC_THREEVIEW_SELECT_BY_TRANSFER : 0)) != 0) return false;
+    if (ts->iterations3 < 0 || ts->iterations3 > HC_REFINE_MAX_ITERATIONS || ts->pad != 0) return false;
+    if (m.mask && !mask_allowed) return false;
+    if (ts->iterations3 > 0) m.iterations = ts->iterations3;
+    return true;
+}
+
+// A refine or refine-and-select call with its modes.  Three-view: the
+// refinement, the scale fit of every selection (reports as in the scale mode, no
+// mask), the three-view stage in place on out, then the selection among a
+// group's k.
+template <bool GROUPED>
+hcStatus launch_refine_modes(const RefineArgs &a, const ScaleMode &m, const ThreeViewMode &tv, int num_groups,
+                             hcTrifocalSelection *best, int32_t *best_rank, hcStream stream) {
+    if (!tv.on) return launch_refine_scaled<GROUPED>(a, m, num_groups, best, best_rank, stream);
+    ScaleMode fit;
+    fit.on = true;
+    fit.reports = tv.scale_reports;
+    const hcStatus st = launch_refine_scaled<GROUPED>(a, fit, num_groups, nullptr, nullptr, stream);
+    if (st != HC_SUCCESS) return st;
+    const int n = num_groups * a.per_group;
+    const Refine3Args ra{a.out, tv.scale_reports, tv.reports, reinterpret_cast<unsigned long long *>(tv.mask),
+                         a.E, a.loc, a.K, a.groups, tv.iterations, a.min_inliers, a.per_group};
+    hipLaunchKernelGGL(k_pose_refine3<GROUPED>, dim3(n), dim3(R3_THREADS), 0, (hipStream_t)stream, ra);
+    if ((g_last_hip_error = hipGetLastError()) != hipSuccess) return HC_ERROR_LAUNCH;
+    if (!best) return HC_SUCCESS;
+    if ((tv.bits & HC_THREEVIEW_SELECT_BY_TRANSFER) != 0)
+        hipLaunchKernelGGL(k_pose_topk_select_transfer3, dim3((num_groups + 63) / 64), dim3(64), 0,
+                           (hipStream_t)stream, num_groups, a.per_group, a.out, tv.reports, best, best_rank);
+    else
+        hipLaunchKernelGGL(k_pose_topk_select, dim3((num_groups + 63) / 64), dim3(64), 0, (hipStream_t)stream,
+                           num_groups, a.per_group, a.out, best, best_rank);
+    if ((g_last_hip_error = hipGetLastError()) != hipSuccess) return HC_ERROR_LAUNCH;
+    return HC_SUCCESS;
+}
+
 }  // namespace
 
 }  // namespace hc
@@ -1130,11 +1578,12 @@ extern "C" hcStatus hc_trifocal_pose_refine(const hcTrifocalSelection *in, int n
     using namespace hc;
     int iterations, min_inliers;
     ScaleMode m;
+    ThreeViewMode tv;
     if (!in || num_edgels <= 0 || !locations || !K || !out || !refine_settings(settings, iterations, min_inliers) ||
-        !scale_mode(settings, false, true, m))
+        !scale_mode(settings, false, true, m) || !threeview_mode(settings, false, true, tv))
         return HC_ERROR_INVALID_VALUE;
     const RefineArgs a{in, out, report, num_edgels, locations, K, nullptr, iterations, min_inliers, 1};
-    return launch_refine_scaled<false>(a, m, 1, nullptr, nullptr, stream);
+    return launch_refine_modes<false>(a, m, tv, 1, nullptr, nullptr, stream);
 }
 
 extern "C" hcStatus hc_trifocal_pose_refine_grouped(int num_groups, const hcTripletGroup *groups,
@@ -1144,11 +1593,12 @@ extern "C" hcStatus hc_trifocal_pose_refine_grouped(int num_groups, const hcTrip
     using namespace hc;
     int iterations, min_inliers;
     ScaleMode m;
+    ThreeViewMode tv;
     if (num_groups <= 0 || !groups || !in || !out || !refine_settings(settings, iterations, min_inliers) ||
-        !scale_mode(settings, false, false, m))
+        !scale_mode(settings, false, false, m) || !threeview_mode(settings, false, false, tv))
         return HC_ERROR_INVALID_VALUE;
     const RefineArgs a{in, out, reports, 0, nullptr, nullptr, groups, iterations, min_inliers, 1};
-    return launch_refine_scaled<true>(a, m, num_groups, nullptr, nullptr, stream);
+    return launch_refine_modes<true>(a, m, tv, num_groups, nullptr, nullptr, stream);
 }
 
 extern "C" hcStatus hc_trifocal_pose_topk_joint(int num_paths, const hcComplex *tracks, const int32_t *inliers, int k,
@@ -1181,11 +1631,13 @@ extern "C" hcStatus hc_trifocal_pose_refine_topk(int k, const hcTrifocalSelectio
     using namespace hc;
     int iterations, min_inliers;
     ScaleMode m;
+    ThreeViewMode tv;
     if (k < 1 || k > HC_TOPK_MAX || !candidates || num_edgels <= 0 || !locations || !K || !refined || !best ||
-        !best_rank || !refine_settings(settings, iterations, min_inliers) || !scale_mode(settings, true, false, m))
+        !best_rank || !refine_settings(settings, iterations, min_inliers) || !scale_mode(settings, true, false, m) ||
+        !threeview_mode(settings, true, false, tv))
         return HC_ERROR_INVALID_VALUE;
     const RefineArgs a{candidates, refined, reports, num_edgels, locations, K, nullptr, iterations, min_inliers, k};
-    return launch_refine_scaled<false>(a, m, 1, best, best_rank, stream);
+    return launch_refine_modes<false>(a, m, tv, 1, best, best_rank, stream);
 }
 
 extern "C" hcStatus hc_trifocal_pose_refine_topk_grouped(int num_groups, const hcTripletGroup *groups, int k,
@@ -1197,10 +1649,11 @@ extern "C" hcStatus hc_trifocal_pose_refine_topk_grouped(int num_groups, const h
     using namespace hc;
     int iterations, min_inliers;
     ScaleMode m;
+    ThreeViewMode tv;
     if (num_groups < 1 || num_groups > 0x7FFFFFFF / HC_TOPK_MAX || !groups || k < 1 || k > HC_TOPK_MAX ||
         !candidates || !refined || !best || !best_rank || !refine_settings(settings, iterations, min_inliers) ||
-        !scale_mode(settings, true, false, m))
+        !scale_mode(settings, true, false, m) || !threeview_mode(settings, true, false, tv))
         return HC_ERROR_INVALID_VALUE;
     const RefineArgs a{candidates, refined, reports, 0, nullptr, nullptr, groups, iterations, min_inliers, k};
-    return launch_refine_scaled<true>(a, m, num_groups, best, best_rank, stream);
+    return launch_refine_modes<true>(a, m, tv, num_groups, best, best_rank, stream);
 }

@@ -29,6 +29,12 @@ t21, by three-view transfer support after the refinement (fit_scale,
 transfer_mask and select_by_transfer on the refine wrappers; fit_scale31 is the
 scale-only form).
 
+Three-view refinement (not in the reference): a further mode of the same calls
+(include/threeview/hc_pose_threeview.h) refines both views and the scale
+jointly on the three-view transfer after the refinement and the scale fit
+(three_view and three_view_iterations on the refine wrappers; it implies
+fit_scale).
+
 The four pose-support calls (per view / joint, one triplet / grouped) share one
 launcher and one synchronous wrapper (_launch, _run), parameterised by a _Rule.
 Every native call goes through the signature table of _abi: buffers and streams
@@ -323,8 +329,67 @@ def _check_scale_flags(what: str, fit_scale, transfer_mask=False, select_by_tran
 
 
 def _settings_ptr(settings):
-    """The hcRefineSettings pointer of settings, or of an hcRefineScaleSettings' head."""
+    """The hcRefineSettings pointer of settings, or of an extended settings struct's head."""
     return C.cast(C.pointer(settings), C.POINTER(_abi.hcRefineSettings))
+
+
+# ---- the three-view refinement, a further mode (include/threeview/hc_pose_threeview.h) ----
+THREEVIEW_REPORT_BYTES = _abi.THREEVIEW_REPORT_BYTES
+
+
+def three_view_report_dict(raw) -> dict:
+    r = _struct_from_raw(_abi.hcThreeViewReport, THREEVIEW_REPORT_BYTES, raw)
+    return dict(status=r.status, none=bool(r.status & _abi.HC_THREEVIEW_NONE),
+                too_few=bool(r.status & _abi.HC_THREEVIEW_TOO_FEW),
+                singular=bool(r.status & _abi.HC_THREEVIEW_SINGULAR),
+                skipped=bool(r.status & _abi.HC_THREEVIEW_SKIPPED),
+                iterations_run=r.iterations_run, best_iteration=r.best_iteration,
+                transfer_history=np.array(r.transfer_history[:], np.int32),
+                joint_history=np.array(r.joint_history[:], np.int32),
+                fit_set=r.fit_set, transfer_inliers=r.transfer_inliers,
+                scale_in=np.float32(r.scale_in), scale_out=np.float32(r.scale_out),
+                rms_px_in=np.array(r.rms_px_in[:], np.float64), rms_px_out=np.array(r.rms_px_out[:], np.float64))
+
+
+def _three_view_report_dicts(raw: torch.Tensor, count: int) -> list:
+    rows = raw.cpu().numpy().reshape(count, THREEVIEW_REPORT_BYTES)
+    return [three_view_report_dict(r) for r in rows]
+
+
+def _check_three_view(what: str, three_view, three_view_iterations, fit_scale):
+    """The three-view keywords of a refine wrapper, checked before anything
+    touches a device.  Returns fit_scale, which three_view implies."""
+    if not isinstance(three_view, (bool, np.bool_)):
+        raise _abi.HCError(f"{what}: three_view must be a boolean")
+    if three_view_iterations is not None:
+        v = three_view_iterations
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or \
+                not 1 <= v <= _abi.HC_REFINE_MAX_ITERATIONS:
+            raise _abi.HCError(f"{what}: three_view_iterations {v!r} outside 1..{_abi.HC_REFINE_MAX_ITERATIONS}")
+        if not three_view:
+            raise _abi.HCError(f"{what}: three_view_iterations needs three_view")
+    if three_view and not isinstance(fit_scale, (bool, np.bool_)):
+        raise _abi.HCError(f"{what}: fit_scale must be a boolean")
+    return True if three_view else fit_scale
+
+
+def _three_view_mode(settings, count: int, dev, three_view_iterations, transfer_mask=False, num_edgels=None,
+                     select_by_transfer=False):
+    """An hcRefineThreeViewSettings with `settings` as its head, count scale
+    reports and count three-view reports and, with transfer_mask, the mask's
+    words (new device tensors).  Returns (settings, scale reports, mask words or
+    None, three-view reports)."""
+    ts = _abi.hcRefineThreeViewSettings()
+    ts.head.iterations, ts.head.min_inliers = settings.iterations, settings.min_inliers
+    ts.head.pad[0] = _abi.HC_REFINE_THREEVIEW
+    ts.head.pad[1] = _abi.HC_THREEVIEW_SELECT_BY_TRANSFER if select_by_transfer else 0
+    scale = torch.empty(count * SCALE_REPORT_BYTES, dtype=torch.uint8, device=dev)
+    reports = torch.empty(count * THREEVIEW_REPORT_BYTES, dtype=torch.uint8, device=dev)
+    words = torch.empty((num_edgels + 63) // 64, dtype=torch.int64, device=dev) if transfer_mask else None
+    ts.scale_reports, ts.reports = scale.data_ptr(), reports.data_ptr()
+    ts.transfer_mask = words.data_ptr() if words is not None else None
+    ts.iterations3 = 10 if three_view_iterations is None else int(three_view_iterations)
+    return ts, scale, words, reports
 
 
 def _scale_mode(settings, count: int, dev, what: str, fit_scale, transfer_mask=False, num_edgels=None,
@@ -350,7 +415,8 @@ def _scale_mode(settings, count: int, dev, what: str, fit_scale, transfer_mask=F
 
 def launch_refine_joint(selection, edgels: torch.Tensor, K: torch.Tensor, iterations: int = 10,
                         min_inliers: int = 16, stream=None, out: torch.Tensor | None = None,
-                        fit_scale: bool = False, transfer_mask: bool = False, _scale_only: bool = False):
+                        fit_scale: bool = False, transfer_mask: bool = False, _scale_only: bool = False,
+                        three_view: bool = False, three_view_iterations: int | None = None):
     """Enqueue hc_trifocal_pose_refine (no sync): the joint selection's pose
     fitted to its joint inliers among the E edgels, the inlier set recomputed at
     every iterate.  selection: the device bytes of an hcTrifocalSelection, or a
@@ -361,9 +427,15 @@ def launch_refine_joint(selection, edgels: torch.Tensor, K: torch.Tensor, iterat
     fit_scale: the refined pose's scale31 is fitted by three-view transfer
     support in the same call (include/scale/hc_pose_scale.h); two more device
     tensors are returned, the scale report (SCALE_REPORT_BYTES,) u8 and, with
-    transfer_mask, the transfer mask's (E + 63) // 64 int64 words (else None)."""
+    transfer_mask, the transfer mask's (E + 63) // 64 int64 words (else None).
+    three_view: after the fit, both views and the scale are refined jointly on
+    the three-view transfer for three_view_iterations steps (default 10;
+    include/threeview/hc_pose_threeview.h).  It implies fit_scale; a fifth
+    device tensor is returned, the three-view report (THREEVIEW_REPORT_BYTES,)
+    u8, and the transfer mask describes the pose and scale that went out."""
     what = "refine_joint"
     settings = _refine_settings(iterations, min_inliers, what)
+    fit_scale = _check_three_view(what, three_view, three_view_iterations, fit_scale)
     _check_scale_flags(what, fit_scale, transfer_mask)
     dev = edgels.device
     selection = _device_selections(selection, dev, 1, what)
@@ -373,12 +445,19 @@ def launch_refine_joint(selection, edgels: torch.Tensor, K: torch.Tensor, iterat
     if out is None:
         out = torch.empty(JOINT_SEL_BYTES, dtype=torch.uint8, device=dev)
     out = _device_selections(out, dev, 1, what)
-    settings, scale, words = _scale_mode(settings, 1, dev, what, fit_scale, transfer_mask, int(edgels.shape[0]),
-                                         scale_only=_scale_only)
+    tv = None
+    if three_view:
+        settings, scale, words, tv = _three_view_mode(settings, 1, dev, three_view_iterations, transfer_mask,
+                                                      int(edgels.shape[0]))
+    else:
+        settings, scale, words = _scale_mode(settings, 1, dev, what, fit_scale, transfer_mask, int(edgels.shape[0]),
+                                             scale_only=_scale_only)
     report = None if _scale_only else torch.empty(REPORT_BYTES, dtype=torch.uint8, device=dev)
     _abi.call("hc_trifocal_pose_refine", _abi.ptr(selection), int(edgels.shape[0]), _abi.ptr(edgels), _abi.ptr(K),
               _settings_ptr(settings), _abi.ptr(out), _abi.ptr(report),
               _abi.ptr(stream if stream is not None else torch.cuda.current_stream(dev)))
+    if three_view:
+        return out, report, scale, words, tv
     return (out, report, scale, words) if fit_scale else (out, report)
 
 
@@ -390,16 +469,25 @@ def _scale_entry(scale: torch.Tensor, words) -> dict:
 
 
 def refine_joint(selection, edgels: torch.Tensor, K: torch.Tensor, iterations: int = 10, min_inliers: int = 16,
-                 return_device_selection: bool = False, fit_scale: bool = False, transfer_mask: bool = False):
+                 return_device_selection: bool = False, fit_scale: bool = False, transfer_mask: bool = False,
+                 three_view: bool = False, three_view_iterations: int | None = None):
     """Synchronous wrapper: (refined selection dict, report dict), and with
     return_device_selection also the refined selection's device bytes.  With
     fit_scale the report dict has a "scale" entry, the scale report as a dict
-    (with transfer_mask also its "mask", the packed uint64 words)."""
+    (with transfer_mask also its "mask", the packed uint64 words).  With
+    three_view it has both "scale" (the vote's report) and "three_view" (the
+    three-view report as a dict, which then holds "mask")."""
     out, report, *rest = launch_refine_joint(selection, edgels, K, iterations, min_inliers, fit_scale=fit_scale,
-                                             transfer_mask=transfer_mask)
+                                             transfer_mask=transfer_mask, three_view=three_view,
+                                             three_view_iterations=three_view_iterations)
     torch.cuda.synchronize(edgels.device)
     rep = refine_report_dict(report)
-    if fit_scale:
+    if three_view:
+        rep["scale"] = scale_report_dict(rest[0])
+        rep["three_view"] = three_view_report_dict(rest[2])
+        if rest[1] is not None:
+            rep["three_view"]["mask"] = _mask_words(rest[1])
+    elif fit_scale:
         rep["scale"] = _scale_entry(*rest)
     res = (joint_selection_dict(joint_selection_struct(out)), rep)
     return (*res, out) if return_device_selection else res
@@ -423,15 +511,19 @@ def fit_scale31(selection, edgels: torch.Tensor, K: torch.Tensor, transfer_mask:
 
 
 def launch_refine_joint_grouped(selections, batch, iterations: int = 10, min_inliers: int = 16, stream=None,
-                                fit_scale: bool = False, transfer_mask: bool = False):
+                                fit_scale: bool = False, transfer_mask: bool = False, three_view: bool = False,
+                                three_view_iterations: int | None = None):
     """Enqueue hc_trifocal_pose_refine_grouped (no sync): selection t refined on
     triplet t of batch (a multi.DeviceTripletBatch).  selections: T selections
     as device bytes, or a list of dicts / structs, which is uploaded.  Returns
     (selections (T * JOINT_SEL_BYTES,) u8, reports (T * REPORT_BYTES,) u8), and
     with fit_scale also the scale reports (T * SCALE_REPORT_BYTES,) u8.  The
-    grouped call writes no transfer mask: transfer_mask is refused."""
+    grouped call writes no transfer mask: transfer_mask is refused.  With
+    three_view (which implies fit_scale) a fourth tensor follows, the three-view
+    reports (T * THREEVIEW_REPORT_BYTES,) u8."""
     what = "refine_joint_grouped"
     settings = _refine_settings(iterations, min_inliers, what)
+    fit_scale = _check_three_view(what, three_view, three_view_iterations, fit_scale)
     _check_scale_flags(what, fit_scale, transfer_mask, mask_allowed=False)
     dev = batch.device
     T = batch.num_groups
@@ -441,25 +533,35 @@ def launch_refine_joint_grouped(selections, batch, iterations: int = 10, min_inl
     batch.check()   # edgel counts: the kernel does not validate them
     out = torch.empty(T * JOINT_SEL_BYTES, dtype=torch.uint8, device=dev)
     reports = torch.empty(T * REPORT_BYTES, dtype=torch.uint8, device=dev)
-    settings, scale, _ = _scale_mode(settings, T, dev, what, fit_scale, transfer_mask)
+    tv = None
+    if three_view:
+        settings, scale, _, tv = _three_view_mode(settings, T, dev, three_view_iterations)
+    else:
+        settings, scale, _ = _scale_mode(settings, T, dev, what, fit_scale, transfer_mask)
     _abi.call("hc_trifocal_pose_refine_grouped", T, _abi.ptr(batch.groups), _abi.ptr(selections),
               _settings_ptr(settings), _abi.ptr(out), _abi.ptr(reports),
               _abi.ptr(stream if stream is not None else torch.cuda.current_stream(dev)))
+    if three_view:
+        return out, reports, scale, tv
     return (out, reports, scale) if fit_scale else (out, reports)
 
 
 def refine_joint_grouped(selections, batch, iterations: int = 10, min_inliers: int = 16, device=None,
-                         fit_scale: bool = False, transfer_mask: bool = False):
+                         fit_scale: bool = False, transfer_mask: bool = False, three_view: bool = False,
+                         three_view_iterations: int | None = None):
     """Synchronous wrapper: ([refined selection dict] * T, [report dict] * T).
     batch: a multi.TripletBatch (copied to device, or to the selections' device)
     or a multi.DeviceTripletBatch.  With fit_scale every report dict has a
-    "scale" entry."""
+    "scale" entry, with three_view also a "three_view" entry."""
+    fit_scale = _check_three_view("refine_joint_grouped", three_view, three_view_iterations, fit_scale)
+    _check_scale_flags("refine_joint_grouped", fit_scale, transfer_mask, mask_allowed=False)
     if not hasattr(batch, "groups"):
         if device is None:
             device = selections.device if isinstance(selections, torch.Tensor) else "cuda:0"
         batch = batch.to(device)
     out, reports, *rest = launch_refine_joint_grouped(selections, batch, iterations, min_inliers, fit_scale=fit_scale,
-                                                      transfer_mask=transfer_mask)
+                                                      transfer_mask=transfer_mask, three_view=three_view,
+                                                      three_view_iterations=three_view_iterations)
     torch.cuda.synchronize(batch.device)
     T = batch.num_groups
     sels = out.cpu().numpy().reshape(T, JOINT_SEL_BYTES)
@@ -467,6 +569,9 @@ def refine_joint_grouped(selections, batch, iterations: int = 10, min_inliers: i
     if fit_scale:
         for r, s in zip(reps, _scale_report_dicts(rest[0], T)):
             r["scale"] = s
+    if three_view:
+        for r, s in zip(reps, _three_view_report_dicts(rest[1], T)):
+            r["three_view"] = s
     return [joint_selection_dict(joint_selection_struct(r)) for r in sels], reps
 
 
@@ -566,13 +671,19 @@ def topk_joint_grouped(tracks: torch.Tensor, inliers: torch.Tensor, batch, k: in
 
 
 def _launch_refine_topk(what, candidates, k, scene, iterations, min_inliers, stream, refined, fit_scale=False,
-                        transfer_mask=False, select_by_transfer=False):
+                        transfer_mask=False, select_by_transfer=False, three_view=False, three_view_iterations=None):
     """scene: (edgels, K) or a multi.DeviceTripletBatch.  With fit_scale the
     returned tuple has a fifth tensor, the T * k scale reports, and, when
     transfer_mask is set, a sixth: the transfer mask of best (the single-scene
-    call only), written by a scale-only fit of best on the same stream."""
+    call only), written by a scale-only fit of best on the same stream.  With
+    three_view the tuple is (best, best_rank, refined, reports, scale reports,
+    three-view reports); a transfer mask is then refused (the scale-only fit of
+    best would vote its scale again)."""
     k = _check_k(k, what)
     settings = _refine_settings(iterations, min_inliers, what)
+    fit_scale = _check_three_view(what, three_view, three_view_iterations, fit_scale)
+    if three_view and transfer_mask is True:
+        raise _abi.HCError(f"{what}: with three_view the transfer mask is written by refine_joint only")
     grouped = not isinstance(scene, tuple)
     _check_scale_flags(what, fit_scale, transfer_mask, select_by_transfer, not grouped)
     dev = scene.device if grouped else scene[0].device
@@ -586,7 +697,12 @@ def _launch_refine_topk(what, candidates, k, scene, iterations, min_inliers, str
     reports = torch.empty(T * k * REPORT_BYTES, dtype=torch.uint8, device=dev)
     best = torch.empty(T * JOINT_SEL_BYTES, dtype=torch.uint8, device=dev)
     best_rank = torch.empty(T, dtype=torch.int32, device=dev)
-    settings, scale, _ = _scale_mode(settings, T * k, dev, what, fit_scale, select_by_transfer=select_by_transfer)
+    tv = None
+    if three_view:
+        settings, scale, _, tv = _three_view_mode(settings, T * k, dev, three_view_iterations,
+                                                  select_by_transfer=select_by_transfer)
+    else:
+        settings, scale, _ = _scale_mode(settings, T * k, dev, what, fit_scale, select_by_transfer=select_by_transfer)
     s = _abi.ptr(stream if stream is not None else torch.cuda.current_stream(dev))
     out = (_abi.ptr(refined), _abi.ptr(reports), _abi.ptr(best), _abi.ptr(best_rank), s)
     if grouped:
@@ -599,6 +715,8 @@ def _launch_refine_topk(what, candidates, k, scene, iterations, min_inliers, str
                 raise _abi.HCError(f"{what}: buffers must be contiguous tensors on one device")
         _abi.call("hc_trifocal_pose_refine_topk", k, _abi.ptr(candidates), int(scene[0].shape[0]), _abi.ptr(scene[0]),
                   _abi.ptr(scene[1]), _settings_ptr(settings), *out)
+    if three_view:
+        return best, best_rank, refined, reports, scale, tv
     if not fit_scale:
         return best, best_rank, refined, reports
     if not transfer_mask:
@@ -606,6 +724,11 @@ def _launch_refine_topk(what, candidates, k, scene, iterations, min_inliers, str
     # the same pose gives the same vote: best keeps its bytes, and the mask is its own
     _, _, words = launch_fit_scale31(best, scene[0], scene[1], transfer_mask=True, stream=stream, out=best)
     return best, best_rank, refined, reports, scale, words
+
+
+def _topk_extra(out: tuple, three_view: bool) -> tuple:
+    """The (scale, words, three_view) arguments of _refine_topk_dicts from a launch's tuple."""
+    return (out[4], None, out[5]) if three_view else out[4:]
 
 
 def _topk_count(candidates, what: str) -> int:
@@ -619,7 +742,8 @@ def _topk_count(candidates, what: str) -> int:
 
 def launch_refine_topk(candidates, edgels: torch.Tensor, K: torch.Tensor, iterations: int = 10, min_inliers: int = 16,
                        stream=None, refined: torch.Tensor | None = None, fit_scale: bool = False,
-                       transfer_mask: bool = False, select_by_transfer: bool = False):
+                       transfer_mask: bool = False, select_by_transfer: bool = False, three_view: bool = False,
+                       three_view_iterations: int | None = None):
     """Enqueue hc_trifocal_pose_refine_topk (no sync): every candidate refined
     on the E edgels as launch_refine_joint refines it, in one launch, and the
     refined selection with the most joint inliers (ties -> the larger batch id)
@@ -632,19 +756,29 @@ def launch_refine_topk(candidates, edgels: torch.Tensor, K: torch.Tensor, iterat
     transfer support (include/scale/hc_pose_scale.h) and a fifth tensor, the k
     scale reports (k * SCALE_REPORT_BYTES,) u8, is returned; best is chosen as
     without it, or with select_by_transfer by the largest transfer_inliers << 32
-    | path.  transfer_mask: a sixth tensor, the transfer mask's words of best."""
+    | path.  transfer_mask: a sixth tensor, the transfer mask's words of best.
+    three_view: all k selections also go through the three-view refinement
+    (include/threeview/hc_pose_threeview.h; it implies fit_scale); the tuple is
+    then (best, best_rank, refined, reports, scale reports, three-view reports
+    (k * THREEVIEW_REPORT_BYTES,) u8), best is chosen by the final joint key, or
+    with select_by_transfer by the final transfer_inliers << 32 | path."""
     what = "refine_topk"
     _refine_settings(iterations, min_inliers, what)
+    _check_three_view(what, three_view, three_view_iterations, fit_scale)
     return _launch_refine_topk(what, candidates, _topk_count(candidates, what), (edgels, K), iterations, min_inliers,
-                               stream, refined, fit_scale, transfer_mask, select_by_transfer)
+                               stream, refined, fit_scale, transfer_mask, select_by_transfer, three_view,
+                               three_view_iterations)
 
 
-def _refine_topk_dicts(best, best_rank, refined, reports, T, k, scale=None, words=None):
+def _refine_topk_dicts(best, best_rank, refined, reports, T, k, scale=None, words=None, three_view=None):
     sels = _selection_dicts(refined, T * k)
     reps = [refine_report_dict(r) for r in reports.cpu().numpy().reshape(T * k, REPORT_BYTES)]
     if scale is not None:
         for r, sc in zip(reps, _scale_report_dicts(scale, T * k)):
             r["scale"] = sc
+    if three_view is not None:
+        for r, tv in zip(reps, _three_view_report_dicts(three_view, T * k)):
+            r["three_view"] = tv
     ranks = best_rank.cpu().numpy()
     out = [dict(best=b, best_rank=int(ranks[t]), refined=sels[t * k:(t + 1) * k], reports=reps[t * k:(t + 1) * k])
            for t, b in enumerate(_selection_dicts(best, T))]
@@ -654,14 +788,17 @@ def _refine_topk_dicts(best, best_rank, refined, reports, T, k, scale=None, word
 
 
 def refine_topk(candidates, edgels: torch.Tensor, K: torch.Tensor, iterations: int = 10, min_inliers: int = 16,
-                fit_scale: bool = False, transfer_mask: bool = False, select_by_transfer: bool = False):
+                fit_scale: bool = False, transfer_mask: bool = False, select_by_transfer: bool = False,
+                three_view: bool = False, three_view_iterations: int | None = None):
     """Synchronous wrapper: (best dict, best_rank, [refined dict] * k, [report dict] * k).
     With fit_scale every report dict has a "scale" entry; with transfer_mask
-    best's entry (reports[best_rank]["scale"]) also has "mask", the packed words."""
+    best's entry (reports[best_rank]["scale"]) also has "mask", the packed words.
+    With three_view every report dict also has a "three_view" entry."""
     out = launch_refine_topk(candidates, edgels, K, iterations, min_inliers, fit_scale=fit_scale,
-                             transfer_mask=transfer_mask, select_by_transfer=select_by_transfer)
+                             transfer_mask=transfer_mask, select_by_transfer=select_by_transfer,
+                             three_view=three_view, three_view_iterations=three_view_iterations)
     torch.cuda.synchronize(edgels.device)
-    d = _refine_topk_dicts(*out[:4], 1, _topk_count(candidates, "refine_topk"), *out[4:])[0]
+    d = _refine_topk_dicts(*out[:4], 1, _topk_count(candidates, "refine_topk"), *_topk_extra(out, three_view))[0]
     if "transfer_mask" in d and d["best_rank"] >= 0:
         d["reports"][d["best_rank"]]["scale"]["mask"] = d["transfer_mask"]
     return d["best"], d["best_rank"], d["refined"], d["reports"]
@@ -669,33 +806,40 @@ def refine_topk(candidates, edgels: torch.Tensor, K: torch.Tensor, iterations: i
 
 def launch_refine_topk_grouped(candidates, batch, k: int, iterations: int = 10, min_inliers: int = 16, stream=None,
                                refined: torch.Tensor | None = None, fit_scale: bool = False,
-                               transfer_mask: bool = False, select_by_transfer: bool = False):
+                               transfer_mask: bool = False, select_by_transfer: bool = False,
+                               three_view: bool = False, three_view_iterations: int | None = None):
     """Enqueue hc_trifocal_pose_refine_topk_grouped (no sync): candidates
     [t * k + r] refined on triplet t of batch (a multi.DeviceTripletBatch), one
     selection per triplet.  Returns (best (T * JOINT_SEL_BYTES,) u8, best_rank
     (T,) i32, refined, reports), and with fit_scale also the T * k scale reports
-    (select_by_transfer as in launch_refine_topk; transfer_mask is refused)."""
+    (select_by_transfer as in launch_refine_topk; transfer_mask is refused);
+    with three_view the scale reports and the T * k three-view reports."""
     _check_k(k, "refine_topk_grouped")
     return _launch_refine_topk("refine_topk_grouped", candidates, k, batch, iterations, min_inliers, stream, refined,
-                               fit_scale, transfer_mask, select_by_transfer)
+                               fit_scale, transfer_mask, select_by_transfer, three_view, three_view_iterations)
 
 
 def refine_topk_grouped(candidates, batch, k: int, iterations: int = 10, min_inliers: int = 16, device=None,
-                        fit_scale: bool = False, transfer_mask: bool = False, select_by_transfer: bool = False):
+                        fit_scale: bool = False, transfer_mask: bool = False, select_by_transfer: bool = False,
+                        three_view: bool = False, three_view_iterations: int | None = None):
     """Synchronous wrapper: per triplet a dict(best, best_rank, refined, reports)
     of dicts.  batch: a multi.TripletBatch (copied to device, or to the
     candidates' device) or a multi.DeviceTripletBatch.  With fit_scale every
-    report dict has a "scale" entry."""
+    report dict has a "scale" entry, with three_view also a "three_view" entry."""
     _check_k(k, "refine_topk_grouped")
     _refine_settings(iterations, min_inliers, "refine_topk_grouped")
+    _check_scale_flags("refine_topk_grouped", _check_three_view("refine_topk_grouped", three_view,
+                                                                 three_view_iterations, fit_scale),
+                       transfer_mask, select_by_transfer, mask_allowed=False)
     if not hasattr(batch, "groups"):
         if device is None:
             device = candidates.device if isinstance(candidates, torch.Tensor) else "cuda:0"
         batch = batch.to(device)
     out = launch_refine_topk_grouped(candidates, batch, k, iterations, min_inliers, fit_scale=fit_scale,
-                                     transfer_mask=transfer_mask, select_by_transfer=select_by_transfer)
+                                     transfer_mask=transfer_mask, select_by_transfer=select_by_transfer,
+                                     three_view=three_view, three_view_iterations=three_view_iterations)
     torch.cuda.synchronize(batch.device)
-    return _refine_topk_dicts(*out[:4], batch.num_groups, k, *out[4:])
+    return _refine_topk_dicts(*out[:4], batch.num_groups, k, *_topk_extra(out, three_view))
 
 
 def merge_topk(parts: list, path_offsets: list, k: int) -> list:
@@ -724,7 +868,8 @@ def merge_topk(parts: list, path_offsets: list, k: int) -> list:
 
 def select_refined(tracks: torch.Tensor, converge: torch.Tensor, edgels: torch.Tensor, K: torch.Tensor, k: int = 8,
                    iterations: int = 10, min_inliers: int = 16, stream=None, fit_scale: bool = False,
-                   transfer_mask: bool = False, select_by_transfer: bool = False):
+                   transfer_mask: bool = False, select_by_transfer: bool = False, three_view: bool = False,
+                   three_view_iterations: int | None = None):
     """Joint pose support, the k best candidates, their refinement and the
     selection among the refined ones, enqueued on one stream with a single
     synchronisation at the end.  Returns (best dict, info); info: joint (the
@@ -732,11 +877,16 @@ def select_refined(tracks: torch.Tensor, converge: torch.Tensor, edgels: torch.T
     ([dict] * k), refined_inliers ([int] * k, -1 for a "none" rank) and reports.
     With fit_scale every report has a "scale" entry and info has scale, best's
     own (None without a best; with transfer_mask it holds "mask");
-    select_by_transfer as in launch_refine_topk."""
+    select_by_transfer as in launch_refine_topk.  With three_view (which
+    implies fit_scale) every report also has a "three_view" entry and info has
+    three_view, best's own (None without a best); a transfer mask is refused."""
     what = "select_refined"
     k = _check_k(k, what)
     _refine_settings(iterations, min_inliers, what)
+    fit_scale = _check_three_view(what, three_view, three_view_iterations, fit_scale)
     _check_scale_flags(what, fit_scale, transfer_mask, select_by_transfer)
+    if three_view and transfer_mask:
+        raise _abi.HCError(f"{what}: with three_view the transfer mask is written by refine_joint only")
     dev = tracks.device
     n = converge.numel()
     inl = torch.empty((n, 3), dtype=torch.int32, device=dev)
@@ -745,9 +895,10 @@ def select_refined(tracks: torch.Tensor, converge: torch.Tensor, edgels: torch.T
     launch_pose_support_joint(tracks, converge, edgels, K, inl, sel, stream)
     cand = launch_topk_joint(tracks, inl, k, stream=stream)
     out = launch_refine_topk(cand, edgels, K, iterations, min_inliers, stream, fit_scale=fit_scale,
-                             transfer_mask=transfer_mask, select_by_transfer=select_by_transfer)
+                             transfer_mask=transfer_mask, select_by_transfer=select_by_transfer,
+                             three_view=three_view, three_view_iterations=three_view_iterations)
     stream.synchronize()
-    d = _refine_topk_dicts(*out[:4], 1, k, *out[4:])[0]
+    d = _refine_topk_dicts(*out[:4], 1, k, *_topk_extra(out, three_view))[0]
     info = dict(joint=joint_selection_dict(joint_selection_struct(sel)), best_rank=d["best_rank"],
                 candidates=_selection_dicts(cand, k), refined=d["refined"],
                 refined_inliers=[r["inliers"] for r in d["refined"]], reports=d["reports"])
@@ -757,6 +908,8 @@ def select_refined(tracks: torch.Tensor, converge: torch.Tensor, edgels: torch.T
             info["scale"] = dict(d["reports"][d["best_rank"]]["scale"])
             if "transfer_mask" in d:
                 info["scale"]["mask"] = d["transfer_mask"]
+    if three_view:
+        info["three_view"] = dict(d["reports"][d["best_rank"]]["three_view"]) if d["best_rank"] >= 0 else None
     return d["best"], info
 
 
