@@ -41,6 +41,11 @@
 #             (scripts/threeview_fit.py [TRIALS [REPS]]) -> TAG_threeview.json
 #   threeview_ab  the refine calls with the modes off (scripts/threeview_fit.py --existing) on builds NAME=lib/libX.so ...
 #             (package-relative), alternately, 3 rounds -> TAG_threeview_existing.jsonl; config 2 and one sample: the ab step
+#   structure the 3D edgels of the selected pose on the config-5 protocol: count, tangents and oriented per size, the median
+#             sin3 on runs that pass and that fail the GT check, and the stage's cost against the same call in three-view
+#             mode (scripts/structure_fit.py [TRIALS [REPS]]) -> TAG_structure.json
+#   structure_ab  the refine calls with the modes off (scripts/threeview_fit.py --existing) on builds NAME=lib/libX.so ...
+#             (package-relative), alternately, 3 rounds -> TAG_structure_existing.jsonl; config 2 and one sample: the ab step
 #   p2c       the ablation ladder from the archived P2C tracker up: P2C, PH, PH_CodeOpt and the headline launch
 #             alternately on config 2 (scripts/ablation_p2c.py [--reps R]) -> TAG_ablation_p2c.json
 #   validate  tests,luwork,bench,profile,datasets
@@ -158,6 +163,17 @@ for k,v in sorted(g.items()): print(k, v)" ;;
         done
       done
       [ -f $O/${T}_threeview_existing.jsonl ] && cat $O/${T}_threeview_existing.jsonl ;;
+    structure) run structure 900 python scripts/structure_fit.py "$@" > $O/${T}_structure.json; rc=$?; tail -c 600 $O/${T}_structure.json ;;
+    structure_ab)
+      rc=0
+      for rd in 0 1 2; do
+        for kv in "$@"; do
+          HC_TRIFOCAL_LIB=$P/${kv#*=} run existing_${kv%%=*} 200 python scripts/threeview_fit.py --existing > $O/${T}_tmp.json; rc=$?
+          [ $rc -eq 0 ] || break 2
+          python -c "import json; d=json.load(open('$O/${T}_tmp.json')); d.update(build='${kv%%=*}', round=$rd); print(json.dumps(d))" >> $O/${T}_structure_existing.jsonl
+        done
+      done
+      [ -f $O/${T}_structure_existing.jsonl ] && cat $O/${T}_structure_existing.jsonl ;;
     p2c) run p2c 300 python scripts/ablation_p2c.py --out $O/${T}_ablation_p2c.json "$@"; rc=$? ;;
     gated_ab)
       rc=0

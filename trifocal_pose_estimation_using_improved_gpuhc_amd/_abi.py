@@ -11,7 +11,7 @@ holds both against the headers (layouts through the C compiler, signatures
 against the prototypes).  The headers in directories of their own
 (include/p2c, include/refine, include/topk, include/adaptive) have tables of their own,
 P2C_SIGNATURES, REFINE_SIGNATURES, TOPK_SIGNATURES and ADAPTIVE_SIGNATURES, checked the same way
-(include/scale and include/threeview declare structs only: the scale fit and the three-view refinement are modes of the refine calls).  Callers go through two helpers: ptr(x), the c_void_p
+(include/scale, include/threeview and include/structure declare structs only: the scale fit, the three-view refinement and the reconstruction are modes of the refine calls).  Callers go through two helpers: ptr(x), the c_void_p
 of a tensor, array or stream, and call(name, *args), which raises HCError on a
 status other than HC_SUCCESS.
 """
@@ -20,6 +20,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 from collections import namedtuple
+
+import numpy as np
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 # HC_TRIFOCAL_LIB: an alternative build of the same library (A/B experiments,
@@ -219,6 +221,45 @@ class hcRefineThreeViewSettings(C.Structure):
 
 
 THREEVIEW_REPORT_BYTES = C.sizeof(hcThreeViewReport)   # 328
+
+# include/structure/hc_pose_structure.h: the reconstruction of the 3D edgels, a
+# further mode of the refine calls (no function of its own; its structs and the
+# table below are held against the header by tests/test_structure_host.py)
+HC_REFINE_STRUCTURE = 0x53543344          # hcRefineSettings::pad[0] of an hcRefineStructureSettings
+HC_STRUCTURE_ONLY = 1                     # pad[1]: mode bit (bit 2 stays HC_THREEVIEW_SELECT_BY_TRANSFER)
+HC_EDGEL3D_TANGENT, HC_EDGEL3D_ORIENTED = 1, 2   # hcEdgel3D::flags
+HC_STRUCTURE_NONE = 1                     # hcStructureReport::status
+STRUCTURE_CONSTANTS = {"HC_REFINE_STRUCTURE": HC_REFINE_STRUCTURE, "HC_STRUCTURE_ONLY": HC_STRUCTURE_ONLY,
+                       "HC_EDGEL3D_TANGENT": HC_EDGEL3D_TANGENT, "HC_EDGEL3D_ORIENTED": HC_EDGEL3D_ORIENTED,
+                       "HC_STRUCTURE_NONE": HC_STRUCTURE_NONE}
+
+
+class hcEdgel3D(C.Structure):
+    """include/structure/hc_pose_structure.h: one reconstructed edgel, 48 bytes"""
+    _fields_ = [("X", C.c_float * 3), ("T", C.c_float * 3), ("err3_px", C.c_float), ("sin_plane", C.c_float),
+                ("sin3", C.c_float), ("edgel", C.c_int32), ("flags", C.c_int32), ("pad", C.c_int32)]
+
+
+class hcStructureReport(C.Structure):
+    """include/structure/hc_pose_structure.h: what one reconstruction did, 32 bytes"""
+    _fields_ = [("status", C.c_int32), ("count", C.c_int32), ("tangents", C.c_int32), ("oriented", C.c_int32),
+                ("scale31", C.c_float), ("pad", C.c_int32 * 3)]
+
+
+class hcRefineStructureSettings(C.Structure):
+    """include/structure/hc_pose_structure.h: the settings of the structure mode,
+    88 bytes; its address is passed as the hcRefineSettings'."""
+    _fields_ = [("tv", hcRefineThreeViewSettings), ("tangents", C.c_void_p), ("edgel_offsets", C.c_void_p),
+                ("edgels3d", C.c_void_p), ("reports", C.c_void_p), ("min_sin_plane", C.c_float),
+                ("max_sin3", C.c_float)]
+
+
+EDGEL3D_BYTES = C.sizeof(hcEdgel3D)                    # 48
+STRUCTURE_REPORT_BYTES = C.sizeof(hcStructureReport)   # 32
+# hcEdgel3D as a numpy record
+EDGEL3D_DTYPE = np.dtype([("X", "<f4", (3,)), ("T", "<f4", (3,)), ("err3_px", "<f4"), ("sin_plane", "<f4"),
+                          ("sin3", "<f4"), ("edgel", "<i4"), ("flags", "<i4"), ("pad", "<i4")])
+assert EDGEL3D_DTYPE.itemsize == EDGEL3D_BYTES
 
 
 # One entry per function of include/*.h: restype and argtypes as the prototype

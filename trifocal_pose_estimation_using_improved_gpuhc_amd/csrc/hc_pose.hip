@@ -35,6 +35,8 @@
 // described below the top-k) fit a refined selection's scale31 by three-view transfer.
 // k_pose_refine3<GROUPED> (include/threeview/hc_pose_threeview.h, described at the
 // end) then refines both views and the scale jointly on the three-view transfer.
+// k_pose_structure<GROUPED> (include/structure/hc_pose_structure.h, in
+// hc_structure.hpp) reconstructs the 3D edgels of the pose that goes out.
 #include <type_traits>
 
 #include "../../include/hc_pose.h"
@@ -42,6 +44,7 @@
 #include "../../include/topk/hc_pose_topk.h"
 #include "../../include/scale/hc_pose_scale.h"
 #include "../../include/threeview/hc_pose_threeview.h"
+#include "../../include/structure/hc_pose_structure.h"
 #include "hc_device.hpp"
 #include "hc_pose_device.hpp"   // make_pose, reproj_inlier, edgel_views, is_candidate: shared with the gated tracker
 
@@ -1472,13 +1475,12 @@ struct ThreeViewMode {
     uint64_t *mask = nullptr;
 };
 
-// settings (a host pointer or nullptr) -> the mode; false when the mode is
-// selected and its fields are not valid for this call
-inline bool threeview_mode(const hcRefineSettings *s, bool topk, bool mask_allowed, ThreeViewMode &m) {
-    if (!s || s->pad[0] != HC_REFINE_THREEVIEW) return true;
-    const hcRefineThreeViewSettings *ts = reinterpret_cast<const hcRefineThreeViewSettings *>(s);
+// The fields of a three-view settings block with the mode bits `bits` -> the
+// mode; false when they are not valid for this call
+inline bool threeview_fields(const hcRefineThreeViewSettings *ts, int bits, bool topk, bool mask_allowed,
+                             ThreeViewMode &m) {
     m.on = true;
-    m.bits = s->pad[1];
+    m.bits = bits;
     m.scale_reports = ts->scale_reports;
     m.reports = ts->reports;
     m.mask = ts->transfer_mask;
@@ -1489,13 +1491,30 @@ inline bool threeview_mode(const hcRefineSettings *s, bool topk, bool mask_allow
     return true;
 }
 
+// settings (a host pointer or nullptr) -> the mode; false when the mode is
+// selected and its fields are not valid for this call
+inline bool threeview_mode(const hcRefineSettings *s, bool topk, bool mask_allowed, ThreeViewMode &m) {
+    if (!s || s->pad[0] != HC_REFINE_THREEVIEW) return true;
+    return threeview_fields(reinterpret_cast<const hcRefineThreeViewSettings *>(s), s->pad[1], topk, mask_allowed, m);
+}
+
+// ---- the structure stage (include/structure/hc_pose_structure.h) ---------------
+#include "hc_structure.hpp"
+
 // A refine or refine-and-select call with its modes.  Three-view: the
 // refinement, the scale fit of every selection (reports as in the scale mode, no
 // mask), the three-view stage in place on out, then the selection among a
-// group's k.
+// group's k.  Structure: the same (its settings embed the three-view mode's),
+// then the structure stage on out, or on best after the selection; with
+// HC_STRUCTURE_ONLY that stage alone, on in.
 template <bool GROUPED>
-hcStatus launch_refine_modes(const RefineArgs &a, const ScaleMode &m, const ThreeViewMode &tv, int num_groups,
-                             hcTrifocalSelection *best, int32_t *best_rank, hcStream stream) {
+hcStatus launch_refine_modes(const RefineArgs &a, const ScaleMode &m, const ThreeViewMode &tv, const StructureMode &sm,
+                             int num_groups, hcTrifocalSelection *best, int32_t *best_rank, hcStream stream) {
+    if (sm.only) {
+        (void)hipGetLastError();
+        return launch_structure<GROUPED>(a, sm, a.in, a.out != a.in ? a.out : nullptr, nullptr, nullptr, num_groups,
+                                         stream);
+    }
     if (!tv.on) return launch_refine_scaled<GROUPED>(a, m, num_groups, best, best_rank, stream);
     ScaleMode fit;
     fit.on = true;
@@ -1507,15 +1526,18 @@ hcStatus launch_refine_modes(const RefineArgs &a, const ScaleMode &m, const Thre
                          a.E, a.loc, a.K, a.groups, tv.iterations, a.min_inliers, a.per_group};
     hipLaunchKernelGGL(k_pose_refine3<GROUPED>, dim3(n), dim3(R3_THREADS), 0, (hipStream_t)stream, ra);
     if ((g_last_hip_error = hipGetLastError()) != hipSuccess) return HC_ERROR_LAUNCH;
-    if (!best) return HC_SUCCESS;
-    if ((tv.bits & HC_THREEVIEW_SELECT_BY_TRANSFER) != 0)
-        hipLaunchKernelGGL(k_pose_topk_select_transfer3, dim3((num_groups + 63) / 64), dim3(64), 0,
-                           (hipStream_t)stream, num_groups, a.per_group, a.out, tv.reports, best, best_rank);
-    else
-        hipLaunchKernelGGL(k_pose_topk_select, dim3((num_groups + 63) / 64), dim3(64), 0, (hipStream_t)stream,
-                           num_groups, a.per_group, a.out, best, best_rank);
-    if ((g_last_hip_error = hipGetLastError()) != hipSuccess) return HC_ERROR_LAUNCH;
-    return HC_SUCCESS;
+    if (best) {
+        if ((tv.bits & HC_THREEVIEW_SELECT_BY_TRANSFER) != 0)
+            hipLaunchKernelGGL(k_pose_topk_select_transfer3, dim3((num_groups + 63) / 64), dim3(64), 0,
+                               (hipStream_t)stream, num_groups, a.per_group, a.out, tv.reports, best, best_rank);
+        else
+            hipLaunchKernelGGL(k_pose_topk_select, dim3((num_groups + 63) / 64), dim3(64), 0, (hipStream_t)stream,
+                               num_groups, a.per_group, a.out, best, best_rank);
+        if ((g_last_hip_error = hipGetLastError()) != hipSuccess) return HC_ERROR_LAUNCH;
+    }
+    if (!sm.on) return HC_SUCCESS;
+    return launch_structure<GROUPED>(a, sm, best ? best : a.out, nullptr, tv.scale_reports, best ? best_rank : nullptr,
+                                     num_groups, stream);
 }
 
 }  // namespace
@@ -1579,11 +1601,13 @@ extern "C" hcStatus hc_trifocal_pose_refine(const hcTrifocalSelection *in, int n
     int iterations, min_inliers;
     ScaleMode m;
     ThreeViewMode tv;
+    StructureMode sm;
     if (!in || num_edgels <= 0 || !locations || !K || !out || !refine_settings(settings, iterations, min_inliers) ||
-        !scale_mode(settings, false, true, m) || !threeview_mode(settings, false, true, tv))
+        !scale_mode(settings, false, true, m) || !threeview_mode(settings, false, true, tv) ||
+        !structure_mode(settings, false, false, sm, tv))
         return HC_ERROR_INVALID_VALUE;
     const RefineArgs a{in, out, report, num_edgels, locations, K, nullptr, iterations, min_inliers, 1};
-    return launch_refine_modes<false>(a, m, tv, 1, nullptr, nullptr, stream);
+    return launch_refine_modes<false>(a, m, tv, sm, 1, nullptr, nullptr, stream);
 }
 
 extern "C" hcStatus hc_trifocal_pose_refine_grouped(int num_groups, const hcTripletGroup *groups,
@@ -1594,11 +1618,13 @@ extern "C" hcStatus hc_trifocal_pose_refine_grouped(int num_groups, const hcTrip
     int iterations, min_inliers;
     ScaleMode m;
     ThreeViewMode tv;
+    StructureMode sm;
     if (num_groups <= 0 || !groups || !in || !out || !refine_settings(settings, iterations, min_inliers) ||
-        !scale_mode(settings, false, false, m) || !threeview_mode(settings, false, false, tv))
+        !scale_mode(settings, false, false, m) || !threeview_mode(settings, false, false, tv) ||
+        !structure_mode(settings, false, true, sm, tv))
         return HC_ERROR_INVALID_VALUE;
     const RefineArgs a{in, out, reports, 0, nullptr, nullptr, groups, iterations, min_inliers, 1};
-    return launch_refine_modes<true>(a, m, tv, num_groups, nullptr, nullptr, stream);
+    return launch_refine_modes<true>(a, m, tv, sm, num_groups, nullptr, nullptr, stream);
 }
 
 extern "C" hcStatus hc_trifocal_pose_topk_joint(int num_paths, const hcComplex *tracks, const int32_t *inliers, int k,
@@ -1632,12 +1658,13 @@ extern "C" hcStatus hc_trifocal_pose_refine_topk(int k, const hcTrifocalSelectio
     int iterations, min_inliers;
     ScaleMode m;
     ThreeViewMode tv;
+    StructureMode sm;
     if (k < 1 || k > HC_TOPK_MAX || !candidates || num_edgels <= 0 || !locations || !K || !refined || !best ||
         !best_rank || !refine_settings(settings, iterations, min_inliers) || !scale_mode(settings, true, false, m) ||
-        !threeview_mode(settings, true, false, tv))
+        !threeview_mode(settings, true, false, tv) || !structure_mode(settings, true, false, sm, tv))
         return HC_ERROR_INVALID_VALUE;
     const RefineArgs a{candidates, refined, reports, num_edgels, locations, K, nullptr, iterations, min_inliers, k};
-    return launch_refine_modes<false>(a, m, tv, 1, best, best_rank, stream);
+    return launch_refine_modes<false>(a, m, tv, sm, 1, best, best_rank, stream);
 }
 
 extern "C" hcStatus hc_trifocal_pose_refine_topk_grouped(int num_groups, const hcTripletGroup *groups, int k,
@@ -1650,10 +1677,12 @@ extern "C" hcStatus hc_trifocal_pose_refine_topk_grouped(int num_groups, const h
     int iterations, min_inliers;
     ScaleMode m;
     ThreeViewMode tv;
+    StructureMode sm;
     if (num_groups < 1 || num_groups > 0x7FFFFFFF / HC_TOPK_MAX || !groups || k < 1 || k > HC_TOPK_MAX ||
         !candidates || !refined || !best || !best_rank || !refine_settings(settings, iterations, min_inliers) ||
-        !scale_mode(settings, true, false, m) || !threeview_mode(settings, true, false, tv))
+        !scale_mode(settings, true, false, m) || !threeview_mode(settings, true, false, tv) ||
+        !structure_mode(settings, true, true, sm, tv))
         return HC_ERROR_INVALID_VALUE;
     const RefineArgs a{candidates, refined, reports, 0, nullptr, nullptr, groups, iterations, min_inliers, k};
-    return launch_refine_modes<true>(a, m, tv, num_groups, best, best_rank, stream);
+    return launch_refine_modes<true>(a, m, tv, sm, num_groups, best, best_rank, stream);
 }

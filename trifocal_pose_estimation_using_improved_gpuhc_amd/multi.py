@@ -67,6 +67,8 @@ class TripletBatch:
     sample_group (N,) int32; index[t]: the rows of triplet t, in its own order;
     sample_ordinal (N,) int32: a row's index among its own triplet's rows, in
     launch order (the adaptive sample limit compares it with the triplet's limit).
+    tangents[t]: the tangents of triplet t's scoring set, the first E rows of
+    its data's (E, 6), beside locations[t] (the structure stage reads them).
     """
 
     def __init__(self, problem: Problem, datas, seeds=0, samples_per_triplet=8, interleave: bool = False,
@@ -82,12 +84,13 @@ class TripletBatch:
         ecs = _per_triplet(edgel_counts, T, "edgel counts")
         self.datas = datas
         self.num_groups = T
-        self.locations, self.Ks = [], []
+        self.locations, self.Ks, self.tangents = [], [], []
         for t, (d, e) in enumerate(zip(datas, ecs)):
             E = d.locations.shape[0] if e is None else int(e)
             if E <= 0 or E > d.locations.shape[0]:
                 raise _abi.HCError(f"TripletBatch: triplet {t}: scoring set of {E} of {d.locations.shape[0]} edgels")
             self.locations.append(np.ascontiguousarray(d.locations[:E], np.float32))
+            self.tangents.append(np.ascontiguousarray(d.tangents[:E], np.float32))
             self.Ks.append(np.ascontiguousarray(d.K, np.float32).reshape(9))
         self.edgel_counts = np.array([l.shape[0] for l in self.locations], np.int32)
         parts = [prepare_target_params(problem, d, seed=int(s), num_samples=c) if c > 0 else
@@ -117,7 +120,9 @@ class TripletBatch:
 class DeviceTripletBatch:
     """Device copies of a TripletBatch: target, diff, the concatenated edgels
     (sum E, 6), K (T, 9), sample_group and sample_ordinal (N,) int32 and `groups`, the
-    hcTripletGroup array (T x 24 bytes) whose pointers go into edgels / K."""
+    hcTripletGroup array (T x 24 bytes) whose pointers go into edgels / K.
+    tangents (sum E, 6) is laid out as edgels; edgel_offsets (host, int64) and
+    edgel_offsets_device (int32) are every triplet's first row in both."""
 
     def __init__(self, batch: TripletBatch, device):
         import torch
@@ -134,6 +139,10 @@ class DeviceTripletBatch:
         self.sample_group = torch.from_numpy(batch.sample_group).to(dev)
         self.sample_ordinal = torch.from_numpy(batch.sample_ordinal).to(dev)
         self.edgel_offsets = np.concatenate([[0], np.cumsum(batch.edgel_counts[:-1], dtype=np.int64)]).astype(np.int64)
+        if int(batch.edgel_counts.astype(np.int64).sum()) > 0x7FFFFFFF:
+            raise _abi.HCError("DeviceTripletBatch: more than 2^31 - 1 edgels in all")
+        self.tangents = torch.from_numpy(np.ascontiguousarray(np.concatenate(batch.tangents))).to(dev)
+        self.edgel_offsets_device = torch.from_numpy(self.edgel_offsets.astype(np.int32)).to(dev)
         g = np.zeros(batch.num_groups, GROUP_DTYPE)
         g["locations"] = self.edgels.data_ptr() + self.edgel_offsets * 24     # E x 6 floats per triplet
         g["K"] = self.K.data_ptr() + np.arange(batch.num_groups, dtype=np.int64) * 36

@@ -35,6 +35,12 @@ jointly on the three-view transfer after the refinement and the scale fit
 (three_view and three_view_iterations on the refine wrappers; it implies
 fit_scale).
 
+Structure (not in the reference): a fourth stage of the same calls
+(include/structure/hc_pose_structure.h) writes the 3D edgels, point and
+tangent, that the pose that goes out explains in all three views (structure and
+tangents on the refine wrappers; it implies three_view; reconstruct is the
+structure-only form and write_edgels3d a text writer).
+
 The four pose-support calls (per view / joint, one triplet / grouped) share one
 launcher and one synchronous wrapper (_launch, _run), parameterised by a _Rule.
 Every native call goes through the signature table of _abi: buffers and streams
@@ -392,6 +398,83 @@ def _three_view_mode(settings, count: int, dev, three_view_iterations, transfer_
     return ts, scale, words, reports
 
 
+# ---- the 3D edgels, a further mode (include/structure/hc_pose_structure.h) ----
+EDGEL3D_BYTES = _abi.EDGEL3D_BYTES
+EDGEL3D_DTYPE = _abi.EDGEL3D_DTYPE
+STRUCTURE_REPORT_BYTES = _abi.STRUCTURE_REPORT_BYTES
+
+
+def structure_report_dict(raw) -> dict:
+    r = _struct_from_raw(_abi.hcStructureReport, STRUCTURE_REPORT_BYTES, raw)
+    return dict(status=r.status, none=bool(r.status & _abi.HC_STRUCTURE_NONE), count=r.count, tangents=r.tangents,
+                oriented=r.oriented, scale31=np.float32(r.scale31))
+
+
+def _structure_report_dicts(raw: torch.Tensor, count: int) -> list:
+    rows = raw.cpu().numpy().reshape(count, STRUCTURE_REPORT_BYTES)
+    return [structure_report_dict(r) for r in rows]
+
+
+def structure_records(edgels3d: torch.Tensor, report: dict, first: int = 0) -> np.ndarray:
+    """The report's first `count` hcEdgel3D of a device buffer, from entry
+    `first`, as a structured array (EDGEL3D_DTYPE)."""
+    rec = edgels3d.cpu().numpy().view(np.uint8).reshape(-1).view(EDGEL3D_DTYPE)
+    return rec[first:first + report["count"]].copy()
+
+
+def _check_structure(what: str, structure, tangents, min_sin_plane, max_sin3, three_view):
+    """The structure keywords of a refine wrapper, checked before anything
+    touches a device.  Returns three_view, which structure implies."""
+    if not isinstance(structure, (bool, np.bool_)):
+        raise _abi.HCError(f"{what}: structure must be a boolean")
+    if not structure:
+        if tangents is not None:
+            raise _abi.HCError(f"{what}: tangents need structure")
+        return three_view
+    if not isinstance(three_view, (bool, np.bool_)):
+        raise _abi.HCError(f"{what}: three_view must be a boolean")
+    for v in (min_sin_plane, max_sin3):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.floating)) or not 0.0 < float(v) <= 1.0:
+            raise _abi.HCError(f"{what}: min_sin_plane and max_sin3 must lie in (0, 1], not {v!r}")
+    return True
+
+
+def _structure_mode(ts, what: str, dev, tangents, num_edgels: int, min_sin_plane, max_sin3, groups: int = 1,
+                    edgel_offsets=None, edgels3d=None):
+    """An hcRefineStructureSettings around the three-view settings ts (None:
+    HC_STRUCTURE_ONLY), the tangents of num_edgels edgels in all, and new device
+    tensors for the records (unless edgels3d is given) and the `groups` reports.
+    Returns (settings, records (num_edgels * EDGEL3D_BYTES,) u8, reports)."""
+    if not isinstance(tangents, torch.Tensor) or tangents.dtype != torch.float32 or not tangents.is_cuda or \
+            not tangents.is_contiguous() or tangents.device != dev or tangents.numel() != 6 * num_edgels:
+        raise _abi.HCError(f"{what}: tangents must be a contiguous float32 ({num_edgels}, 6) tensor on the scene's device")
+    ss = _abi.hcRefineStructureSettings()
+    if ts is not None:
+        ss.tv = ts
+        bits = ts.head.pad[1]
+    else:
+        bits = _abi.HC_STRUCTURE_ONLY
+    ss.tv.head.pad[0], ss.tv.head.pad[1] = _abi.HC_REFINE_STRUCTURE, bits
+    if edgels3d is None:
+        edgels3d = torch.empty(num_edgels * EDGEL3D_BYTES, dtype=torch.uint8, device=dev)
+    if not edgels3d.is_cuda or not edgels3d.is_contiguous() or edgels3d.device != dev or \
+            edgels3d.numel() * edgels3d.element_size() < num_edgels * EDGEL3D_BYTES:
+        raise _abi.HCError(f"{what}: edgels3d must hold {num_edgels} hcEdgel3D on the scene's device")
+    reports = torch.empty(groups * STRUCTURE_REPORT_BYTES, dtype=torch.uint8, device=dev)
+    ss.tangents, ss.edgels3d, ss.reports = tangents.data_ptr(), edgels3d.data_ptr(), reports.data_ptr()
+    ss.edgel_offsets = edgel_offsets.data_ptr() if edgel_offsets is not None else None
+    ss.min_sin_plane, ss.max_sin3 = float(min_sin_plane), float(max_sin3)
+    return ss, edgels3d, reports
+
+
+def write_edgels3d(path: str, structure: np.ndarray) -> None:
+    """One text line per record: edgel X T err3_px sin_plane sin3 flags, floats as %.9g."""
+    with open(path, "w") as fh:
+        for r in np.asarray(structure, EDGEL3D_DTYPE).reshape(-1):
+            vals = [*r["X"], *r["T"], r["err3_px"], r["sin_plane"], r["sin3"]]
+            fh.write(f"{int(r['edgel'])} " + " ".join("%.9g" % float(v) for v in vals) + f" {int(r['flags'])}\n")
+
+
 def _scale_mode(settings, count: int, dev, what: str, fit_scale, transfer_mask=False, num_edgels=None,
                 select_by_transfer=False, scale_only=False):
     """The settings a refine call is given: `settings` itself with the mode off,
@@ -416,7 +499,9 @@ def _scale_mode(settings, count: int, dev, what: str, fit_scale, transfer_mask=F
 def launch_refine_joint(selection, edgels: torch.Tensor, K: torch.Tensor, iterations: int = 10,
                         min_inliers: int = 16, stream=None, out: torch.Tensor | None = None,
                         fit_scale: bool = False, transfer_mask: bool = False, _scale_only: bool = False,
-                        three_view: bool = False, three_view_iterations: int | None = None):
+                        three_view: bool = False, three_view_iterations: int | None = None,
+                        structure: bool = False, tangents: torch.Tensor | None = None, min_sin_plane: float = 0.05,
+                        max_sin3: float = 0.05, edgels3d: torch.Tensor | None = None, _structure_only: bool = False):
     """Enqueue hc_trifocal_pose_refine (no sync): the joint selection's pose
     fitted to its joint inliers among the E edgels, the inlier set recomputed at
     every iterate.  selection: the device bytes of an hcTrifocalSelection, or a
@@ -432,9 +517,16 @@ def launch_refine_joint(selection, edgels: torch.Tensor, K: torch.Tensor, iterat
     the three-view transfer for three_view_iterations steps (default 10;
     include/threeview/hc_pose_threeview.h).  It implies fit_scale; a fifth
     device tensor is returned, the three-view report (THREEVIEW_REPORT_BYTES,)
-    u8, and the transfer mask describes the pose and scale that went out."""
+    u8, and the transfer mask describes the pose and scale that went out.
+    structure: after the three-view stage, which it implies, the 3D edgels the
+    pose that went out explains are reconstructed from tangents (E, 6) f32
+    (include/structure/hc_pose_structure.h); two more device tensors follow, the
+    records (E * EDGEL3D_BYTES,) u8 (a new tensor unless edgels3d is given; the
+    report's count of them are written) and the structure report
+    (STRUCTURE_REPORT_BYTES,) u8."""
     what = "refine_joint"
     settings = _refine_settings(iterations, min_inliers, what)
+    three_view = _check_structure(what, structure, tangents, min_sin_plane, max_sin3, three_view)
     fit_scale = _check_three_view(what, three_view, three_view_iterations, fit_scale)
     _check_scale_flags(what, fit_scale, transfer_mask)
     dev = edgels.device
@@ -446,16 +538,25 @@ def launch_refine_joint(selection, edgels: torch.Tensor, K: torch.Tensor, iterat
         out = torch.empty(JOINT_SEL_BYTES, dtype=torch.uint8, device=dev)
     out = _device_selections(out, dev, 1, what)
     tv = None
-    if three_view:
+    if _structure_only:
+        scale = words = None
+        settings, rec, srep = _structure_mode(None, what, dev, tangents, int(edgels.shape[0]), min_sin_plane, max_sin3,
+                                              edgels3d=edgels3d)
+    elif three_view:
         settings, scale, words, tv = _three_view_mode(settings, 1, dev, three_view_iterations, transfer_mask,
                                                       int(edgels.shape[0]))
+        if structure:
+            settings, rec, srep = _structure_mode(settings, what, dev, tangents, int(edgels.shape[0]), min_sin_plane,
+                                                  max_sin3, edgels3d=edgels3d)
     else:
         settings, scale, words = _scale_mode(settings, 1, dev, what, fit_scale, transfer_mask, int(edgels.shape[0]),
                                              scale_only=_scale_only)
-    report = None if _scale_only else torch.empty(REPORT_BYTES, dtype=torch.uint8, device=dev)
+    report = None if _scale_only or _structure_only else torch.empty(REPORT_BYTES, dtype=torch.uint8, device=dev)
     _abi.call("hc_trifocal_pose_refine", _abi.ptr(selection), int(edgels.shape[0]), _abi.ptr(edgels), _abi.ptr(K),
               _settings_ptr(settings), _abi.ptr(out), _abi.ptr(report),
               _abi.ptr(stream if stream is not None else torch.cuda.current_stream(dev)))
+    if structure:
+        return out, report, scale, words, tv, rec, srep
     if three_view:
         return out, report, scale, words, tv
     return (out, report, scale, words) if fit_scale else (out, report)
@@ -470,18 +571,24 @@ def _scale_entry(scale: torch.Tensor, words) -> dict:
 
 def refine_joint(selection, edgels: torch.Tensor, K: torch.Tensor, iterations: int = 10, min_inliers: int = 16,
                  return_device_selection: bool = False, fit_scale: bool = False, transfer_mask: bool = False,
-                 three_view: bool = False, three_view_iterations: int | None = None):
+                 three_view: bool = False, three_view_iterations: int | None = None, structure: bool = False,
+                 tangents: torch.Tensor | None = None, min_sin_plane: float = 0.05, max_sin3: float = 0.05):
     """Synchronous wrapper: (refined selection dict, report dict), and with
     return_device_selection also the refined selection's device bytes.  With
     fit_scale the report dict has a "scale" entry, the scale report as a dict
     (with transfer_mask also its "mask", the packed uint64 words).  With
     three_view it has both "scale" (the vote's report) and "three_view" (the
-    three-view report as a dict, which then holds "mask")."""
+    three-view report as a dict, which then holds "mask").  With structure
+    (which implies three_view) it also has "structure", the structure report as
+    a dict, and the records follow the report dict: (selection dict, report
+    dict, structure), structure a structured array of EDGEL3D_DTYPE."""
     out, report, *rest = launch_refine_joint(selection, edgels, K, iterations, min_inliers, fit_scale=fit_scale,
                                              transfer_mask=transfer_mask, three_view=three_view,
-                                             three_view_iterations=three_view_iterations)
+                                             three_view_iterations=three_view_iterations, structure=structure,
+                                             tangents=tangents, min_sin_plane=min_sin_plane, max_sin3=max_sin3)
     torch.cuda.synchronize(edgels.device)
     rep = refine_report_dict(report)
+    three_view = three_view or structure
     if three_view:
         rep["scale"] = scale_report_dict(rest[0])
         rep["three_view"] = three_view_report_dict(rest[2])
@@ -490,7 +597,35 @@ def refine_joint(selection, edgels: torch.Tensor, K: torch.Tensor, iterations: i
     elif fit_scale:
         rep["scale"] = _scale_entry(*rest)
     res = (joint_selection_dict(joint_selection_struct(out)), rep)
+    if structure:
+        rep["structure"] = structure_report_dict(rest[4])
+        res = (*res, structure_records(rest[3], rep["structure"]))
     return (*res, out) if return_device_selection else res
+
+
+def launch_reconstruct(selection, edgels: torch.Tensor, tangents: torch.Tensor, K: torch.Tensor,
+                       min_sin_plane: float = 0.05, max_sin3: float = 0.05, stream=None,
+                       out: torch.Tensor | None = None, edgels3d: torch.Tensor | None = None):
+    """Enqueue the reconstruction alone (hc_trifocal_pose_refine with
+    HC_STRUCTURE_ONLY, no sync): nothing is refined or voted, the 3D edgels are
+    those of the selection's own pose and scale31.  Returns device tensors
+    (selection, a bit-for-bit copy; records (E * EDGEL3D_BYTES,) u8; structure
+    report (STRUCTURE_REPORT_BYTES,) u8)."""
+    o, *_, rec, srep = launch_refine_joint(selection, edgels, K, stream=stream, out=out, structure=True,
+                                           tangents=tangents, min_sin_plane=min_sin_plane, max_sin3=max_sin3,
+                                           edgels3d=edgels3d, _structure_only=True)
+    return o, rec, srep
+
+
+def reconstruct(selection, edgels: torch.Tensor, tangents: torch.Tensor, K: torch.Tensor, min_sin_plane: float = 0.05,
+                max_sin3: float = 0.05):
+    """The 3D edgels a selection's pose and scale31 explain, synchronous:
+    (structure, report): the report's count records in edgel order as a
+    structured array of EDGEL3D_DTYPE, and the structure report as a dict."""
+    _, rec, srep = launch_reconstruct(selection, edgels, tangents, K, min_sin_plane, max_sin3)
+    torch.cuda.synchronize(edgels.device)
+    report = structure_report_dict(srep)
+    return structure_records(rec, report), report
 
 
 def launch_fit_scale31(selection, edgels: torch.Tensor, K: torch.Tensor, transfer_mask: bool = False, stream=None,
@@ -512,7 +647,10 @@ def fit_scale31(selection, edgels: torch.Tensor, K: torch.Tensor, transfer_mask:
 
 def launch_refine_joint_grouped(selections, batch, iterations: int = 10, min_inliers: int = 16, stream=None,
                                 fit_scale: bool = False, transfer_mask: bool = False, three_view: bool = False,
-                                three_view_iterations: int | None = None):
+                                three_view_iterations: int | None = None, structure: bool = False,
+                                tangents: torch.Tensor | None = None, min_sin_plane: float = 0.05,
+                                max_sin3: float = 0.05, edgels3d: torch.Tensor | None = None,
+                                _structure_only: bool = False):
     """Enqueue hc_trifocal_pose_refine_grouped (no sync): selection t refined on
     triplet t of batch (a multi.DeviceTripletBatch).  selections: T selections
     as device bytes, or a list of dicts / structs, which is uploaded.  Returns
@@ -520,9 +658,13 @@ def launch_refine_joint_grouped(selections, batch, iterations: int = 10, min_inl
     with fit_scale also the scale reports (T * SCALE_REPORT_BYTES,) u8.  The
     grouped call writes no transfer mask: transfer_mask is refused.  With
     three_view (which implies fit_scale) a fourth tensor follows, the three-view
-    reports (T * THREEVIEW_REPORT_BYTES,) u8."""
+    reports (T * THREEVIEW_REPORT_BYTES,) u8.  With structure (which implies
+    three_view) two more follow: the records of all triplets (sum E *
+    EDGEL3D_BYTES,) u8, triplet t's from entry batch.edgel_offsets[t], and
+    the T structure reports.  tangents: the batch's own unless given."""
     what = "refine_joint_grouped"
     settings = _refine_settings(iterations, min_inliers, what)
+    three_view = _check_structure(what, structure, tangents, min_sin_plane, max_sin3, three_view)
     fit_scale = _check_three_view(what, three_view, three_view_iterations, fit_scale)
     _check_scale_flags(what, fit_scale, transfer_mask, mask_allowed=False)
     dev = batch.device
@@ -534,13 +676,22 @@ def launch_refine_joint_grouped(selections, batch, iterations: int = 10, min_inl
     out = torch.empty(T * JOINT_SEL_BYTES, dtype=torch.uint8, device=dev)
     reports = torch.empty(T * REPORT_BYTES, dtype=torch.uint8, device=dev)
     tv = None
-    if three_view:
+    sm = (what, dev, batch.tangents if tangents is None else tangents, int(batch.edgels.shape[0]), min_sin_plane,
+          max_sin3, T, batch.edgel_offsets_device, edgels3d) if structure else None
+    if _structure_only:
+        scale, reports = None, None
+        settings, rec, srep = _structure_mode(None, *sm)
+    elif three_view:
         settings, scale, _, tv = _three_view_mode(settings, T, dev, three_view_iterations)
+        if structure:
+            settings, rec, srep = _structure_mode(settings, *sm)
     else:
         settings, scale, _ = _scale_mode(settings, T, dev, what, fit_scale, transfer_mask)
     _abi.call("hc_trifocal_pose_refine_grouped", T, _abi.ptr(batch.groups), _abi.ptr(selections),
               _settings_ptr(settings), _abi.ptr(out), _abi.ptr(reports),
               _abi.ptr(stream if stream is not None else torch.cuda.current_stream(dev)))
+    if structure:
+        return out, reports, scale, tv, rec, srep
     if three_view:
         return out, reports, scale, tv
     return (out, reports, scale) if fit_scale else (out, reports)
@@ -548,11 +699,15 @@ def launch_refine_joint_grouped(selections, batch, iterations: int = 10, min_inl
 
 def refine_joint_grouped(selections, batch, iterations: int = 10, min_inliers: int = 16, device=None,
                          fit_scale: bool = False, transfer_mask: bool = False, three_view: bool = False,
-                         three_view_iterations: int | None = None):
+                         three_view_iterations: int | None = None, structure: bool = False,
+                         tangents: torch.Tensor | None = None, min_sin_plane: float = 0.05, max_sin3: float = 0.05):
     """Synchronous wrapper: ([refined selection dict] * T, [report dict] * T).
     batch: a multi.TripletBatch (copied to device, or to the selections' device)
     or a multi.DeviceTripletBatch.  With fit_scale every report dict has a
-    "scale" entry, with three_view also a "three_view" entry."""
+    "scale" entry, with three_view also a "three_view" entry.  With structure
+    (which implies three_view) also a "structure" entry, and a third list
+    follows, every triplet's records."""
+    three_view = _check_structure("refine_joint_grouped", structure, tangents, min_sin_plane, max_sin3, three_view)
     fit_scale = _check_three_view("refine_joint_grouped", three_view, three_view_iterations, fit_scale)
     _check_scale_flags("refine_joint_grouped", fit_scale, transfer_mask, mask_allowed=False)
     if not hasattr(batch, "groups"):
@@ -561,7 +716,8 @@ def refine_joint_grouped(selections, batch, iterations: int = 10, min_inliers: i
         batch = batch.to(device)
     out, reports, *rest = launch_refine_joint_grouped(selections, batch, iterations, min_inliers, fit_scale=fit_scale,
                                                       transfer_mask=transfer_mask, three_view=three_view,
-                                                      three_view_iterations=three_view_iterations)
+                                                      three_view_iterations=three_view_iterations, structure=structure,
+                                                      tangents=tangents, min_sin_plane=min_sin_plane, max_sin3=max_sin3)
     torch.cuda.synchronize(batch.device)
     T = batch.num_groups
     sels = out.cpu().numpy().reshape(T, JOINT_SEL_BYTES)
@@ -572,7 +728,41 @@ def refine_joint_grouped(selections, batch, iterations: int = 10, min_inliers: i
     if three_view:
         for r, s in zip(reps, _three_view_report_dicts(rest[1], T)):
             r["three_view"] = s
-    return [joint_selection_dict(joint_selection_struct(r)) for r in sels], reps
+    dicts = [joint_selection_dict(joint_selection_struct(r)) for r in sels]
+    if structure:
+        for r, s in zip(reps, _structure_report_dicts(rest[3], T)):
+            r["structure"] = s
+        return dicts, reps, _group_records(rest[2], reps, batch)
+    return dicts, reps
+
+
+def _group_records(edgels3d: torch.Tensor, structure_reports, batch) -> list:
+    """Every triplet's records of a grouped call; structure_reports: dicts with
+    a "structure" entry, or structure report dicts."""
+    rec = edgels3d.cpu().numpy().view(np.uint8).reshape(-1).view(EDGEL3D_DTYPE)
+    offs = batch.edgel_offsets
+    return [rec[int(o):int(o) + r.get("structure", r)["count"]].copy() for o, r in zip(offs, structure_reports)]
+
+
+def launch_reconstruct_grouped(selections, batch, tangents: torch.Tensor | None = None, min_sin_plane: float = 0.05,
+                               max_sin3: float = 0.05, stream=None, edgels3d: torch.Tensor | None = None):
+    """launch_reconstruct for every triplet of batch (a
+    multi.DeviceTripletBatch) in one call, hc_trifocal_pose_refine_grouped with
+    HC_STRUCTURE_ONLY (no sync).  Returns device tensors (selections, copied bit
+    for bit; the records of all triplets; the T structure reports)."""
+    o, *_, rec, srep = launch_refine_joint_grouped(selections, batch, stream=stream, structure=True,
+                                                   tangents=tangents, min_sin_plane=min_sin_plane,
+                                                   max_sin3=max_sin3, edgels3d=edgels3d, _structure_only=True)
+    return o, rec, srep
+
+
+def reconstruct_grouped(selections, batch, tangents: torch.Tensor | None = None, min_sin_plane: float = 0.05,
+                        max_sin3: float = 0.05):
+    """Synchronous: ([structure] * T, [report dict] * T)."""
+    _, rec, srep = launch_reconstruct_grouped(selections, batch, tangents, min_sin_plane, max_sin3)
+    torch.cuda.synchronize(batch.device)
+    reports = _structure_report_dicts(srep, batch.num_groups)
+    return _group_records(rec, reports, batch), reports
 
 
 def merge_joint(parts: list, path_offsets: list) -> dict:
@@ -671,16 +861,21 @@ def topk_joint_grouped(tracks: torch.Tensor, inliers: torch.Tensor, batch, k: in
 
 
 def _launch_refine_topk(what, candidates, k, scene, iterations, min_inliers, stream, refined, fit_scale=False,
-                        transfer_mask=False, select_by_transfer=False, three_view=False, three_view_iterations=None):
+                        transfer_mask=False, select_by_transfer=False, three_view=False, three_view_iterations=None,
+                        structure=False, tangents=None, min_sin_plane=0.05, max_sin3=0.05):
     """scene: (edgels, K) or a multi.DeviceTripletBatch.  With fit_scale the
     returned tuple has a fifth tensor, the T * k scale reports, and, when
     transfer_mask is set, a sixth: the transfer mask of best (the single-scene
     call only), written by a scale-only fit of best on the same stream.  With
     three_view the tuple is (best, best_rank, refined, reports, scale reports,
     three-view reports); a transfer mask is then refused (the scale-only fit of
-    best would vote its scale again)."""
+    best would vote its scale again).  With structure (which implies
+    three_view) two more tensors follow: the records of best (one scene: E;
+    grouped: sum E, triplet t's from entry edgel_offsets[t]) and the T structure
+    reports."""
     k = _check_k(k, what)
     settings = _refine_settings(iterations, min_inliers, what)
+    three_view = _check_structure(what, structure, tangents, min_sin_plane, max_sin3, three_view)
     fit_scale = _check_three_view(what, three_view, three_view_iterations, fit_scale)
     if three_view and transfer_mask is True:
         raise _abi.HCError(f"{what}: with three_view the transfer mask is written by refine_joint only")
@@ -701,6 +896,13 @@ def _launch_refine_topk(what, candidates, k, scene, iterations, min_inliers, str
     if three_view:
         settings, scale, _, tv = _three_view_mode(settings, T * k, dev, three_view_iterations,
                                                   select_by_transfer=select_by_transfer)
+        if structure and grouped:
+            settings, rec, srep = _structure_mode(settings, what, dev, scene.tangents if tangents is None else tangents,
+                                                  int(scene.edgels.shape[0]), min_sin_plane, max_sin3, T,
+                                                  scene.edgel_offsets_device)
+        elif structure:
+            settings, rec, srep = _structure_mode(settings, what, dev, tangents, int(scene[0].shape[0]),
+                                                  min_sin_plane, max_sin3)
     else:
         settings, scale, _ = _scale_mode(settings, T * k, dev, what, fit_scale, select_by_transfer=select_by_transfer)
     s = _abi.ptr(stream if stream is not None else torch.cuda.current_stream(dev))
@@ -715,6 +917,8 @@ def _launch_refine_topk(what, candidates, k, scene, iterations, min_inliers, str
                 raise _abi.HCError(f"{what}: buffers must be contiguous tensors on one device")
         _abi.call("hc_trifocal_pose_refine_topk", k, _abi.ptr(candidates), int(scene[0].shape[0]), _abi.ptr(scene[0]),
                   _abi.ptr(scene[1]), _settings_ptr(settings), *out)
+    if structure:
+        return best, best_rank, refined, reports, scale, tv, rec, srep
     if three_view:
         return best, best_rank, refined, reports, scale, tv
     if not fit_scale:
@@ -743,7 +947,8 @@ def _topk_count(candidates, what: str) -> int:
 def launch_refine_topk(candidates, edgels: torch.Tensor, K: torch.Tensor, iterations: int = 10, min_inliers: int = 16,
                        stream=None, refined: torch.Tensor | None = None, fit_scale: bool = False,
                        transfer_mask: bool = False, select_by_transfer: bool = False, three_view: bool = False,
-                       three_view_iterations: int | None = None):
+                       three_view_iterations: int | None = None, structure: bool = False,
+                       tangents: torch.Tensor | None = None, min_sin_plane: float = 0.05, max_sin3: float = 0.05):
     """Enqueue hc_trifocal_pose_refine_topk (no sync): every candidate refined
     on the E edgels as launch_refine_joint refines it, in one launch, and the
     refined selection with the most joint inliers (ties -> the larger batch id)
@@ -761,13 +966,17 @@ def launch_refine_topk(candidates, edgels: torch.Tensor, K: torch.Tensor, iterat
     (include/threeview/hc_pose_threeview.h; it implies fit_scale); the tuple is
     then (best, best_rank, refined, reports, scale reports, three-view reports
     (k * THREEVIEW_REPORT_BYTES,) u8), best is chosen by the final joint key, or
-    with select_by_transfer by the final transfer_inliers << 32 | path."""
+    with select_by_transfer by the final transfer_inliers << 32 | path.
+    structure (which implies three_view): the 3D edgels of best, after the
+    selection, from tangents (E, 6) f32; two more tensors follow, the records
+    (E * EDGEL3D_BYTES,) u8 and the structure report."""
     what = "refine_topk"
     _refine_settings(iterations, min_inliers, what)
-    _check_three_view(what, three_view, three_view_iterations, fit_scale)
+    _check_three_view(what, _check_structure(what, structure, tangents, min_sin_plane, max_sin3, three_view),
+                      three_view_iterations, fit_scale)
     return _launch_refine_topk(what, candidates, _topk_count(candidates, what), (edgels, K), iterations, min_inliers,
                                stream, refined, fit_scale, transfer_mask, select_by_transfer, three_view,
-                               three_view_iterations)
+                               three_view_iterations, structure, tangents, min_sin_plane, max_sin3)
 
 
 def _refine_topk_dicts(best, best_rank, refined, reports, T, k, scale=None, words=None, three_view=None):
@@ -789,45 +998,62 @@ def _refine_topk_dicts(best, best_rank, refined, reports, T, k, scale=None, word
 
 def refine_topk(candidates, edgels: torch.Tensor, K: torch.Tensor, iterations: int = 10, min_inliers: int = 16,
                 fit_scale: bool = False, transfer_mask: bool = False, select_by_transfer: bool = False,
-                three_view: bool = False, three_view_iterations: int | None = None):
+                three_view: bool = False, three_view_iterations: int | None = None, structure: bool = False,
+                tangents: torch.Tensor | None = None, min_sin_plane: float = 0.05, max_sin3: float = 0.05):
     """Synchronous wrapper: (best dict, best_rank, [refined dict] * k, [report dict] * k).
     With fit_scale every report dict has a "scale" entry; with transfer_mask
     best's entry (reports[best_rank]["scale"]) also has "mask", the packed words.
-    With three_view every report dict also has a "three_view" entry."""
+    With three_view every report dict also has a "three_view" entry.  With
+    structure (which implies three_view) two more values follow: best's
+    structure report as a dict and its records."""
     out = launch_refine_topk(candidates, edgels, K, iterations, min_inliers, fit_scale=fit_scale,
                              transfer_mask=transfer_mask, select_by_transfer=select_by_transfer,
-                             three_view=three_view, three_view_iterations=three_view_iterations)
+                             three_view=three_view, three_view_iterations=three_view_iterations, structure=structure,
+                             tangents=tangents, min_sin_plane=min_sin_plane, max_sin3=max_sin3)
     torch.cuda.synchronize(edgels.device)
-    d = _refine_topk_dicts(*out[:4], 1, _topk_count(candidates, "refine_topk"), *_topk_extra(out, three_view))[0]
+    d = _refine_topk_dicts(*out[:4], 1, _topk_count(candidates, "refine_topk"),
+                           *_topk_extra(out, three_view or structure))[0]
     if "transfer_mask" in d and d["best_rank"] >= 0:
         d["reports"][d["best_rank"]]["scale"]["mask"] = d["transfer_mask"]
+    if structure:
+        srep = structure_report_dict(out[7])
+        return d["best"], d["best_rank"], d["refined"], d["reports"], srep, structure_records(out[6], srep)
     return d["best"], d["best_rank"], d["refined"], d["reports"]
 
 
 def launch_refine_topk_grouped(candidates, batch, k: int, iterations: int = 10, min_inliers: int = 16, stream=None,
                                refined: torch.Tensor | None = None, fit_scale: bool = False,
                                transfer_mask: bool = False, select_by_transfer: bool = False,
-                               three_view: bool = False, three_view_iterations: int | None = None):
+                               three_view: bool = False, three_view_iterations: int | None = None,
+                               structure: bool = False, tangents: torch.Tensor | None = None,
+                               min_sin_plane: float = 0.05, max_sin3: float = 0.05):
     """Enqueue hc_trifocal_pose_refine_topk_grouped (no sync): candidates
     [t * k + r] refined on triplet t of batch (a multi.DeviceTripletBatch), one
     selection per triplet.  Returns (best (T * JOINT_SEL_BYTES,) u8, best_rank
     (T,) i32, refined, reports), and with fit_scale also the T * k scale reports
     (select_by_transfer as in launch_refine_topk; transfer_mask is refused);
-    with three_view the scale reports and the T * k three-view reports."""
+    with three_view the scale reports and the T * k three-view reports; with
+    structure (which implies three_view; tangents: the batch's own unless given)
+    also the records of every triplet's best and the T structure reports."""
     _check_k(k, "refine_topk_grouped")
     return _launch_refine_topk("refine_topk_grouped", candidates, k, batch, iterations, min_inliers, stream, refined,
-                               fit_scale, transfer_mask, select_by_transfer, three_view, three_view_iterations)
+                               fit_scale, transfer_mask, select_by_transfer, three_view, three_view_iterations,
+                               structure, tangents, min_sin_plane, max_sin3)
 
 
 def refine_topk_grouped(candidates, batch, k: int, iterations: int = 10, min_inliers: int = 16, device=None,
                         fit_scale: bool = False, transfer_mask: bool = False, select_by_transfer: bool = False,
-                        three_view: bool = False, three_view_iterations: int | None = None):
+                        three_view: bool = False, three_view_iterations: int | None = None, structure: bool = False,
+                        tangents: torch.Tensor | None = None, min_sin_plane: float = 0.05, max_sin3: float = 0.05):
     """Synchronous wrapper: per triplet a dict(best, best_rank, refined, reports)
     of dicts.  batch: a multi.TripletBatch (copied to device, or to the
     candidates' device) or a multi.DeviceTripletBatch.  With fit_scale every
-    report dict has a "scale" entry, with three_view also a "three_view" entry."""
+    report dict has a "scale" entry, with three_view also a "three_view" entry.
+    With structure (which implies three_view) every triplet's dict also has
+    "structure_report" and "structure", those of its best."""
     _check_k(k, "refine_topk_grouped")
     _refine_settings(iterations, min_inliers, "refine_topk_grouped")
+    three_view = _check_structure("refine_topk_grouped", structure, tangents, min_sin_plane, max_sin3, three_view)
     _check_scale_flags("refine_topk_grouped", _check_three_view("refine_topk_grouped", three_view,
                                                                  three_view_iterations, fit_scale),
                        transfer_mask, select_by_transfer, mask_allowed=False)
@@ -837,9 +1063,16 @@ def refine_topk_grouped(candidates, batch, k: int, iterations: int = 10, min_inl
         batch = batch.to(device)
     out = launch_refine_topk_grouped(candidates, batch, k, iterations, min_inliers, fit_scale=fit_scale,
                                      transfer_mask=transfer_mask, select_by_transfer=select_by_transfer,
-                                     three_view=three_view, three_view_iterations=three_view_iterations)
+                                     three_view=three_view, three_view_iterations=three_view_iterations,
+                                     structure=structure, tangents=tangents, min_sin_plane=min_sin_plane,
+                                     max_sin3=max_sin3)
     torch.cuda.synchronize(batch.device)
-    return _refine_topk_dicts(*out[:4], batch.num_groups, k, *_topk_extra(out, three_view))
+    res = _refine_topk_dicts(*out[:4], batch.num_groups, k, *_topk_extra(out, three_view))
+    if structure:
+        sreps = _structure_report_dicts(out[7], batch.num_groups)
+        for d, r, rec in zip(res, sreps, _group_records(out[6], sreps, batch)):
+            d["structure_report"], d["structure"] = r, rec
+    return res
 
 
 def merge_topk(parts: list, path_offsets: list, k: int) -> list:
@@ -869,7 +1102,8 @@ def merge_topk(parts: list, path_offsets: list, k: int) -> list:
 def select_refined(tracks: torch.Tensor, converge: torch.Tensor, edgels: torch.Tensor, K: torch.Tensor, k: int = 8,
                    iterations: int = 10, min_inliers: int = 16, stream=None, fit_scale: bool = False,
                    transfer_mask: bool = False, select_by_transfer: bool = False, three_view: bool = False,
-                   three_view_iterations: int | None = None):
+                   three_view_iterations: int | None = None, structure: bool = False,
+                   tangents: torch.Tensor | None = None, min_sin_plane: float = 0.05, max_sin3: float = 0.05):
     """Joint pose support, the k best candidates, their refinement and the
     selection among the refined ones, enqueued on one stream with a single
     synchronisation at the end.  Returns (best dict, info); info: joint (the
@@ -879,10 +1113,13 @@ def select_refined(tracks: torch.Tensor, converge: torch.Tensor, edgels: torch.T
     own (None without a best; with transfer_mask it holds "mask");
     select_by_transfer as in launch_refine_topk.  With three_view (which
     implies fit_scale) every report also has a "three_view" entry and info has
-    three_view, best's own (None without a best); a transfer mask is refused."""
+    three_view, best's own (None without a best); a transfer mask is refused.
+    With structure (which implies three_view) info has structure_report, the
+    structure report of best as a dict, and structure, its records."""
     what = "select_refined"
     k = _check_k(k, what)
     _refine_settings(iterations, min_inliers, what)
+    three_view = _check_structure(what, structure, tangents, min_sin_plane, max_sin3, three_view)
     fit_scale = _check_three_view(what, three_view, three_view_iterations, fit_scale)
     _check_scale_flags(what, fit_scale, transfer_mask, select_by_transfer)
     if three_view and transfer_mask:
@@ -896,7 +1133,8 @@ def select_refined(tracks: torch.Tensor, converge: torch.Tensor, edgels: torch.T
     cand = launch_topk_joint(tracks, inl, k, stream=stream)
     out = launch_refine_topk(cand, edgels, K, iterations, min_inliers, stream, fit_scale=fit_scale,
                              transfer_mask=transfer_mask, select_by_transfer=select_by_transfer,
-                             three_view=three_view, three_view_iterations=three_view_iterations)
+                             three_view=three_view, three_view_iterations=three_view_iterations, structure=structure,
+                             tangents=tangents, min_sin_plane=min_sin_plane, max_sin3=max_sin3)
     stream.synchronize()
     d = _refine_topk_dicts(*out[:4], 1, k, *_topk_extra(out, three_view))[0]
     info = dict(joint=joint_selection_dict(joint_selection_struct(sel)), best_rank=d["best_rank"],
@@ -910,6 +1148,9 @@ def select_refined(tracks: torch.Tensor, converge: torch.Tensor, edgels: torch.T
                 info["scale"]["mask"] = d["transfer_mask"]
     if three_view:
         info["three_view"] = dict(d["reports"][d["best_rank"]]["three_view"]) if d["best_rank"] >= 0 else None
+    if structure:
+        info["structure_report"] = structure_report_dict(out[7])
+        info["structure"] = structure_records(out[6], info["structure_report"])
     return d["best"], info
 
 
