@@ -654,14 +654,15 @@ void hc_trifocal_set_small_launch(int mode) {
 void hc_trifocal_set_retry_reuse(int on) { hc::g_retry_reuse.store(on ? 1 : 0, std::memory_order_relaxed); }
 
 const char *hc_trifocal_version(void) {
-    return "hc_trifocal gfx950 v10.10 (2 paths/wave, structurally sparse LDS-broadcast LU with lean pivot steps fused by level, "
+    return "hc_trifocal gfx950 v10.11 (2 paths/wave, structurally sparse LDS-broadcast LU with lean pivot steps fused by level, "
            "one exec region per pivot step for the eligible rows with the column groups through scratch windows, "
            "column groups by structural class (never-fillable groups untested, always-live groups unconditional), "
            "pivot search narrowed to the candidate rows' DPP group "
            "(abort kernel and tracking launches filling at most half of the path slots -- the latter at 3 waves/SIMD, "
            "16 columns per batch: batched latency mode, one LDS round trip per pivot step, every live-able column "
            "group untested), "
-           "structure-agnostic twin kernels for other dH/dx structures, readlane back substitution, pipelined evals over "
+           "structure-agnostic twin kernels for other dH/dx structures, readlane back substitution (the throughput "
+           "kernel's fused positions level by level through LDS), pipelined evals over "
            "per-slot prefix tables, 5 waves/SIMD, time slicing at step boundaries with least-attained-service "
            "issue priority, a rejected step's retry reuses its first RK4 slope, the throughput kernel's operand "
            "addresses read complete from per-slot tables and its finiteness check made on the dH/dx entries)";

@@ -10,7 +10,7 @@
 //                     the three pivot steps (batched, tested, dense), the pivot
 //                     search (lu_forward), the back substitution, lu_solve and
 //                     which solve each tracking kernel runs (lu_mode)
-//   hc_lu_levels.hpp  the fused levels (lu_level), included below the primitives
+//   hc_lu_levels.hpp  the fused levels (lu_level, lu_back_level), included below the primitives
 //
 // Semantics: magmaHC/dev-cgesv-batched-small.cuh:38-107 -- partial pivoting
 // on cabs1 = |re| + |im| with first-maximum ties (the pivot search scans the
@@ -683,9 +683,11 @@ __device__ __forceinline__ void lu_forward_fused(cf (&rA)[NV], cf &rB, int &rowi
 // no LDS redistribution at the end).  The owner's rB is final at its step
 // (every step J > I has updated it) and dead after it, so the later steps
 // J < I may update it unmasked.
-template <int I>
+// LAST: the position the walk ends with (18 in lu_solve<..., FUSE>, whose
+// positions 17..0 run level by level: lu_backward_fused, hc_lu_levels.hpp).
+template <int I, int LAST = 0>
 __device__ __forceinline__ void lu_backward(const cf (&rA)[NV], cf &rB, int rowid, const PivF &my, pf2 &res) {
-    if constexpr (I >= 0) {
+    if constexpr (I >= LAST) {
         HC_ISA_MARK_I("lu_back", I);
         const unsigned long long own = __builtin_amdgcn_ballot_w64(rowid == I);
         const int o0 = __builtin_ctz((unsigned)own);          // one owner per half
@@ -712,7 +714,7 @@ __device__ __forceinline__ void lu_backward(const cf (&rA)[NV], cf &rB, int rowi
             const pf2 w = pcmsub(pf2{rB.x, rB.y}, xv, pf2{rA[I].x, rA[I].y});
             rB = cmk(w.x, w.y);
         }
-        lu_backward<I - 1>(rA, rB, rowid, my, res);
+        lu_backward<I - 1, LAST>(rA, rB, rowid, my, res);
     }
 }
 
@@ -745,8 +747,10 @@ constexpr LuMode lu_mode(bool ABORT, bool ARCH, int LULAT, bool LUS) {
 // the rows from (eval_hx_terms_abs) and passes the wave-uniform verdict in
 // ent_bad; the row loop below is left out.
 // FUSE (the throughput tracker's solve): the fusable steps run level by level
-// (lu_forward_fused); scratch then has LU_SCRATCH_FUSED_CF entries, and a
-// rare condition inside a level reports `redo` as well.
+// (lu_forward_fused), and so do their positions of the back substitution
+// (lu_backward_fused); scratch then has LU_SCRATCH_FUSED_CF entries, and a
+// rare condition inside a level or a solution that is not finite reports
+// `redo` as well.
 // count_mask: diagnostic builds (HC_DIAG_LUWORK), the lanes whose executed
 // work is counted; call sites pass HC_LU_COUNT(mask).
 template <bool DENSE, int LAT = 0, bool STRUCT = false, bool ENTCHK = false, bool FUSE = false>
@@ -818,7 +822,26 @@ __device__ __forceinline__ cf lu_solve(cf (&rA)[NV], cf rB, int lane, uint32_t p
     // lane r returns x_r (captured at back-substitution step r; padding lanes 0)
     HC_ISA_MARK("lu_back_init");
     pf2 res = {0.0f, 0.0f};
-    lu_backward<NV - 1>(rA, rB, rowid, my, res);
+    if constexpr (FUSE) {
+        lu_backward<NV - 1, lu_first_unfused_step()>(rA, rB, rowid, my, res);
+        lu_backward_fused<LU_LEVELS.nlevels - 1>(rA, rB, rowid, my, L, r, res);
+        // the levels skip the rows that take x_J * 0, which is a zero only for
+        // a finite x_J: a solve with a non-finite x goes to the dense one
+        // (padding lanes return 0)
+        const float nf = __builtin_fmaf(res.y, 0.0f, res.x * 0.0f);   // NaN unless both parts are finite
+        redo = __builtin_amdgcn_ballot_w64(nf != nf) != 0ull;
+#ifdef HC_DIAG_LUWORK
+        if (lane == 0 && redo) {   // not a completed sparse solve after all: its counts are taken back
+            atomicAdd(&g_diag_luwork[0], 0ull - lu_work_acc.acc);
+            atomicAdd(&g_diag_luwork[1], 0ull - solves);
+            atomicAdd(&g_diag_luwork[3], 0ull - 1ull);
+            atomicAdd(&g_diag_luwork[4], 0ull - lu_work_acc.groups);
+            atomicAdd(&g_diag_luwork[5], 0ull - lu_work_acc.rare);
+        }
+#endif
+    } else {
+        lu_backward<NV - 1>(rA, rB, rowid, my, res);
+    }
     return cmk(res.x, res.y);
 }
 

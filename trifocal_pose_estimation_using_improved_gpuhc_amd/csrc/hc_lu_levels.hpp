@@ -170,4 +170,78 @@ __device__ __forceinline__ bool lu_level(cf (&rA)[NV], cf &rB, int &rowid, uint3
     return true;
 }
 
+// ---------------------------------------------- the back substitution by level
+// Positions 0..17 of the back substitution, one step per level, from the top
+// level down (lu_solve<..., FUSE>, after the sequential positions 29..18).  A
+// row pivoted at a fused step I holds a non-zero in a column J, I < J <= 17, only
+// where J is an ancestor of I in the forest (lu_back_chains_nested,
+// hc_lu_struct.hpp), and every lane has at most one member per level, so a lane
+// does for its own chain's column what lu_backward<I> does for column I:
+//  * select: its entry in the member's column, on the static lane masks of
+//    lvl_pick, and the member's position;
+//  * divide: cuCdivf(b, pivot) with the factors it kept, once per level; the
+//    owner's (the lane whose label is its member: its b is final, every
+//    position above 17 and every ancestor has updated it) is x_I;
+//  * broadcast: the owner writes x_I into its half's buffer at row[I] (free
+//    since the forward elimination ended);
+//  * update: every lane of the level's rows reads the x of its own member and
+//    takes b -= x * a.  Rows at later positions are solved, so they update
+//    unmasked as in lu_backward; lanes without a member at the level keep their
+//    b (it may still be waiting for a lower level).  The rows outside the
+//    member's chain, which the sequential substitution updates with x_I * 0, are
+//    skipped: equal up to the sign of a zero while x_I is finite, and lu_solve
+//    hands a solve with a non-finite x to the dense one (equivalence 5 of
+//    DESIGN.md §4).  Along a row's ancestors the column rises with the level
+//    (lu_back_order_kept), so its non-zero updates keep the descending order.
+// Level 0 has nothing left to update: after its broadcast the lanes r < 18 read
+// the x_r they return.
+template <int LV, int K>
+__device__ __forceinline__ void lvl_back_pick(const cf (&rA)[NV], pf2 &c, int &mem) {
+    if constexpr (K < lu_level_count(LV)) {
+        constexpr int I = lu_level_member(LV, K);
+        if constexpr (K == 0) {   // (lanes outside the level: never owners, masked off the update)
+            c = pf2{rA[I].x, rA[I].y};
+            mem = I;
+        } else {
+            const bool in = __builtin_amdgcn_inverse_ballot_w64(lu_both(LU_BOUND.cand[I]));
+            c.x = in ? rA[I].x : c.x;
+            c.y = in ? rA[I].y : c.y;
+            mem = in ? I : mem;
+        }
+        lvl_back_pick<LV, K + 1>(rA, c, mem);
+    }
+}
+template <int LV>
+__device__ __forceinline__ void lu_back_level(const cf (&rA)[NV], cf &rB, int rowid, const PivF &my, LUBuf &L) {
+    HC_ISA_MARK_I("lu_back_level", LV);
+    pf2 c;
+    int mem;
+    lvl_back_pick<LV, 0>(rA, c, mem);
+    const pf2 q = pcdiv_apply(pf2{rB.x, rB.y}, c, my);
+    if (rowid == mem) L.row[mem] = cmk(q.x, q.y);   // mem is one of the level's members: inside row[0..17]
+    wave_lds_sync();
+    if constexpr (LV > 0) {
+        if (__builtin_amdgcn_inverse_ballot_w64(lu_both(LU_LEVELS.rows[LV]))) {
+            const cf x = L.row[mem];
+            const pf2 w = pcmsub(pf2{rB.x, rB.y}, pf2{x.x, x.y}, c);
+            rB = cmk(w.x, w.y);
+        }
+    }
+}
+// levels LV .. 0, then x_r into the lanes r < 18 (lanes 18..29 hold theirs from
+// the sequential positions)
+template <int LV>
+__device__ __forceinline__ void lu_backward_fused(const cf (&rA)[NV], cf &rB, int rowid, const PivF &my, LUBuf &L, int r,
+                                                  pf2 &res) {
+    if constexpr (LV >= 0) {
+        lu_back_level<LV>(rA, rB, rowid, my, L);
+        lu_backward_fused<LV - 1>(rA, rB, rowid, my, L, r, res);
+    } else {
+        if (__builtin_amdgcn_inverse_ballot_w64(lu_both(lu_fused_steps()))) {
+            const cf x = L.row[r];
+            res = pf2{x.x, x.y};
+        }
+    }
+}
+
 }  // namespace hc

@@ -160,6 +160,33 @@ constexpr bool lu_levels_ordered() {   // a fused step's dependencies are fused 
                 !(lu_step_fusable(i) && LU_LEVELS.level[i] < LU_LEVELS.level[j])) return false;
     return true;
 }
+// The back substitution of the fused positions, level by level (lu_back_level,
+// hc_lu_levels.hpp).  The row pivoted at a fused step I lies within LU_BOUND.s[I]
+// above the diagonal, and a column J of that bound with J <= 17 is an ancestor
+// of I: every candidate row of I is a candidate row of J, on a higher level.
+// So x_J reaches every row it can change through the lanes of cand[J] alone.
+constexpr bool lu_back_chains_nested() {
+    for (int i = 0; i < NV; i++)
+        for (int j = i + 1; j < NV; j++)
+            if (lu_step_fusable(i) && lu_step_fusable(j) && ((LU_BOUND.s[i] >> j) & 1u) &&
+                !((LU_BOUND.cand[i] & ~LU_BOUND.cand[j]) == 0u && LU_LEVELS.level[i] < LU_LEVELS.level[j])) return false;
+    return true;
+}
+// Along the fused steps a row is a candidate of -- one per level
+// (lu_levels_disjoint) -- the column rises with the level: walking the levels
+// downwards gives a row its non-zero updates in the reference's descending order.
+constexpr bool lu_back_order_kept() {
+    for (int r = 0; r < NV; r++) {
+        int last = -1;
+        for (int l = 0; l < NV; l++)
+            for (int i = 0; i < NV; i++)
+                if (lu_step_fusable(i) && LU_LEVELS.level[i] == l && ((LU_BOUND.cand[i] >> r) & 1u)) {
+                    if (i <= last) return false;
+                    last = i;
+                }
+    }
+    return true;
+}
 constexpr uint32_t lu_fused_steps() {
     uint32_t m = 0u;
     for (int l = 0; l < LU_LEVELS.nlevels; l++) m |= LU_LEVELS.fused[l];
@@ -178,6 +205,8 @@ constexpr uint32_t lu_bits(std::initializer_list<int> v) {
 }
 static_assert(lu_levels_disjoint(), "two steps of one level share a candidate row");
 static_assert(lu_levels_ordered(), "a fused step depends on a step outside the lower fused levels");
+static_assert(lu_back_chains_nested(), "a fused pivot row can hold a fused column outside its chain's ancestors");
+static_assert(lu_back_order_kept(), "a row's ancestors do not rise in column with the level");
 static_assert(lu_fused_steps() == (1u << 18) - 1u, "the fused levels cover exactly steps 0..17");
 static_assert(LU_LEVELS.nlevels == 4 && LU_LEVELS.fused[0] == lu_bits({0, 1, 2, 5, 8, 9, 10, 11}) &&
               LU_LEVELS.fused[1] == lu_bits({3, 4, 12, 15}) && LU_LEVELS.fused[2] == lu_bits({6, 7, 13, 16}) &&
