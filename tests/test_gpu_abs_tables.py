@@ -16,6 +16,7 @@ import pytest
 
 from checks import (KERNEL_BY_SIZE, SMALL_NEVER, assert_matches_golden, assert_matches_oracle, golden, launch_mode,
                     scaled_samples)
+from eval_cases import row_permuted as _row_permuted
 
 pytestmark = pytest.mark.gpu
 
@@ -23,19 +24,11 @@ N = 2
 SWAP = (0, 9)   # a row order outside the specialised LU's structure (the structure-agnostic twin tracks it)
 
 
-def _row_permuted(problem, perm):
-    """The index tables with the equations (rows) reordered: row r of the new
-    system is row perm[r] of the reference's (a valid, equivalent problem)."""
-    dx = problem.dHdx_index.reshape(-1, 30)[:, perm].reshape(-1)
-    dt = problem.dHdt_index.reshape(-1, 30)[:, perm].reshape(-1)
-    return np.ascontiguousarray(np.concatenate([dx, dt]), np.int32)
-
-
 @pytest.fixture(scope="module")
 def permuted_index(problem):
     perm = np.arange(30)
     perm[SWAP[0]], perm[SWAP[1]] = SWAP[1], SWAP[0]
-    U = _row_permuted(problem, perm)
+    _, _, U = _row_permuted(problem, perm)
     U.setflags(write=False)
     return U
 

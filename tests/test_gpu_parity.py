@@ -11,6 +11,7 @@ from checks import (KERNEL_BY_SIZE, SMALL_ALWAYS, SMALL_NEVER, assert_bit_identi
                     assert_matches_oracle, assert_untouched, found_ids, golden, golden_passing, launch_mode,
                     ring_counters, run_cli, scaled_samples, tracked)
 from conftest import same
+from eval_cases import row_permuted as _row_permuted
 from lu_cases import edge_case_systems, extreme_scale_systems
 from lu_cases import jacobians_from_path as _jacobians_from_path
 
@@ -439,15 +440,6 @@ def test_ph_matches_golden_N100(problem, samples100, tracker):
     tgt, dif, _ = samples100
     r = tracker.track(tgt, dif, truncate=False, explicit_rk=True).host()
     assert_matches_golden(r, golden("gpuhc_ph_N100_seed0"))
-
-
-def _row_permuted(problem, perm):
-    """The index tables with the equations (rows) reordered: row r of the new
-    system is row perm[r] of the reference's (a valid, equivalent problem)."""
-    dx = problem.dHdx_index.reshape(-1, 30)[:, perm].reshape(-1)
-    dt = problem.dHdt_index.reshape(-1, 30)[:, perm].reshape(-1)
-    return (np.ascontiguousarray(dx, np.int32), np.ascontiguousarray(dt, np.int32),
-            np.ascontiguousarray(np.concatenate([dx, dt]), np.int32))
 
 
 def test_eval_row_permuted_tables_match_oracle(problem, oracle, samples100):

@@ -11,7 +11,8 @@ from conftest import ROOT
 INCLUDE = os.path.join(ROOT, "include")
 
 # Test hooks that synchronise by design: not capturable, and their header comments say so
-BLOCKING = ("hc_trifocal_ring_check_test", "hc_cgesv_30x30_struct_batched", "hc_cgesv_30x30_variant_batched")
+BLOCKING = ("hc_trifocal_ring_check_test", "hc_cgesv_30x30_struct_batched", "hc_cgesv_30x30_variant_batched",
+            "hc_trifocal_eval_variant_batched")
 
 
 def _headers():

@@ -382,6 +382,17 @@ LU_VARIANTS = ("throughput", "throughput_twin", "abort", "abort_twin", "small", 
                "archived_twin")
 LU_DECLARED_SYMBOLS = tuple(s.name for s in LU_SIGNATURES)
 
+# include/eval/hc_eval_testing.h, the test hook of the tracking kernels' evaluations
+# beside the LU's: its table, bound and checked the same way
+# (tests/test_eval_cases_host.py)
+EVAL_SIGNATURES = (
+    Sig("hc_trifocal_eval_variant_batched", _ST, (_i, _u, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, *_WS), True),
+)
+# hcEvalVariant, in the header's order: the tables the evaluations read
+EVAL_VARIANTS = ("packed", "abs")
+HC_EVAL_REDO = 1
+EVAL_DECLARED_SYMBOLS = tuple(s.name for s in EVAL_SIGNATURES)
+
 # include/adaptive/hc_trifocal_adaptive.h, the adaptive sample limit's header beside
 # include/hc_trifocal.h: no launch of its own (a mode of the gated one), one host
 # function; its table, bound and checked the same way (tests/test_adaptive_host.py)
@@ -406,7 +417,7 @@ def lib() -> C.CDLL:
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
         for s in SIGNATURES + P2C_SIGNATURES + REFINE_SIGNATURES + TOPK_SIGNATURES + LU_SIGNATURES + \
-                ADAPTIVE_SIGNATURES:
+                EVAL_SIGNATURES + ADAPTIVE_SIGNATURES:
             fn = getattr(L, s.name, None)
             if fn is None:
                 if s.optional:

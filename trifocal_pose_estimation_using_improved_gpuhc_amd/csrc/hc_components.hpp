@@ -1,4 +1,4 @@
-// The component kernels k_cgesv and k_eval.
+// The component kernels k_cgesv and k_eval, and the test hooks' k_cgesv_variant and k_eval_variant.
 #pragma once
 
 #include "hc_layout.hpp"
@@ -147,6 +147,136 @@ __global__ void __launch_bounds__(WG_THREADS) k_eval(int n, const Workspace *ws,
         for (int c = 0; c < NV; c++) HX[((size_t)sys * NV + r) * NV + c] = rA[c];
         HT[(size_t)sys * NV + r] = ht;
         H[(size_t)sys * NV + r] = h;
+    }
+}
+
+// One stage's evaluations as the tracking kernels run them
+// (include/eval/hc_eval_testing.h, hc_trifocal_eval_variant_batched): k_eval
+// above builds the prefixes from a staged p and reads LDS copies of the packed
+// tables, which no tracking kernel does.  This kernel restates
+// hc_track_body.inc's sequence call for call, by hand (that file is included
+// textually into the trackers and cannot be called): keep the two in step; the
+// numbers below are that file's lines.  ABSTAB as there: the throughput
+// kernel's slot-absolute tables and its verdict on the dH/dx entries; else the
+// packed tables, read from the workspace.  Point i is served by path slot i % 8
+// of workgroup i / 8, the slot a path of that wave half has in a tracker, so
+// the absolute offsets count from s_slot as they do there.  kind: 0 a
+// predictor stage (pred), 1 the corrector; a half without a point is not `act`.
+// redo: the values of the evaluations before the dense re-solve (:606-633),
+// after the entry block was overwritten as the sparse solve's scratch use may.
+template <bool ABSTAB>
+__global__ void __launch_bounds__(WG_THREADS) k_eval_variant(int n, int redo_vals, const Workspace *ws,
+                                                             const cf *__restrict__ X, const cf *__restrict__ TGT,
+                                                             const cf *__restrict__ DIF, const cf *__restrict__ SP,
+                                                             const float *__restrict__ T0,
+                                                             const uint8_t *__restrict__ KIND, cf *__restrict__ HX,
+                                                             cf *__restrict__ RHS, uint8_t *__restrict__ ENT_OK) {
+    __shared__ cf s_sp[NPP];                                                      // :35-36
+    __shared__ SlotLDS s_slot[2 * WAVES_PER_WG];
+    const EvalTables *T = &ws->tab;                                               // :38-39
+    if (ws->status != 0u) return;
+    const uint2 *s_ht = T->ht;                                                    // :44-46
+    const uint32_t *s_hx = T->hx;
+    const uint32_t *s_hxd = &T->hxd[0][0];
+    if (threadIdx.x < NPP) s_sp[threadIdx.x] = SP[threadIdx.x];                   // :49-54
+    {
+        float *z = reinterpret_cast<float *>(s_slot);
+        for (int i = threadIdx.x; i < (int)(sizeof(s_slot) / 4); i += WG_THREADS) z[i] = 0.0f;
+    }
+    __syncthreads();
+    const int lane = lane_id();                                                   // :56-60
+    const int r = lane & 31, hb = lane & 32;
+    const int wid = threadIdx.x / WAVE;
+    SlotLDS &S = s_slot[wid * 2 + (hb >> 5)];
+    if (r == 30) S.x[30] = cmk(1.0f, 0.0f);
+    __shared__ uint32_t s_rowc[GM_WORDS + 1][32];                                 // :64-69
+    if (threadIdx.x < 32) {
+        for (int q = 0; q < GM_WORDS; q++) s_rowc[q][threadIdx.x] = T->gm[q][threadIdx.x];
+        s_rowc[GM_WORDS][threadIdx.x] = T->pat[threadIdx.x];
+    }
+    __syncthreads();
+    const bool rl = r < NV;                                                       // :70-75
+    wave_lds_sync();
+    const AbsTables *AT = &ws->abs;
+    const int wv = ABSTAB ? __builtin_amdgcn_readfirstlane(wid) : 0;
+    char *const l0 = reinterpret_cast<char *>(s_slot);
+
+    // the slot's point: its x, and its prefix tables from its own target, diff and t (a half
+    // without a point stages the last point's parameters, as an idle tracker slot stages sample 0's)
+    const int pt = (blockIdx.x * WAVES_PER_WG + wid) * 2 + (hb >> 5);
+    const size_t pi = (size_t)(pt < n ? pt : n - 1);
+    const unsigned kd = KIND[pi];
+    const bool act = pt < n && kd < 2u;   // (2: HC_EVAL_KIND_IDLE)
+    const bool pred = act && kd == 0u;
+    if (act && rl) S.x[r] = X[pi * (NV + 1) + r];                                 // :518
+    build_prefixes(S, r, &T->pre[0][0], TGT + pi * NPP, DIF + pi * NPP, s_sp, T0[pi]);   // :532
+    wave_lds_sync();                                                              // :535
+    const int lane_v = lane_fresh();                                              // :540-542
+    const int r_v = lane_v & 31;
+    const uint32_t l16 = (uint32_t)lane_v << 4;
+    cf rB = cmk(0.0f, 0.0f);                                                      // :550-573
+    {
+        const bool any_p = __ballot(pred) != 0ull, any_c = __ballot(act && !pred) != 0ull;
+        const RhsMasks mk = rhs_masks(T);
+        if (any_p && any_c) {
+            if constexpr (ABSTAB) rB = eval_rhs_abs<RHS_MIXED>(AT->ht[wv], AT->htq[wv], l0, l16, pred, mk);
+            else rB = eval_rhs<RHS_MIXED>(s_ht, S, r_v, pred, mk);
+        } else if (any_p) {
+            const cf t = ABSTAB ? eval_rhs_abs<RHS_HT>(AT->ht[wv], AT->htq[wv], l0, l16, true, mk)
+                                : eval_rhs<RHS_HT>(s_ht, S, r_v, true, mk);
+            if (pred) rB = t;
+        } else if (any_c) {
+            const cf t = ABSTAB ? eval_rhs_abs<RHS_H>(AT->ht[wv], AT->htq[wv], l0, l16, false, mk)
+                                : eval_rhs<RHS_H>(s_ht, S, r_v, false, mk);
+            if (!pred) rB = t;
+        }
+    }
+    cf rA[NV];                                                                    // :575-587
+    if constexpr (ABSTAB) {
+        uint4 gmv[ABS_GM_Q];
+        const bool ent_ok = eval_hx_terms_abs(AT->hx[wv], l0, l16, AT->gm[wv], gmv);
+        if (act) ENT_OK[pi * 32 + r] = ent_ok ? 1 : 0;   // the lane's own verdict, before the tracker's ballot (:588)
+        wave_lds_sync();
+        gather_hx_abs(rA, l0, gmv);
+    } else {
+        eval_hx(rA, s_hx, s_hxd, &s_rowc[0][0], S, r_v);
+    }
+    wave_lds_sync();
+    if (redo_vals) {
+        // what lu_solve<false> may leave of the entry block (hc_slot.hpp): everything but the structural zero
+        for (int k = r; k < ENT_CAP - 1; k += 32) S.ent[k] = cmk(__builtin_nanf(""), __builtin_nanf(""));
+        wave_lds_sync();
+        const bool act_r = act, pred_r = pred;                                    // :606-634
+        const int l_r = lane_fresh(), r_r = l_r & 31;
+        const uint32_t l16_r = (uint32_t)l_r << 4;
+        cf rb = cmk(0.0f, 0.0f);
+        if (__ballot(pred_r) != 0ull) {
+            const cf t = ABSTAB ? eval_rhs_abs<RHS_HT>(AT->ht[wv], AT->htq[wv], l0, l16_r, true, rhs_masks(T))
+                                : eval_rhs<RHS_HT>(s_ht, S, r_r, true, rhs_masks(T));
+            if (pred_r) rb = t;
+        }
+        if (__ballot(act_r && !pred_r) != 0ull) {
+            const cf t = ABSTAB ? eval_rhs_abs<RHS_H>(AT->ht[wv], AT->htq[wv], l0, l16_r, false, rhs_masks(T))
+                                : eval_rhs<RHS_H>(s_ht, S, r_r, false, rhs_masks(T));
+            if (!pred_r) rb = t;
+        }
+        if constexpr (ABSTAB) {
+            uint4 gmv[ABS_GM_Q];
+            eval_hx_terms_abs(AT->hx[wv], l0, l16_r, AT->gm[wv], gmv);
+            wave_lds_sync();
+            gather_hx_abs(rA, l0, gmv);
+        } else {
+            eval_hx_terms(s_hx, s_hxd, reinterpret_cast<char *>(&S), r_r);
+            wave_lds_sync();
+            gather_hx(rA, &s_rowc[0][0], S, r_r);
+        }
+        wave_lds_sync();
+        rB = rb;
+    }
+    if (act && rl) {
+#pragma unroll
+        for (int c = 0; c < NV; c++) HX[(pi * NV + r) * NV + c] = rA[c];
+        RHS[pi * NV + r] = rB;
     }
 }
 

@@ -29,6 +29,7 @@
 #include "../../include/hc_trifocal_testing.h"
 #include "../../include/p2c/hc_trifocal_p2c.h"
 #include "../../include/lu/hc_lu_testing.h"
+#include "../../include/eval/hc_eval_testing.h"
 #include "../../include/adaptive/hc_trifocal_adaptive.h"
 
 #include <atomic>
@@ -512,6 +513,50 @@ hcStatus hc_trifocal_eval_batched(int n, const int32_t *unified_index, const hcC
                        (const hc::cf *)x, (const hc::cf *)p, (const hc::cf *)d, (hc::cf *)Hx, (hc::cf *)Ht,
                        (hc::cf *)H);
     return hc::launch_status(HC_ERROR_LAUNCH);
+}
+
+// tests only (include/eval/hc_eval_testing.h): k_eval_variant.  Blocks: the
+// workspace's status is read back once the kernel has run.
+hcStatus hc_trifocal_eval_variant_batched(int variant, unsigned flags, int n, const int32_t *unified_index,
+                                          const hcComplex *x, const hcComplex *target, const hcComplex *diff,
+                                          const hcComplex *start_params, const float *t, const uint8_t *kind,
+                                          hcComplex *Hx, hcComplex *rhs, uint8_t *ent_ok, void *workspace,
+                                          size_t workspace_bytes, hcStream stream) {
+    if (variant < 0 || variant >= HC_EVAL_VARIANT_COUNT || (flags & ~HC_EVAL_REDO) != 0u) return HC_ERROR_INVALID_VALUE;
+    const bool abs_tables = variant == HC_EVAL_VARIANT_ABS;
+    if (n < 0 || (n > 0 && (!unified_index || !x || !target || !diff || !start_params || !t || !kind || !Hx || !rhs ||
+                            (abs_tables && !ent_ok))))
+        return HC_ERROR_INVALID_VALUE;
+    if (!workspace || workspace_bytes < hc::ws_bytes_needed()) return HC_ERROR_WORKSPACE;
+    if (n == 0) return HC_SUCCESS;
+    hipStream_t s = (hipStream_t)stream;
+    hc::Workspace *ws = (hc::Workspace *)workspace;
+    (void)hipGetLastError();
+    hc::PrepArgs pa{unified_index, ws, nullptr, nullptr, nullptr, nullptr, 0u, 0u, 0u};
+    hipLaunchKernelGGL(hc::k_prep_tables, dim3(1), dim3(hc::PREP_THREADS), 0, s, pa);
+    if (hc::launch_status(HC_ERROR_LAUNCH) != HC_SUCCESS) return HC_ERROR_LAUNCH;
+    const int per = 2 * hc::WAVES_PER_WG;
+    const dim3 grid((n + per - 1) / per), block(hc::WG_THREADS);
+    const int redo = (flags & HC_EVAL_REDO) ? 1 : 0;
+    if (abs_tables)
+        hipLaunchKernelGGL(hc::k_eval_variant<true>, grid, block, 0, s, n, redo, ws, (const hc::cf *)x,
+                           (const hc::cf *)target, (const hc::cf *)diff, (const hc::cf *)start_params, t, kind,
+                           (hc::cf *)Hx, (hc::cf *)rhs, ent_ok);
+    else
+        hipLaunchKernelGGL(hc::k_eval_variant<false>, grid, block, 0, s, n, redo, ws, (const hc::cf *)x,
+                           (const hc::cf *)target, (const hc::cf *)diff, (const hc::cf *)start_params, t, kind,
+                           (hc::cf *)Hx, (hc::cf *)rhs, ent_ok);
+    if (hc::launch_status(HC_ERROR_LAUNCH) != HC_SUCCESS) return HC_ERROR_LAUNCH;
+    unsigned ctl[16];   // the control block (hc_layout.hpp: 64 bytes)
+    hipError_t e = hipMemcpyAsync(ctl, workspace, sizeof(ctl), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+        hc::g_last_hip_error = e;
+        return HC_ERROR_DEVICE;
+    }
+    const unsigned status = ctl[offsetof(hc::Workspace, status) / sizeof(unsigned)];
+    if (status == 0u) return HC_SUCCESS;
+    return status == (unsigned)HC_ERROR_TABLE ? HC_ERROR_TABLE : HC_ERROR_DEVICE;
 }
 
 hcStatus hc_trifocal_p2c_eval_batched(int n, const int32_t *hx_index, const int32_t *ht_index, const hcComplex *x,

@@ -616,3 +616,43 @@ def eval_batched(unified: np.ndarray, x: np.ndarray, p: np.ndarray, d: np.ndarra
               _abi.ptr(torch.cuda.current_stream(dev)))
     torch.cuda.synchronize(dev)
     return HX.cpu().numpy(), HT.cpu().numpy(), H.cpu().numpy()
+
+
+def eval_variant_batched(variant, unified: np.ndarray, x: np.ndarray, target: np.ndarray, diff: np.ndarray,
+                         start_params: np.ndarray, t: np.ndarray, kind: np.ndarray, redo: bool = False,
+                         device="cuda:0", workspace: torch.Tensor | None = None):
+    """hc_trifocal_eval_variant_batched (include/eval/hc_eval_testing.h): one
+    stage's evaluations as a tracking kernel runs them, at n points; point i in
+    path slot i % 8, points 2k and 2k + 1 in one wave.  variant: hcEvalVariant,
+    its number or its name in _abi.EVAL_VARIANTS.  x (n, 31, 2), target and diff
+    (n, 34, 2), t (n,), kind (n,) uint8 (0: the negated dH/dt, 1: H).  Returns
+    (Hx (n, 30, 30, 2), rhs (n, 30, 2), ent_ok (n, 32) uint8: the lanes' verdicts,
+    all 255 for the packed variant, which leaves them untouched).  workspace: a
+    device tensor to run in (default: a fresh one)."""
+    dev = _require_gpu(device)
+    if isinstance(variant, str):
+        variant = _abi.EVAL_VARIANTS.index(variant)
+    n = x.shape[0]
+    U = torch.from_numpy(np.ascontiguousarray(unified, np.int32)).to(dev)
+    X = torch.from_numpy(np.ascontiguousarray(x, np.float32)).to(dev)
+    TG = torch.from_numpy(np.ascontiguousarray(target, np.float32)).to(dev)
+    DF = torch.from_numpy(np.ascontiguousarray(diff, np.float32)).to(dev)
+    SP = torch.from_numpy(np.ascontiguousarray(start_params, np.float32)).to(dev)
+    T = torch.from_numpy(np.ascontiguousarray(t, np.float32)).to(dev)
+    K = torch.from_numpy(np.ascontiguousarray(kind, np.uint8)).to(dev)
+    if tuple(X.shape) != (n, 31, 2) or tuple(TG.shape) != (n, 34, 2) or tuple(DF.shape) != (n, 34, 2) or \
+            tuple(SP.shape) != (34, 2) or tuple(T.shape) != (n,) or tuple(K.shape) != (n,) or U.numel() != 38880:
+        raise _abi.HCError("eval_variant_batched: x (n, 31, 2), target and diff (n, 34, 2), start_params (34, 2), "
+                           "t and kind (n,), a unified index of 38880 values")
+    HX = torch.empty((n, 30, 30, 2), dtype=torch.float32, device=dev)
+    RHS = torch.empty((n, 30, 2), dtype=torch.float32, device=dev)
+    OK = torch.full((n, 32), 255, dtype=torch.uint8, device=dev)
+    wsb = int(_abi.lib().hc_trifocal_workspace_size())
+    ws = workspace if workspace is not None else torch.zeros(wsb, dtype=torch.uint8, device=dev)
+    if ws.numel() * ws.element_size() < wsb:
+        raise _abi.HCError("eval_variant_batched: workspace too small")
+    _abi.call("hc_trifocal_eval_variant_batched", int(variant), _abi.HC_EVAL_REDO if redo else 0, n,
+              *(_abi.ptr(v) for v in (U, X, TG, DF, SP, T, K, HX, RHS, OK, ws)), ws.numel() * ws.element_size(),
+              _abi.ptr(torch.cuda.current_stream(dev)))
+    torch.cuda.synchronize(dev)
+    return HX.cpu().numpy(), RHS.cpu().numpy(), OK.cpu().numpy()
