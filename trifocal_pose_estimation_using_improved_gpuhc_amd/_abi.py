@@ -382,6 +382,14 @@ LU_VARIANTS = ("throughput", "throughput_twin", "abort", "abort_twin", "small", 
                "archived_twin")
 LU_DECLARED_SYMBOLS = tuple(s.name for s in LU_SIGNATURES)
 
+# include/lu/hc_lu_rowtable_testing.h, the fused levels' row records beside the
+# LU's other test hooks (tests/test_lu_rowtable_host.py); hcLuRowField in the
+# header's order
+LU_ROWTABLE_SIGNATURES = (
+    Sig("hc_lu_row_field", _i, (_i, _i, _i), True),
+)
+LU_ROW_FIELDS = ("member", "bound", "window", "partner", "place", "chain")
+
 # include/eval/hc_eval_testing.h, the test hook of the tracking kernels' evaluations
 # beside the LU's: its table, bound and checked the same way
 # (tests/test_eval_cases_host.py)
@@ -417,7 +425,7 @@ def lib() -> C.CDLL:
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
         for s in SIGNATURES + P2C_SIGNATURES + REFINE_SIGNATURES + TOPK_SIGNATURES + LU_SIGNATURES + \
-                EVAL_SIGNATURES + ADAPTIVE_SIGNATURES:
+                LU_ROWTABLE_SIGNATURES + EVAL_SIGNATURES + ADAPTIVE_SIGNATURES:
             fn = getattr(L, s.name, None)
             if fn is None:
                 if s.optional:

@@ -66,6 +66,10 @@ __global__ void __launch_bounds__(WG_THREADS) k_cgesv_variant(int n, const cf *_
                                                               const cf *__restrict__ B, cf *__restrict__ X) {
     __shared__ LUBuf s_lu[2 * WAVES_PER_WG];
     __shared__ __attribute__((aligned(16))) cf s_scr[2 * WAVES_PER_WG][FUSE ? LU_SCRATCH_FUSED_CF : LU_SCRATCH_CF];
+    if constexpr (FUSE) {   // the fused levels' row records (hc_lu_levels.hpp)
+        lu_rowtab_fill(threadIdx.x);
+        __syncthreads();
+    }
     const int lane = lane_id();
     const int r = lane & 31;
     const int sys = (blockIdx.x * WAVES_PER_WG + threadIdx.x / WAVE) * 2 + (lane >> 5);

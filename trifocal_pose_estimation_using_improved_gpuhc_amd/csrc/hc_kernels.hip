@@ -29,6 +29,7 @@
 #include "../../include/hc_trifocal_testing.h"
 #include "../../include/p2c/hc_trifocal_p2c.h"
 #include "../../include/lu/hc_lu_testing.h"
+#include "../../include/lu/hc_lu_rowtable_testing.h"
 #include "../../include/eval/hc_eval_testing.h"
 #include "../../include/adaptive/hc_trifocal_adaptive.h"
 
@@ -667,6 +668,23 @@ int hc_lu_group_class(int step, int group) {
     if (step < 0 || step >= hc::NV - 1 || group < 0 || group >= hc::LuChunks::count(step)) return -1;
     return hc::lu_group_class(step, group);
 }
+// tests only (include/lu/hc_lu_rowtable_testing.h): a field of the fused levels'
+// row records, decoded from the table the kernels copy to LDS (LU_ROWTAB)
+int hc_lu_row_field(int level, int row, int field) {
+    if (level < 0 || level >= hc::LU_REC_LEVELS || row < 0 || row >= hc::LU_REC_ROWS) return -2;
+    hc::LuRowRec rec{0u, hc::LU_ROWTAB.w[level * hc::LU_REC_ROWS + row]};
+    rec.bound = hc::LU_ROWTAB.w[hc::LU_REC_BOUND0 + ((rec.word >> hc::LU_REC_MEMBER_AT) & 31u)];
+    const int mem = (int)((rec.word >> hc::LU_REC_MEMBER_AT) & 31u), k = (int)((rec.word >> hc::LU_REC_CHAIN_AT) & 15u);
+    switch (field) {
+    case HC_LU_ROW_MEMBER: return mem == hc::LU_REC_NO_MEMBER ? -1 : mem;
+    case HC_LU_ROW_BOUND: return (int)rec.bound;
+    case HC_LU_ROW_WINDOW: return (int)(rec.word & ((1u << hc::LU_REC_WIN_BITS) - 1u)) / 8 + 2 * row;
+    case HC_LU_ROW_PARTNER: return (int)((rec.word >> hc::LU_REC_PARTNER_AT) & 31u);
+    case HC_LU_ROW_PLACE: return (rec.word & hc::LU_REC_FIRST) ? 0 : (rec.word & hc::LU_REC_UP) ? 1 : 2;
+    case HC_LU_ROW_CHAIN: return k == hc::LU_REC_NO_CHAIN ? -1 : k;
+    default: return -2;
+    }
+}
 
 hcStatus hc_trifocal_ring_check_test(void *workspace, size_t workspace_bytes, unsigned head, unsigned tail,
                                      unsigned avail, hcStream stream) {
@@ -699,7 +717,7 @@ void hc_trifocal_set_small_launch(int mode) {
 void hc_trifocal_set_retry_reuse(int on) { hc::g_retry_reuse.store(on ? 1 : 0, std::memory_order_relaxed); }
 
 const char *hc_trifocal_version(void) {
-    return "hc_trifocal gfx950 v10.11 (2 paths/wave, structurally sparse LDS-broadcast LU with lean pivot steps fused by level, "
+    return "hc_trifocal gfx950 v10.12 (2 paths/wave, structurally sparse LDS-broadcast LU with lean pivot steps fused by level, the levels' per-row constants and row labels read from LDS tables, "
            "one exec region per pivot step for the eligible rows with the column groups through scratch windows, "
            "column groups by structural class (never-fillable groups untested, always-live groups unconditional), "
            "pivot search narrowed to the candidate rows' DPP group "

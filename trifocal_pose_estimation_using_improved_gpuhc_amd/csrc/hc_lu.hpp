@@ -660,7 +660,7 @@ __device__ __forceinline__ void lu_forward_fused(cf (&rA)[NV], cf &rB, int &rowi
                                                  bool row_lane, PivF &my, LUBuf &L, cf *scr, bool &redo,
                                                  unsigned long long elig_m HC_LU_WORK_ARG) {
     if constexpr (LV < LU_LEVELS.nlevels) {
-        if (!lu_level<LV>(rA, rB, rowid, pat, lane, r, hb, my, scr, elig_m HC_LU_WORK_PASS)) {
+        if (!lu_level<LV>(rA, rB, rowid, pat, r, hb, my, L, scr, elig_m HC_LU_WORK_PASS)) {
 #ifdef HC_DIAG_LUWORK
             lu_work_acc.rare++;
             lu_work_acc.rare_fusable = 1ull;
@@ -787,7 +787,8 @@ __device__ __forceinline__ cf lu_solve(cf (&rA)[NV], cf rB, int lane, uint32_t p
             return cmk(0.0f, 0.0f);
         }
     }
-    int rowid = row_lane ? r : 99;   // padding lanes never pivot
+    // padding lanes never pivot (FUSE: a label is an index into the levels' label table, row[0..31])
+    int rowid = row_lane ? r : FUSE ? NV : 99;
     uint32_t pat = row_lane ? pattern : 0u;
     PivF my{pf2{0.0f, 0.0f}};
 #ifdef HC_DIAG_LUWORK

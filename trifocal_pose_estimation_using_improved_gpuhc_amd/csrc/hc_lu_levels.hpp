@@ -7,10 +7,14 @@
 // candidate sets are pairwise disjoint "chains" of one or two lane triples, and
 // every lane of a chain does for its own chain's column what a step does for
 // column I:
+//  * the row's record: what the row is to the level -- its chain and member,
+//    its chain's window, its partner across a 6-row chain, its place in its
+//    triple -- is one word of LU_ROWTAB (hc_lu_struct.hpp), read from LDS;
 //  * candidate: the lane's entry in its chain's column (a select over the
-//    level's members on static lane masks); 1 / candidate once;
+//    level's members, one compare with the record's chain number each);
+//    1 / candidate once;
 //  * search: the maximum key over the lane's own chain -- inside the triple
-//    with four DPP wave shifts masked by the lane's place in it, across the two
+//    with four DPP wave shifts selected by the lane's place in it, across the two
 //    triples of a 6-row chain with one ds_bpermute (rows 15..17 cross the
 //    16-lane DPP row).  One maximum per chain and half, all in the fast
 //    reciprocal range, or the solve leaves the fused path: `redo` (the labels
@@ -30,49 +34,71 @@
 //    are dead as well);
 //  * pattern: a row that holds its chain's column takes the member's bound
 //    LU_BOUND.s (a superset of the pivot rows' patterns);
-//  * row labels: the members' relabels one after the other in increasing I,
-//    from the pivot ballot (v_readlane of the pivot lanes' labels).
+//  * row labels: the members' relabels at once, through a table of labels in
+//    the half's buffer (lvl_relabel).
 #pragma once
 
 namespace hc {
 
 constexpr int DPP_WAVE_SHL1 = 0x130, DPP_WAVE_SHR1 = 0x138;   // lane i takes lane i + 1 / i - 1 (GFX9)
 
-// each lane's candidate, its member's bound and its chain's window offset
+// The row records' home (LU_ROWTAB, hc_lu_struct.hpp): 640 B of the workgroup's
+// LDS, in the kernels that run the fused solve only.  lu_rowtab_fill runs once
+// per workgroup, before a barrier that precedes the first solve.
+__device__ __forceinline__ uint32_t *lu_rowtab_lds() {
+    __shared__ uint32_t t[LU_REC_WORDS];
+    return t;
+}
+__device__ __forceinline__ void lu_rowtab_fill(int tid) {
+    if (tid < LU_REC_WORDS) lu_rowtab_lds()[tid] = LU_ROWTAB.w[tid];
+}
+// the candidate of a lane whose record names chain kk (no chain: it stays zero)
 template <int LV, int K>
-__device__ __forceinline__ void lvl_pick(const cf (&rA)[NV], pf2 &c, uint32_t &bnd, int &cwo) {
+__device__ __forceinline__ void lvl_pick(const cf (&rA)[NV], pf2 &c, int kk) {
     if constexpr (K < lu_level_count(LV)) {
         constexpr int I = lu_level_member(LV, K);
-        const bool in = __builtin_amdgcn_inverse_ballot_w64(lu_both(LU_BOUND.cand[I]));
+        const bool in = kk == K;
         c.x = in ? rA[I].x : c.x;
         c.y = in ? rA[I].y : c.y;
-        bnd = in ? LU_BOUND.s[I] : bnd;
-        cwo = in ? LU_CHAIN_WIN0 + 2 * K : cwo;
-        lvl_pick<LV, K + 1>(rA, c, bnd, cwo);
+        lvl_pick<LV, K + 1>(rA, c, kk);
     }
 }
-// the members' relabels in increasing I (:70-82): the pivot lane takes label
-// I, the lane that held I takes the pivot lane's old label.  Over the whole
-// solve the order is level by level (0, 1, 2, 5, 8..11, then 3, 4, 12, 15, ...),
-// not 0..17, and the labels before step 18 are still exactly the sequential
-// ones: a relabel exchanges the label values I and label(p_I), the pivot lanes
-// p_I are chosen from the entries, never from the labels, and two relabels with
-// different pivot lanes p, q commute -- both orders end with p at I, q at J,
-// and the former holders of I and J (where they are not p or q) at the old
-// labels of p and q; if p held J, the holder of I ends with q's old label
-// either way.  So any order of the 18 relabels gives the same labels.
-template <int LV, int K>
-__device__ __forceinline__ void lvl_relabel(int &rowid, unsigned long long m, int hb) {
-    if constexpr (K < lu_level_count(LV)) {
-        constexpr int I = lu_level_member(LV, K);
-        const unsigned long long mi = and_halves<LU_BOUND.cand[I]>(m);
-        const int p0 = __builtin_amdgcn_readlane(rowid, __builtin_ctz((unsigned)mi));
-        const int p1 = __builtin_amdgcn_readlane(rowid, 32 + __builtin_ctz((unsigned)(mi >> 32)));
-        const int piv_pos = hb ? p1 : p0;
-        const bool is_p = __builtin_amdgcn_inverse_ballot_w64(mi);
-        rowid = is_p ? I : (rowid == I ? piv_pos : rowid);
-        lvl_relabel<LV, K + 1>(rowid, m, hb);
+
+// The members' relabels (:70-82): the pivot lane takes label I, the lane that
+// held I takes the pivot lane's old label.  Over the whole solve the order is
+// level by level (0, 1, 2, 5, 8..11, then 3, 4, 12, 15, ...), not 0..17, and the
+// labels before step 18 are still exactly the sequential ones: a relabel
+// exchanges the label values I and label(p_I), the pivot lanes p_I are chosen
+// from the entries, never from the labels, and two relabels with different
+// pivot lanes p, q commute -- both orders end with p at I, q at J, and the
+// former holders of I and J (where they are not p or q) at the old labels of p
+// and q; if p held J, the holder of I ends with q's old label either way.  So
+// any order of the 18 relabels gives the same labels.
+// A level's relabels at once: the labels' table is row[l].x of the half's buffer
+// (unused until step 18), the label a row that holds label l takes next.  It is
+// the identity (lu_level<0> writes it) but at the level's members, where the
+// pivot lane of member I has written its own label to row[I].x before the
+// level's broadcast.  Every row not pivoted yet takes the table's label for its
+// own, and again while some row has reached another member's label: that
+// member's pivot lane held the label the first member's holder was due (at
+// level 0, row 5 can be member 0's pivot lane), which is what the relabels one
+// after the other give.  No such row enters a cycle of the table: it is
+// injective on the members, and a cycle's labels are all held by pivot lanes.
+// Then the pivot lanes take their members.  A pivoted row keeps its label from
+// there on, so a label a row holds is a member of the level or not in the
+// table's changed part: the entries of earlier levels are never read again.
+// (Until v10.11 the members' relabels ran one after the other, 8 instructions
+// each with two v_readlane.)
+template <int LV>
+__device__ __forceinline__ void lvl_relabel(int &rowid, int mem, bool is_piv, unsigned long long live_m, const LUBuf &L) {
+    const bool live = __builtin_amdgcn_inverse_ballot_w64(live_m);
+    for (;;) {
+        const int t = __float_as_int(L.row[rowid].x);
+        rowid = live ? t : rowid;
+        const bool again = live && ((lu_member_cols(LV) >> rowid) & 1u) != 0u;
+        if (__builtin_expect(__builtin_amdgcn_ballot_w64(again) == 0ull, 1)) break;
     }
+    rowid = is_piv ? mem : rowid;
 }
 // the level's column pairs J, J + 1 (J even) inside the eligible rows' region
 template <int LV, int J>
@@ -91,43 +117,34 @@ __device__ __forceinline__ void lvl_groups(cf (&rA)[NV], const pf2 &l, cf *wrow,
 }
 // returns false when the level met a rare condition (nothing is changed then)
 template <int LV>
-__device__ __forceinline__ bool lu_level(cf (&rA)[NV], cf &rB, int &rowid, uint32_t &pat, int lane, int r, int hb,
-                                         PivF &my, cf *scr, unsigned long long &elig_m HC_LU_WORK_ARG) {
+__device__ __forceinline__ bool lu_level(cf (&rA)[NV], cf &rB, int &rowid, uint32_t &pat, int r, int hb, PivF &my,
+                                         LUBuf &L, cf *scr, unsigned long long &elig_m HC_LU_WORK_ARG) {
     constexpr int CNT = lu_level_count(LV), I0 = lu_level_member(LV, 0);
     constexpr uint32_t ROWS = LU_LEVELS.rows[LV];
     HC_ISA_MARK_I("lu_search", I0);
     pf2 c = {0.0f, 0.0f};
-    uint32_t bnd = 0u;
-    int cwo = 0;
-    lvl_pick<LV, 0>(rA, c, bnd, cwo);
+    const uint32_t rec = lu_rowtab_lds()[LV * LU_REC_ROWS + r];
+    lvl_pick<LV, 0>(rA, c, (int)((rec >> LU_REC_CHAIN_AT) & 15u));
     const float v = __builtin_fabsf(c.x) + __builtin_fabsf(c.y);          // :55
     pf2 oo_s;
     const pf2 reg_s = recip_fast(c, v, oo_s);
     const unsigned long long lv_elig = and_halves<ROWS>(elig_m);
     const bool elig = __builtin_amdgcn_inverse_ballot_w64(lv_elig);
     const int key = elig ? __float_as_int(v) : -1;
-    // the maximum over the lane's triple: the neighbours one and two lanes up
-    // and down, each only where it lies in the same triple
+    // the maximum over the lane's triple: the two other rows are one and two
+    // lanes up from its first row, one up and one down from the middle one, one
+    // and two down from the last
     int mx;
     {
         const int u1 = dpp_i<DPP_WAVE_SHL1>(key), u2 = dpp_i<DPP_WAVE_SHL1>(u1);
         const int d1 = dpp_i<DPP_WAVE_SHR1>(key), d2 = dpp_i<DPP_WAVE_SHR1>(d1);
-        const int a = __builtin_amdgcn_inverse_ballot_w64(lu_both(LU_TRI0 | LU_TRI1)) ? u1 : -1;
-        const int b = __builtin_amdgcn_inverse_ballot_w64(lu_both(LU_TRI0)) ? u2 : -1;
-        const int e = __builtin_amdgcn_inverse_ballot_w64(lu_both(LU_TRI1 | LU_TRI2)) ? d1 : -1;
-        const int f = __builtin_amdgcn_inverse_ballot_w64(lu_both(LU_TRI2)) ? d2 : -1;
-        mx = max(max(key, a), max(b, max(e, f)));
+        const int a = rec >= LU_REC_UP ? u1 : d2;
+        const int b = (int)rec < 0 ? u2 : d1;
+        mx = max(key, max(a, b));
     }
     // ... and over the partner triple of a 6-row chain
-    constexpr uint32_t UP9 = lu_partner_rows(LV, 9), DN9 = lu_partner_rows(LV, -9), UP6 = lu_partner_rows(LV, 6),
-                       DN6 = lu_partner_rows(LV, -6);
-    static_assert((UP9 | DN9 | UP6 | DN6 | lu_partner_rows(LV, 0)) == (1u << NV) - 1u, "partner triples 6 or 9 lanes away");
-    if constexpr ((UP9 | DN9 | UP6 | DN6) != 0u) {
-        int pl = lane;
-        if constexpr (UP9 != 0u) pl = __builtin_amdgcn_inverse_ballot_w64(lu_both(UP9)) ? lane + 9 : pl;
-        if constexpr (DN9 != 0u) pl = __builtin_amdgcn_inverse_ballot_w64(lu_both(DN9)) ? lane - 9 : pl;
-        if constexpr (UP6 != 0u) pl = __builtin_amdgcn_inverse_ballot_w64(lu_both(UP6)) ? lane + 6 : pl;
-        if constexpr (DN6 != 0u) pl = __builtin_amdgcn_inverse_ballot_w64(lu_both(DN6)) ? lane - 6 : pl;
+    if constexpr (lu_partner_rows(LV, 0) != (1u << NV) - 1u) {
+        const int pl = (int)((rec >> LU_REC_PARTNER_AT) & 31u) + hb;   // (a row without a partner: itself)
         mx = max(mx, __builtin_amdgcn_ds_bpermute(pl << 2, mx));
     }
     // one maximum per chain and half, every one in the fast reciprocal range
@@ -137,16 +154,21 @@ __device__ __forceinline__ bool lu_level(cf (&rA)[NV], cf &rB, int &rowid, uint3
     if (__builtin_expect((__builtin_popcountll(m) != 2 * CNT) | (bad != 0ull), 0)) return false;
     const bool is_piv = __builtin_amdgcn_inverse_ballot_w64(m);
     HC_ISA_MARK_I("lu_store", I0);
-    const cf *cw = scr + (cwo - 2 * r);
+    const cf *cw = reinterpret_cast<const cf *>(reinterpret_cast<const char *>(scr) + (rec & ((1u << LU_REC_WIN_BITS) - 1u)));
     cf *wrow = is_piv ? const_cast<cf *>(cw) : scr;
     st4(&wrow[0], cmk(reg_s.x, reg_s.y), rB);
+    const int mem = (int)((rec >> LU_REC_MEMBER_AT) & 31u);
+    const uint32_t bnd = lu_rowtab_lds()[LU_REC_BOUND0 + mem];   // (read back with the broadcast below)
+    // the labels' table (lvl_relabel)
+    if constexpr (LV == 0) L.row[r].x = __int_as_float(r);
+    if (is_piv) L.row[mem].x = __int_as_float(rowid);
     wave_lds_sync();
     HC_ISA_MARK_I("lu_rcp", I0);
     cf reg, sB0;
     ld4(&cw[0], reg, sB0);
     if (is_piv) my.oo = oo_s;
     asm volatile("" : "+v"(my.oo));
-    lvl_relabel<LV, 0>(rowid, m, hb);
+    lvl_relabel<LV>(rowid, mem, is_piv, elig_m & ~m, L);
     HC_ISA_MARK_I("lu_update", I0);
 #ifdef HC_DIAG_LUWORK
     {   // the level's column pairs x the eligible rows below the pivots (wave-uniform)
@@ -177,11 +199,12 @@ __device__ __forceinline__ bool lu_level(cf (&rA)[NV], cf &rB, int &rowid, uint3
 // where J is an ancestor of I in the forest (lu_back_chains_nested,
 // hc_lu_struct.hpp), and every lane has at most one member per level, so a lane
 // does for its own chain's column what lu_backward<I> does for column I:
-//  * select: its entry in the member's column, on the static lane masks of
-//    lvl_pick, and the member's position;
+//  * select: its entry in the member's column and the member's position, from
+//    the row's record as in lu_level;
 //  * divide: cuCdivf(b, pivot) with the factors it kept, once per level; the
-//    owner's (the lane whose label is its member: its b is final, every
-//    position above 17 and every ancestor has updated it) is x_I;
+//    owner's (the lane whose label is its member, which lvl_relabel gave the
+//    member's pivot lane: its b is final, every position above 17 and every
+//    ancestor has updated it) is x_I;
 //  * broadcast: the owner writes x_I into its half's buffer at row[I] (free
 //    since the forward elimination ended);
 //  * update: every lane of the level's rows reads the x of its own member and
@@ -195,28 +218,13 @@ __device__ __forceinline__ bool lu_level(cf (&rA)[NV], cf &rB, int &rowid, uint3
 //    (lu_back_order_kept), so its non-zero updates keep the descending order.
 // Level 0 has nothing left to update: after its broadcast the lanes r < 18 read
 // the x_r they return.
-template <int LV, int K>
-__device__ __forceinline__ void lvl_back_pick(const cf (&rA)[NV], pf2 &c, int &mem) {
-    if constexpr (K < lu_level_count(LV)) {
-        constexpr int I = lu_level_member(LV, K);
-        if constexpr (K == 0) {   // (lanes outside the level: never owners, masked off the update)
-            c = pf2{rA[I].x, rA[I].y};
-            mem = I;
-        } else {
-            const bool in = __builtin_amdgcn_inverse_ballot_w64(lu_both(LU_BOUND.cand[I]));
-            c.x = in ? rA[I].x : c.x;
-            c.y = in ? rA[I].y : c.y;
-            mem = in ? I : mem;
-        }
-        lvl_back_pick<LV, K + 1>(rA, c, mem);
-    }
-}
 template <int LV>
-__device__ __forceinline__ void lu_back_level(const cf (&rA)[NV], cf &rB, int rowid, const PivF &my, LUBuf &L) {
+__device__ __forceinline__ void lu_back_level(const cf (&rA)[NV], cf &rB, int rowid, const PivF &my, LUBuf &L, int r) {
     HC_ISA_MARK_I("lu_back_level", LV);
-    pf2 c;
-    int mem;
-    lvl_back_pick<LV, 0>(rA, c, mem);
+    pf2 c = {0.0f, 0.0f};
+    const uint32_t rec = lu_rowtab_lds()[LV * LU_REC_ROWS + r];
+    lvl_pick<LV, 0>(rA, c, (int)((rec >> LU_REC_CHAIN_AT) & 15u));
+    const int mem = (int)((rec >> LU_REC_MEMBER_AT) & 31u);   // (LU_REC_NO_MEMBER outside the level: no row's label)
     const pf2 q = pcdiv_apply(pf2{rB.x, rB.y}, c, my);
     if (rowid == mem) L.row[mem] = cmk(q.x, q.y);   // mem is one of the level's members: inside row[0..17]
     wave_lds_sync();
@@ -234,7 +242,7 @@ template <int LV>
 __device__ __forceinline__ void lu_backward_fused(const cf (&rA)[NV], cf &rB, int rowid, const PivF &my, LUBuf &L, int r,
                                                   pf2 &res) {
     if constexpr (LV >= 0) {
-        lu_back_level<LV>(rA, rB, rowid, my, L);
+        lu_back_level<LV>(rA, rB, rowid, my, L, r);
         lu_backward_fused<LV - 1>(rA, rB, rowid, my, L, r, res);
     } else {
         if (__builtin_amdgcn_inverse_ballot_w64(lu_both(lu_fused_steps()))) {

@@ -275,4 +275,75 @@ constexpr int LU_SCRATCH_CF = 2 * 31 + 32;   // 94: lane r's window scratch[2r .
 constexpr int LU_CHAIN_WIN0 = LU_SCRATCH_CF;
 constexpr int LU_SCRATCH_FUSED_CF = LU_CHAIN_WIN0 + 2 * (lu_max_level_count() - 1) + 32;
 
+// What a row is to a fused level: one word per level and row, and the fill-in
+// bound of each fused step (hc_lu_levels.hpp reads them from LDS, a ds_read_b32
+// each, where it built the same values with selects on static lane masks).
+// The headline kernel's five workgroups per CU leave less than 1 KB of LDS (an
+// 8-byte record per level and row, 1 024 B, cost the fifth workgroup): the
+// bound, which is a member's and not a row's, stands once per member,
+// LU_REC_WORDS words in all.  A row's
+// word, from bit 0:
+//   10 bits  the byte offset of its chain's window from the row's own window,
+//            8 * (LU_CHAIN_WIN0 + 2k - 2r)
+//    5 bits  the member: the pivot step of its chain
+//    5 bits  the row whose maximum it takes with ds_bpermute: the same place in
+//            the other triple of a 6-row chain
+//    4 bits  k, the chain's number at the level
+//   bit 30   the row is not the last of its triple (it takes the row above's key)
+//   bit 31   the row is the first of its triple
+// A row outside the level's rows, and the pad rows 30 and 31 at every level, hold
+// neutral values: its own window, member LU_REC_NO_MEMBER (whose bound is
+// empty), itself as the partner, chain LU_REC_NO_CHAIN.
+struct LuRowRec { uint32_t bound, word; };
+constexpr int LU_REC_WIN_BITS = 10, LU_REC_MEMBER_AT = 10, LU_REC_PARTNER_AT = 15, LU_REC_CHAIN_AT = 20;
+constexpr uint32_t LU_REC_UP = 1u << 30, LU_REC_FIRST = 1u << 31;
+constexpr int LU_REC_NO_MEMBER = 31, LU_REC_NO_CHAIN = 15;
+constexpr int LU_REC_ROWS = 32, LU_REC_LEVELS = 4;
+constexpr int lu_row_chain(int lv, int row) {   // the chain of the level that holds the row, -1 without one
+    if (row >= NV) return -1;
+    for (int k = 0; k < lu_level_count(lv); k++)
+        if ((LU_BOUND.cand[lu_level_member(lv, k)] >> row) & 1u) return k;
+    return -1;
+}
+constexpr LuRowRec lu_row_record(int lv, int row) {
+    const int k = lu_row_chain(lv, row);
+    const uint32_t place = (row % 3 == 0 ? LU_REC_FIRST : 0u) | (row % 3 != 2 ? LU_REC_UP : 0u);
+    if (k < 0)
+        return LuRowRec{0u, place | (uint32_t)LU_REC_NO_CHAIN << LU_REC_CHAIN_AT | (uint32_t)row << LU_REC_PARTNER_AT |
+                                (uint32_t)LU_REC_NO_MEMBER << LU_REC_MEMBER_AT};
+    const int I = lu_level_member(lv, k);
+    return LuRowRec{LU_BOUND.s[I], place | (uint32_t)k << LU_REC_CHAIN_AT |
+                                       (uint32_t)(row + lu_partner_off(lv, row)) << LU_REC_PARTNER_AT |
+                                       (uint32_t)I << LU_REC_MEMBER_AT | (uint32_t)(8 * (LU_CHAIN_WIN0 + 2 * k - 2 * row))};
+}
+// the rows' words by level, then the bounds by member (0 .. LU_REC_NO_MEMBER)
+constexpr int LU_REC_BOUND0 = LU_REC_LEVELS * LU_REC_ROWS, LU_REC_WORDS = LU_REC_BOUND0 + LU_REC_NO_MEMBER + 1;
+struct LuRowTab { uint32_t w[LU_REC_WORDS]; };
+constexpr LuRowTab lu_row_table() {
+    LuRowTab t{};
+    for (int lv = 0; lv < LU_REC_LEVELS; lv++)
+        for (int r = 0; r < LU_REC_ROWS; r++) {
+            const LuRowRec rec = lu_row_record(lv, r);
+            t.w[lv * LU_REC_ROWS + r] = rec.word;
+            t.w[LU_REC_BOUND0 + (int)((rec.word >> LU_REC_MEMBER_AT) & 31u)] = rec.bound;
+        }
+    return t;
+}
+constexpr LuRowTab LU_ROWTAB = lu_row_table();
+constexpr bool lu_row_fields_fit() {
+    for (int lv = 0; lv < LU_REC_LEVELS; lv++)
+        for (int r = 0; r < NV; r++) {
+            const int k = lu_row_chain(lv, r), p = r + lu_partner_off(lv, r);
+            if (k < 0) continue;
+            const int win = 8 * (LU_CHAIN_WIN0 + 2 * k - 2 * r);
+            if (win <= 0 || win >= (1 << LU_REC_WIN_BITS) || k >= LU_REC_NO_CHAIN || p < 0 || p >= NV) return false;
+            if (lu_level_member(lv, k) >= LU_REC_NO_MEMBER || (LU_BOUND.s[lu_level_member(lv, k)] >> NV) != 0u) return false;
+        }
+    return true;
+}
+static_assert(LU_LEVELS.nlevels == LU_REC_LEVELS && lu_row_fields_fit(), "a field of the row records overflows");
+// 31 120 B of the headline kernel's workgroup + the table: at 32 144 B five
+// workgroups no longer share a CU (measured), at 31 760 B they do
+static_assert(LU_REC_WORDS * sizeof(uint32_t) <= 640, "a larger row table may cost the headline kernel its fifth workgroup per CU: measure");
+
 }  // namespace hc

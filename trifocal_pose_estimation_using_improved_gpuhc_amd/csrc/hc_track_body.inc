@@ -66,6 +66,7 @@
         for (int q = 0; q < GM_WORDS; q++) s_rowc[q][threadIdx.x] = T->gm[q][threadIdx.x];
         s_rowc[GM_WORDS][threadIdx.x] = T->pat[threadIdx.x];
     }
+    if constexpr (LUFUSE) lu_rowtab_fill(threadIdx.x);   // the fused levels' row records (hc_lu_levels.hpp)
     __syncthreads();
     const bool rl = r < NV;
     wave_lds_sync();
