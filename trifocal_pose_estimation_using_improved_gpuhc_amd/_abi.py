@@ -390,6 +390,14 @@ LU_ROWTABLE_SIGNATURES = (
 )
 LU_ROW_FIELDS = ("member", "bound", "window", "partner", "place", "chain")
 
+# include/lu/hc_lu_compact_testing.h, the fused solve's compact row beside the
+# row records (tests/test_lu_compact_host.py); neither takes a stream
+LU_COMPACT_SIGNATURES = (
+    Sig("hc_lu_compact_column", _i, (_i, _i), True),
+    Sig("hc_trifocal_compact_rows_batched", _ST, (_i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, C.c_size_t), True),
+)
+LU_COMPACT_WIDTH = 16
+
 # include/eval/hc_eval_testing.h, the test hook of the tracking kernels' evaluations
 # beside the LU's: its table, bound and checked the same way
 # (tests/test_eval_cases_host.py)
@@ -425,7 +433,7 @@ def lib() -> C.CDLL:
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
         for s in SIGNATURES + P2C_SIGNATURES + REFINE_SIGNATURES + TOPK_SIGNATURES + LU_SIGNATURES + \
-                LU_ROWTABLE_SIGNATURES + EVAL_SIGNATURES + ADAPTIVE_SIGNATURES:
+                LU_ROWTABLE_SIGNATURES + LU_COMPACT_SIGNATURES + EVAL_SIGNATURES + ADAPTIVE_SIGNATURES:
             fn = getattr(L, s.name, None)
             if fn is None:
                 if s.optional:

@@ -74,18 +74,37 @@ __global__ void __launch_bounds__(WG_THREADS) k_cgesv_variant(int n, const cf *_
     const int r = lane & 31;
     const int sys = (blockIdx.x * WAVES_PER_WG + threadIdx.x / WAVE) * 2 + (lane >> 5);
     const bool ok = sys < n && r < NV;
-    cf rA[NV];
+    // FUSE: the row in its compact form (LuRowForm<true>, hc_lu_struct.hpp), as the tracker's gather
+    // leaves it: slot L takes A[r][the member the row's record names at level L] (a zero without
+    // one), columns 18..29 stand behind the slots.  The verdict is still taken on all 30 entries.
+    cf rA[LuRowForm<FUSE>::W];
     uint32_t nz = 0;
     pf2 sq = {0.0f, 0.0f};   // the entries' sums of squares, as eval_hx_terms_abs takes them
+    if constexpr (!FUSE) {
 #pragma unroll
-    for (int c = 0; c < NV; c++) {
-        rA[c] = ok ? A[((size_t)sys * NV + r) * NV + c] : cmk(0.0f, 0.0f);
-        if constexpr (!STRUCT) {
-            if (rA[c].x != 0.0f || rA[c].y != 0.0f) nz |= 1u << c;   // NaN counts as non-zero
+        for (int c = 0; c < NV; c++) {
+            rA[c] = ok ? A[((size_t)sys * NV + r) * NV + c] : cmk(0.0f, 0.0f);
+            if constexpr (!STRUCT) {
+                if (rA[c].x != 0.0f || rA[c].y != 0.0f) nz |= 1u << c;   // NaN counts as non-zero
+            }
+            if constexpr (ENTCHK) {
+                sq.x = __builtin_fmaf(rA[c].x, rA[c].x, sq.x);
+                sq.y = __builtin_fmaf(rA[c].y, rA[c].y, sq.y);
+            }
         }
-        if constexpr (ENTCHK) {
-            sq.x = __builtin_fmaf(rA[c].x, rA[c].x, sq.x);
-            sq.y = __builtin_fmaf(rA[c].y, rA[c].y, sq.y);
+    } else {
+        static_assert(STRUCT && ENTCHK, "the fused solve's mode");
+#pragma unroll
+        for (int c = 0; c < NV; c++) {
+            const cf a = ok ? A[((size_t)sys * NV + r) * NV + c] : cmk(0.0f, 0.0f);
+            if (c >= lu_first_unfused_step()) rA[LuRowForm<FUSE>::pos(c)] = a;
+            sq.x = __builtin_fmaf(a.x, a.x, sq.x);
+            sq.y = __builtin_fmaf(a.y, a.y, sq.y);
+        }
+#pragma unroll
+        for (int lv = 0; lv < LU_SLOTS; lv++) {
+            const int mem = (int)((lu_rowtab_lds()[lv * LU_REC_ROWS + r] >> LU_REC_MEMBER_AT) & 31u);
+            rA[lv] = ok && mem != LU_REC_NO_MEMBER ? A[((size_t)sys * NV + r) * NV + mem] : cmk(0.0f, 0.0f);
         }
     }
     bool ent_bad = false;
@@ -97,13 +116,19 @@ __global__ void __launch_bounds__(WG_THREADS) k_cgesv_variant(int n, const cf *_
     bool redo;
     cf x = lu_solve<false, LAT, STRUCT, ENTCHK, FUSE>(rA, rB, lane, pat, LB, scr, redo, __ballot(sys < n), ent_bad);
     if (__builtin_expect(redo, 0)) {
+        if constexpr (!FUSE) {
 #pragma unroll
-        for (int c = 0; c < NV; c++) rA[c] = ok ? A[((size_t)sys * NV + r) * NV + c] : cmk(0.0f, 0.0f);
-        x = lu_solve<true>(rA, rB, lane, pat, LB, scr, redo);
+            for (int c = 0; c < NV; c++) rA[c] = ok ? A[((size_t)sys * NV + r) * NV + c] : cmk(0.0f, 0.0f);
+            x = lu_solve<true>(rA, rB, lane, pat, LB, scr, redo);
+        } else {
+            cf rD[NV];   // (the dense solve takes the 30 columns)
+#pragma unroll
+            for (int c = 0; c < NV; c++) rD[c] = ok ? A[((size_t)sys * NV + r) * NV + c] : cmk(0.0f, 0.0f);
+            x = lu_solve<true>(rD, rB, lane, pat, LB, scr, redo);
+        }
     }
     if (ok) X[(size_t)sys * NV + r] = x;
 }
-
 
 // dH/dx, dH/dt, H at n points: one point per half-wave
 __global__ void __launch_bounds__(WG_THREADS) k_eval(int n, const Workspace *ws, const cf *__restrict__ X,
@@ -166,9 +191,14 @@ __global__ void __launch_bounds__(WG_THREADS) k_eval(int n, const Workspace *ws,
 // of workgroup i / 8, the slot a path of that wave half has in a tracker, so
 // the absolute offsets count from s_slot as they do there.  kind: 0 a
 // predictor stage (pred), 1 the corrector; a half without a point is not `act`.
-// redo: the values of the evaluations before the dense re-solve (:606-633),
+// redo: the values of the evaluations before the dense re-solve (:607-636),
 // after the entry block was overwritten as the sparse solve's scratch use may.
-template <bool ABSTAB>
+// CROW (hc_trifocal_compact_rows_batched, include/lu/hc_lu_compact_testing.h;
+// with ABSTAB): the stage's gather as the kernel with the fused solve runs it,
+// LUFUSE there: HX takes the rows in their compact form, n x 30 x
+// LU_COMPACT_W.  The dense re-solve's gather is the 30-column one in that
+// kernel too, which CROW = false returns; redo_vals is not read.
+template <bool ABSTAB, bool CROW = false>
 __global__ void __launch_bounds__(WG_THREADS) k_eval_variant(int n, int redo_vals, const Workspace *ws,
                                                              const cf *__restrict__ X, const cf *__restrict__ TGT,
                                                              const cf *__restrict__ DIF, const cf *__restrict__ SP,
@@ -235,10 +265,11 @@ __global__ void __launch_bounds__(WG_THREADS) k_eval_variant(int n, int redo_val
             if (!pred) rB = t;
         }
     }
-    cf rA[NV];                                                                    // :575-587
+    static_assert(ABSTAB || !CROW, "the compact row is gathered through the absolute tables");
+    cf rA[LuRowForm<CROW>::W];                                                    // :576-588
     if constexpr (ABSTAB) {
-        uint4 gmv[ABS_GM_Q];
-        const bool ent_ok = eval_hx_terms_abs(AT->hx[wv], l0, l16, AT->gm[wv], gmv);
+        uint4 gmv[CROW ? ABS_GMC_Q : ABS_GM_Q];
+        const bool ent_ok = eval_hx_terms_abs(AT->hx[wv], l0, l16, CROW ? AT->gmc[wv] : AT->gm[wv], gmv);
         if (act) ENT_OK[pi * 32 + r] = ent_ok ? 1 : 0;   // the lane's own verdict, before the tracker's ballot (:588)
         wave_lds_sync();
         gather_hx_abs(rA, l0, gmv);
@@ -246,6 +277,13 @@ __global__ void __launch_bounds__(WG_THREADS) k_eval_variant(int n, int redo_val
         eval_hx(rA, s_hx, s_hxd, &s_rowc[0][0], S, r_v);
     }
     wave_lds_sync();
+    if constexpr (CROW) {
+        if (act && rl) {
+#pragma unroll
+            for (int c = 0; c < LU_COMPACT_W; c++) HX[(pi * NV + r) * LU_COMPACT_W + c] = rA[c];
+            RHS[pi * NV + r] = rB;
+        }
+    } else {
     if (redo_vals) {
         // what lu_solve<false> may leave of the entry block (hc_slot.hpp): everything but the structural zero
         for (int k = r; k < ENT_CAP - 1; k += 32) S.ent[k] = cmk(__builtin_nanf(""), __builtin_nanf(""));
@@ -281,6 +319,7 @@ __global__ void __launch_bounds__(WG_THREADS) k_eval_variant(int n, int redo_val
 #pragma unroll
         for (int c = 0; c < NV; c++) HX[(pi * NV + r) * NV + c] = rA[c];
         RHS[pi * NV + r] = rB;
+    }
     }
 }
 

@@ -32,6 +32,7 @@
 #include <stddef.h>
 
 #include "hc_slot.hpp"
+#include "hc_lu_struct.hpp"   // the compact row's positions (AbsTables::gmc)
 
 namespace hc {
 
@@ -469,14 +470,20 @@ __device__ __forceinline__ cf eval_rhs(const uint2 *s_ht, const SlotLDS &S, int 
 //                j = HT_FULL: the x[w] of the light terms in .x, .y, .z
 //  htq[w][j][l]  .x qp, .y the coefficient as the float the term loop multiplies by (coef_ht's result)
 //  gm[w][q][l]   the gather addresses of columns 4q .. 4q + 3 of the lane's row
+//  gmc[w][q][l]  the same of positions 4q .. 4q + 3 of the row's compact form (hc_lu_struct.hpp
+//                lu_compact_col: the fused solve's row; the structural zero where the row has no
+//                column at a level)
 constexpr int ABS_WAVES = 4;
 constexpr int ABS_GM_Q = (NV + 3) / 4;
+constexpr int ABS_GMC_Q = LU_COMPACT_W / 4;
+static_assert(LU_COMPACT_W % 4 == 0, "whole words of four positions");
 static_assert(HT_HELP <= 3, "the light terms' x[w] share one word group");
 struct AbsTables {
     uint4 hx[ABS_WAVES][HX_SLOT_CAP][WAVE];
     uint4 ht[ABS_WAVES][HT_FULL + 1][WAVE];
     uint2 htq[ABS_WAVES][HT_FULL][WAVE];
     uint4 gm[ABS_WAVES][ABS_GM_Q][WAVE];
+    uint4 gmc[ABS_WAVES][ABS_GMC_Q][WAVE];
 };
 static_assert(2 * ABS_WAVES * sizeof(SlotLDS) < 65536, "absolute offsets stay in the DS offset range");
 // table words are read this many terms ahead of their term (L2 latency; 4 and 8 measured the same)
@@ -498,10 +505,12 @@ __device__ __forceinline__ HxOps hx_ops_abs(const char *l0, const uint4 &w) {
 // are stored instead of on the gathered rows: a row's non-zero entries are
 // exactly these, the rest of it are structural zeros.  Returns false where a
 // component sum of squares is not finite (an entry NaN, infinite or >= 2^64).
-// The gather's words (g, of gmw) are requested where the last term words have
-// been, so they arrive while the last terms are computed.
+// The gather's words (g, of gmw: the wave's gm block, or its gmc block for the
+// compact row) are requested where the last term words have been, so they
+// arrive while the last terms are computed.
+template <int GQ>
 __device__ __forceinline__ bool eval_hx_terms_abs(const uint4 (*hxw)[WAVE], char *l0, uint32_t l16,
-                                                  const uint4 (*gmw)[WAVE], uint4 (&g)[ABS_GM_Q]) {
+                                                  const uint4 (*gmw)[WAVE], uint4 (&g)[GQ]) {
     uint4 w[HX_SLOT_CAP];
 #pragma unroll
     for (int k = 0; k < EV_TAHEAD; k++) w[k] = abs_ld(hxw[k], l16);
@@ -514,7 +523,7 @@ __device__ __forceinline__ bool eval_hx_terms_abs(const uint4 (*hxw)[WAVE], char
         if (k + EV_TAHEAD < HX_SLOT_CAP) w[k + EV_TAHEAD] = abs_ld(hxw[k + EV_TAHEAD], l16);
         if (k == HX_SLOT_CAP - EV_TAHEAD) {
 #pragma unroll
-            for (int q = 0; q < ABS_GM_Q; q++) g[q] = abs_ld(gmw[q], l16);
+            for (int q = 0; q < GQ; q++) g[q] = abs_ld(gmw[q], l16);
         }
         if (k + EV_AHEAD < HX_SLOT_CAP) o[(k + EV_AHEAD) % (EV_AHEAD + 1)] = hx_ops_abs(l0, w[k + EV_AHEAD]);
         const HxOps &q = o[k % (EV_AHEAD + 1)];
@@ -530,10 +539,14 @@ __device__ __forceinline__ bool eval_hx_terms_abs(const uint4 (*hxw)[WAVE], char
     return sq.x + sq.y < __builtin_inff();
 }
 
-// the gather through the words eval_hx_terms_abs requested
-__device__ __forceinline__ void gather_hx_abs(cf (&rA)[NV], const char *l0, const uint4 (&g)[ABS_GM_Q]) {
+// the gather through the words eval_hx_terms_abs requested: the 30 columns
+// through gm's words, or the W = LU_COMPACT_W positions of the compact row
+// through gmc's
+template <int W, int GQ>
+__device__ __forceinline__ void gather_hx_abs(cf (&rA)[W], const char *l0, const uint4 (&g)[GQ]) {
+    static_assert(W <= 4 * GQ, "a word for every position");
 #pragma unroll
-    for (int c = 0; c < NV; c++) {
+    for (int c = 0; c < W; c++) {
         const uint4 &gw = g[c / 4];
         const pf2 v = ldp(l0, c % 4 == 0 ? gw.x : c % 4 == 1 ? gw.y : c % 4 == 2 ? gw.z : gw.w);
         rA[c] = cmk(v.x, v.y);

@@ -30,6 +30,7 @@
 #include "../../include/p2c/hc_trifocal_p2c.h"
 #include "../../include/lu/hc_lu_testing.h"
 #include "../../include/lu/hc_lu_rowtable_testing.h"
+#include "../../include/lu/hc_lu_compact_testing.h"
 #include "../../include/eval/hc_eval_testing.h"
 #include "../../include/adaptive/hc_trifocal_adaptive.h"
 
@@ -516,13 +517,14 @@ hcStatus hc_trifocal_eval_batched(int n, const int32_t *unified_index, const hcC
     return hc::launch_status(HC_ERROR_LAUNCH);
 }
 
-// tests only (include/eval/hc_eval_testing.h): k_eval_variant.  Blocks: the
-// workspace's status is read back once the kernel has run.
-hcStatus hc_trifocal_eval_variant_batched(int variant, unsigned flags, int n, const int32_t *unified_index,
-                                          const hcComplex *x, const hcComplex *target, const hcComplex *diff,
-                                          const hcComplex *start_params, const float *t, const uint8_t *kind,
-                                          hcComplex *Hx, hcComplex *rhs, uint8_t *ent_ok, void *workspace,
-                                          size_t workspace_bytes, hcStream stream) {
+// tests only (include/eval/hc_eval_testing.h, include/lu/hc_lu_compact_testing.h):
+// k_eval_variant; compact_rows: its CROW form, Hx then n x 30 x LU_COMPACT_W.
+// Blocks: the workspace's status is read back once the kernel has run.
+static hcStatus eval_variant_run(int variant, bool compact_rows, unsigned flags, int n, const int32_t *unified_index,
+                                 const hcComplex *x, const hcComplex *target, const hcComplex *diff,
+                                 const hcComplex *start_params, const float *t, const uint8_t *kind, hcComplex *Hx,
+                                 hcComplex *rhs, uint8_t *ent_ok, void *workspace, size_t workspace_bytes,
+                                 hcStream stream) {
     if (variant < 0 || variant >= HC_EVAL_VARIANT_COUNT || (flags & ~HC_EVAL_REDO) != 0u) return HC_ERROR_INVALID_VALUE;
     const bool abs_tables = variant == HC_EVAL_VARIANT_ABS;
     if (n < 0 || (n > 0 && (!unified_index || !x || !target || !diff || !start_params || !t || !kind || !Hx || !rhs ||
@@ -539,7 +541,11 @@ hcStatus hc_trifocal_eval_variant_batched(int variant, unsigned flags, int n, co
     const int per = 2 * hc::WAVES_PER_WG;
     const dim3 grid((n + per - 1) / per), block(hc::WG_THREADS);
     const int redo = (flags & HC_EVAL_REDO) ? 1 : 0;
-    if (abs_tables)
+    if (compact_rows)
+        hipLaunchKernelGGL((hc::k_eval_variant<true, true>), grid, block, 0, s, n, redo, ws, (const hc::cf *)x,
+                           (const hc::cf *)target, (const hc::cf *)diff, (const hc::cf *)start_params, t, kind,
+                           (hc::cf *)Hx, (hc::cf *)rhs, ent_ok);
+    else if (abs_tables)
         hipLaunchKernelGGL(hc::k_eval_variant<true>, grid, block, 0, s, n, redo, ws, (const hc::cf *)x,
                            (const hc::cf *)target, (const hc::cf *)diff, (const hc::cf *)start_params, t, kind,
                            (hc::cf *)Hx, (hc::cf *)rhs, ent_ok);
@@ -558,6 +564,24 @@ hcStatus hc_trifocal_eval_variant_batched(int variant, unsigned flags, int n, co
     const unsigned status = ctl[offsetof(hc::Workspace, status) / sizeof(unsigned)];
     if (status == 0u) return HC_SUCCESS;
     return status == (unsigned)HC_ERROR_TABLE ? HC_ERROR_TABLE : HC_ERROR_DEVICE;
+}
+
+hcStatus hc_trifocal_eval_variant_batched(int variant, unsigned flags, int n, const int32_t *unified_index,
+                                          const hcComplex *x, const hcComplex *target, const hcComplex *diff,
+                                          const hcComplex *start_params, const float *t, const uint8_t *kind,
+                                          hcComplex *Hx, hcComplex *rhs, uint8_t *ent_ok, void *workspace,
+                                          size_t workspace_bytes, hcStream stream) {
+    return eval_variant_run(variant, false, flags, n, unified_index, x, target, diff, start_params, t, kind, Hx, rhs,
+                            ent_ok, workspace, workspace_bytes, stream);
+}
+
+hcStatus hc_trifocal_compact_rows_batched(int n, const int32_t *unified_index, const hcComplex *x,
+                                          const hcComplex *target, const hcComplex *diff,
+                                          const hcComplex *start_params, const float *t, const uint8_t *kind,
+                                          hcComplex *rows, hcComplex *rhs, uint8_t *ent_ok, void *workspace,
+                                          size_t workspace_bytes) {
+    return eval_variant_run(HC_EVAL_VARIANT_ABS, true, 0u, n, unified_index, x, target, diff, start_params, t, kind,
+                            rows, rhs, ent_ok, workspace, workspace_bytes, nullptr);
 }
 
 hcStatus hc_trifocal_p2c_eval_batched(int n, const int32_t *hx_index, const int32_t *ht_index, const hcComplex *x,
@@ -668,6 +692,12 @@ int hc_lu_group_class(int step, int group) {
     if (step < 0 || step >= hc::NV - 1 || group < 0 || group >= hc::LuChunks::count(step)) return -1;
     return hc::lu_group_class(step, group);
 }
+// tests only (include/lu/hc_lu_compact_testing.h): the compact row's column map
+static_assert(HC_LU_COMPACT_WIDTH == hc::LU_COMPACT_W, "the header's row width");
+int hc_lu_compact_column(int row, int position) {
+    if (row < 0 || row >= hc::NV || position < 0 || position >= hc::LU_COMPACT_W) return -2;
+    return hc::lu_compact_col(row, position);
+}
 // tests only (include/lu/hc_lu_rowtable_testing.h): a field of the fused levels'
 // row records, decoded from the table the kernels copy to LDS (LU_ROWTAB)
 int hc_lu_row_field(int level, int row, int field) {
@@ -717,7 +747,8 @@ void hc_trifocal_set_small_launch(int mode) {
 void hc_trifocal_set_retry_reuse(int on) { hc::g_retry_reuse.store(on ? 1 : 0, std::memory_order_relaxed); }
 
 const char *hc_trifocal_version(void) {
-    return "hc_trifocal gfx950 v10.12 (2 paths/wave, structurally sparse LDS-broadcast LU with lean pivot steps fused by level, the levels' per-row constants and row labels read from LDS tables, "
+    return "hc_trifocal gfx950 v10.13 (2 paths/wave, structurally sparse LDS-broadcast LU with lean pivot steps fused by level, the levels' per-row constants and row labels read from LDS tables, "
+           "the fused solve's row kept in 16 positions (its column of each level, then columns 18..29), "
            "one exec region per pivot step for the eligible rows with the column groups through scratch windows, "
            "column groups by structural class (never-fillable groups untested, always-live groups unconditional), "
            "pivot search narrowed to the candidate rows' DPP group "

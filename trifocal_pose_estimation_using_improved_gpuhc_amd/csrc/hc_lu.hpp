@@ -1,10 +1,12 @@
 // hc_lu.hpp -- the tracker's batched 30x30 complex LU solve, two systems per
-// wavefront (one per 32-lane half; lane r owns row r in 60 VGPRs).
+// wavefront (one per 32-lane half; lane r owns row r in 60 VGPRs, the fused
+// solve in the 32 of its compact form).
 //
 // The LU's headers, all part of this one:
 //   hc_lu_struct.hpp  what is known at compile time: column groups, the fill-in
 //                     bound and group classes, search spans, the levels of
-//                     independent steps, the scratch layout (no device code)
+//                     independent steps, the scratch layout, the fused solve's
+//                     compact row form (no device code)
 //   hc_lu_diag.hpp    the counters of the diagnostic builds (HC_LU_WORK*, ...)
 //   hc_lu.hpp         the primitives, one column group's store / load / update,
 //                     the three pivot steps (batched, tested, dense), the pivot
@@ -215,22 +217,26 @@ __device__ __forceinline__ bool group_live(uint32_t pmw, uint32_t gb) {
 // One column group, columns J .. J + N - 1 (N = 1 or 2), of every mode: a lane
 // writes its row's group to a row buffer or scratch window w, reads the pivot
 // row's group from p into u, and takes a_j -= l * u_j.
-template <int J, int N>
-__device__ __forceinline__ void grp_store(cf *w, const cf (&rA)[NV]) {
-    if constexpr (N == 1) w[J] = rA[J];
-    else st4(&w[J], rA[J], rA[J + 1]);
+// (P: the register position of column J, LuRowForm::pos; the buffer and the
+// windows are indexed by J in every row form)
+template <int J, int N, int P = J, int W>
+__device__ __forceinline__ void grp_store(cf *w, const cf (&rA)[W]) {
+    static_assert(P >= 0 && P + N <= W, "the group lies inside the row");
+    if constexpr (N == 1) w[J] = rA[P];
+    else st4(&w[J], rA[P], rA[P + 1]);
 }
 template <int J, int N>
 __device__ __forceinline__ void grp_load(const cf *p, cf *u) {
     if constexpr (N == 1) u[0] = p[J];
     else ld4(&p[J], u[0], u[1]);
 }
-template <int J, int N>
-__device__ __forceinline__ void grp_update(cf (&rA)[NV], const pf2 &l, const cf *u) {
+template <int J, int N, int P = J, int W>
+__device__ __forceinline__ void grp_update(cf (&rA)[W], const pf2 &l, const cf *u) {
+    static_assert(P >= 0 && P + N <= W, "the group lies inside the row");
 #pragma unroll
     for (int q = 0; q < N; q++) {
-        const pf2 v = pcmsub(pf2{rA[J + q].x, rA[J + q].y}, l, pf2{u[q].x, u[q].y});
-        rA[J + q] = cmk(v.x, v.y);
+        const pf2 v = pcmsub(pf2{rA[P + q].x, rA[P + q].y}, l, pf2{u[q].x, u[q].y});
+        rA[P + q] = cmk(v.x, v.y);
     }
 }
 
@@ -371,25 +377,25 @@ __device__ __forceinline__ void lu_step_batched(cf (&rA)[NV], cf &rB, int &rowid
 // -5 %; a variant whose pivot row also went through a window, its address
 // exchanged with 1/pivot, issued fewer instructions and ran 1 % slower,
 // profiles/r5h_ab_lu_windows.jsonl.)
-template <int I, int K, bool STRUCT>
-__device__ __forceinline__ void lu_group_elig(cf (&rA)[NV], const pf2 &l, uint32_t pmw, uint32_t gb, cf *wrow,
-                                              const LUBuf &L HC_LU_WORK_ARG) {
+template <int I, int K, bool STRUCT, bool COMPACT>
+__device__ __forceinline__ void lu_group_elig(cf (&rA)[LuRowForm<COMPACT>::W], const pf2 &l, uint32_t pmw, uint32_t gb,
+                                              cf *wrow, const LUBuf &L HC_LU_WORK_ARG) {
     using C = LuChunks;
     if constexpr (K < C::count(I)) {
-        constexpr int J = C::start(I, K), N = C::len(I, K);
+        constexpr int J = C::start(I, K), N = C::len(I, K), P = LuRowForm<COMPACT>::pos(J);
         constexpr int CLS = STRUCT ? lu_group_class(I, K) : GRP_TESTED;
         if (CLS != GRP_DEAD && (CLS == GRP_ALWAYS || __builtin_expect(group_live<I, K>(pmw, gb), 1))) {
-            grp_store<J, N>(wrow, rA);
+            grp_store<J, N, P>(wrow, rA);
             wave_lds_sync();
             HC_LU_WORK(N);
             HC_DIAG_LIVE_HIT(I, K);
             HC_LU_WORK_GROUP();
             cf u[N];
             grp_load<J, N>(L.row, u);
-            grp_update<J, N>(rA, l, u);
+            grp_update<J, N, P>(rA, l, u);
         }
         __builtin_amdgcn_sched_barrier(0);
-        lu_group_elig<I, K + 1, STRUCT>(rA, l, pmw, gb, wrow, L HC_LU_WORK_PASS);
+        lu_group_elig<I, K + 1, STRUCT, COMPACT>(rA, l, pmw, gb, wrow, L HC_LU_WORK_PASS);
     }
 }
 // The sparse step that tests its column groups: the throughput tracker's
@@ -399,8 +405,8 @@ __device__ __forceinline__ void lu_group_elig(cf (&rA)[NV], const pf2 &l, uint32
 // and rowid, the pivot lane to the buffer, the others to their scratch windows
 // -- no exec region, at the price of LDS bandwidth
 // (profiles/r5m_ab_lu_x.jsonl: lone sample -2 %, loaded launch +0.8 %).
-template <int I, bool X1, bool STRUCT>
-__device__ __forceinline__ void lu_step_tested(cf (&rA)[NV], cf &rB, int &rowid, uint32_t &pat, PivF &my, LUBuf &L,
+template <int I, bool X1, bool STRUCT, bool COMPACT>
+__device__ __forceinline__ void lu_step_tested(cf (&rA)[LuRowForm<COMPACT>::W], cf &rB, int &rowid, uint32_t &pat, PivF &my, LUBuf &L,
                                                cf *scr, bool is_piv, int pl0, int pl1, pf2 reg_s, pf2 oo_s,
                                                bool elig HC_LU_WORK_ARG) {
     // structural patterns of the two pivot rows (wave-uniform)
@@ -451,12 +457,13 @@ __device__ __forceinline__ void lu_step_tested(cf (&rA)[NV], cf &rB, int &rowid,
         // (the pivot lane's multiplier is zeroed by two selects: reading an
         // exact zero from a zero slot instead held one more address in a VGPR
         // across the solve: 11 -> 20 spills; round 6)
-        const pf2 lq = pcmul(pf2{rA[I].x, rA[I].y}, pf2{reg.x, reg.y});
+        constexpr int PI = LuRowForm<COMPACT>::pos(I);
+        const pf2 lq = pcmul(pf2{rA[PI].x, rA[PI].y}, pf2{reg.x, reg.y});
         const pf2 lp = {is_piv ? 0.0f : lq.x, is_piv ? 0.0f : lq.y};
         const pf2 bp = pcmsub(pf2{rB.x, rB.y}, lp, pf2{sB0.x, sB0.y});
         rB = cmk(bp.x, bp.y);
         pat |= (uint32_t)__builtin_amdgcn_sbfe((int)pat, I, 1) & pmw;   // v_bfe_i32 + v_and_or_b32
-        lu_group_elig<I, 0, STRUCT>(rA, lp, pmw, gb, wrow, L HC_LU_WORK_PASS);
+        lu_group_elig<I, 0, STRUCT, COMPACT>(rA, lp, pmw, gb, wrow, L HC_LU_WORK_PASS);
     }
 }
 
@@ -530,21 +537,25 @@ namespace hc {
 // Pivot steps I .. NV - 1, one after the other: the pivot search, then the
 // step of the solve's mode.  !DENSE: a pivot outside the fast reciprocal range
 // sets `redo` (the solve goes on with garbage, the caller discards it and
-// solves densely).
-template <int I, bool DENSE, int LAT, bool STRUCT>
-__device__ __forceinline__ void lu_forward(cf (&rA)[NV], cf &rB, int &rowid, uint32_t &pat, int lane, int r, int hb,
+// solves densely).  COMPACT: the row form (LuRowForm, hc_lu_struct.hpp; the
+// fused solve's sequential steps, whose columns all lie behind the slots).
+template <int I, bool DENSE, int LAT, bool STRUCT, bool COMPACT = false>
+__device__ __forceinline__ void lu_forward(cf (&rA)[LuRowForm<COMPACT>::W], cf &rB, int &rowid, uint32_t &pat, int lane, int r, int hb,
                                            bool row_lane, PivF &my, LUBuf &L, cf *scr, bool &redo,
                                            unsigned long long elig_m HC_LU_WORK_ARG) {
+    static_assert(!COMPACT || (!DENSE && LAT == 0 && STRUCT && I >= lu_first_unfused_step()),
+                  "the compact row is the fused solve's");
     if constexpr (I < NV) {
         HC_ISA_MARK_I("lu_search", I);
-        const float v = __builtin_fabsf(rA[I].x) + __builtin_fabsf(rA[I].y);          // :55
+        constexpr int PI = LuRowForm<COMPACT>::pos(I);
+        const float v = __builtin_fabsf(rA[PI].x) + __builtin_fabsf(rA[PI].y);          // :55
         // 1 / own candidate as cuCdivf(1, a_rI) (:66, :84), off the step's critical path:
         // the pivot lane's is the step's 1/pivot (same ops on the same value)
         pf2 reg_s, oo_s;
         if constexpr (!DENSE) {
-            reg_s = recip_fast(pf2{rA[I].x, rA[I].y}, v, oo_s);
+            reg_s = recip_fast(pf2{rA[PI].x, rA[PI].y}, v, oo_s);
         } else {
-            const divf f = cdiv_factors(rA[I]);
+            const divf f = cdiv_factors(rA[PI]);
             const cf rg = (v == 0.0f) ? cmk(1.0f, 0.0f) : cdiv_apply(cmk(1.0f, 0.0f), f);
             reg_s = pf2{rg.x, rg.y};
             oo_s = pf2{f.o1, f.o2};
@@ -645,9 +656,9 @@ __device__ __forceinline__ void lu_forward(cf (&rA)[NV], cf &rB, int &rowid, uin
         HC_ISA_MARK_I("lu_pattern", I);
         if constexpr (DENSE) lu_step_dense<I>(rA, rB, rowid, my, L, is_piv, reg_s, oo_s, elig HC_LU_WORK_PASS);
         else if constexpr (LAT > 0 && STRUCT) lu_step_batched<I, LAT>(rA, rB, rowid, my, L, scr, is_piv, reg_s, oo_s, elig);
-        else lu_step_tested<I, (LAT > 0), STRUCT>(rA, rB, rowid, pat, my, L, scr, is_piv, pl0, pl1, reg_s, oo_s,
-                                                  elig HC_LU_WORK_PASS);
-        lu_forward<I + 1, DENSE, LAT, STRUCT>(rA, rB, rowid, pat, lane, r, hb, row_lane, my, L, scr, redo,
+        else lu_step_tested<I, (LAT > 0), STRUCT, COMPACT>(rA, rB, rowid, pat, my, L, scr, is_piv, pl0, pl1, reg_s, oo_s,
+                                                           elig HC_LU_WORK_PASS);
+        lu_forward<I + 1, DENSE, LAT, STRUCT, COMPACT>(rA, rB, rowid, pat, lane, r, hb, row_lane, my, L, scr, redo,
                                               elig_m & ~piv_m HC_LU_WORK_PASS);
     }
 }
@@ -656,7 +667,7 @@ __device__ __forceinline__ void lu_forward(cf (&rA)[NV], cf &rB, int &rowid, uin
 // first step no level holds.  A rare condition inside a level sets `redo` and
 // ends the elimination.
 template <int LV>
-__device__ __forceinline__ void lu_forward_fused(cf (&rA)[NV], cf &rB, int &rowid, uint32_t &pat, int lane, int r, int hb,
+__device__ __forceinline__ void lu_forward_fused(cf (&rA)[LU_COMPACT_W], cf &rB, int &rowid, uint32_t &pat, int lane, int r, int hb,
                                                  bool row_lane, PivF &my, LUBuf &L, cf *scr, bool &redo,
                                                  unsigned long long elig_m HC_LU_WORK_ARG) {
     if constexpr (LV < LU_LEVELS.nlevels) {
@@ -670,7 +681,7 @@ __device__ __forceinline__ void lu_forward_fused(cf (&rA)[NV], cf &rB, int &rowi
         }
         lu_forward_fused<LV + 1>(rA, rB, rowid, pat, lane, r, hb, row_lane, my, L, scr, redo, elig_m HC_LU_WORK_PASS);
     } else {
-        lu_forward<lu_first_unfused_step(), false, 0, true>(rA, rB, rowid, pat, lane, r, hb, row_lane, my, L, scr, redo,
+        lu_forward<lu_first_unfused_step(), false, 0, true, true>(rA, rB, rowid, pat, lane, r, hb, row_lane, my, L, scr, redo,
                                                            elig_m HC_LU_WORK_PASS);
     }
 }
@@ -685,14 +696,17 @@ __device__ __forceinline__ void lu_forward_fused(cf (&rA)[NV], cf &rB, int &rowi
 // J < I may update it unmasked.
 // LAST: the position the walk ends with (18 in lu_solve<..., FUSE>, whose
 // positions 17..0 run level by level: lu_backward_fused, hc_lu_levels.hpp).
-template <int I, int LAST = 0>
-__device__ __forceinline__ void lu_backward(const cf (&rA)[NV], cf &rB, int rowid, const PivF &my, pf2 &res) {
+template <int I, int LAST = 0, bool COMPACT = false>
+__device__ __forceinline__ void lu_backward(const cf (&rA)[LuRowForm<COMPACT>::W], cf &rB, int rowid, const PivF &my,
+                                            pf2 &res) {
+    static_assert(!COMPACT || LAST >= lu_first_unfused_step(), "the compact row's low positions run level by level");
     if constexpr (I >= LAST) {
         HC_ISA_MARK_I("lu_back", I);
+        constexpr int PI = LuRowForm<COMPACT>::pos(I);
         const unsigned long long own = __builtin_amdgcn_ballot_w64(rowid == I);
         const int o0 = __builtin_ctz((unsigned)own);          // one owner per half
         const int o1 = 32 + __builtin_ctz((unsigned)(own >> 32));
-        const pf2 q = pcdiv_apply(pf2{rB.x, rB.y}, pf2{rA[I].x, rA[I].y}, my);
+        const pf2 q = pcdiv_apply(pf2{rB.x, rB.y}, pf2{rA[PI].x, rA[PI].y}, my);
         const float x0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(q.x), o0));
         const float y0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(q.y), o0));
         const float x1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(q.x), o1));
@@ -711,10 +725,10 @@ __device__ __forceinline__ void lu_backward(const cf (&rA)[NV], cf &rB, int rowi
         // (no compare, no exec region): the rows at or below I are solved, so
         // their rB is dead (profiles/r3aa_ab_backsub_unmasked.jsonl)
         if constexpr (I > 0) {
-            const pf2 w = pcmsub(pf2{rB.x, rB.y}, xv, pf2{rA[I].x, rA[I].y});
+            const pf2 w = pcmsub(pf2{rB.x, rB.y}, xv, pf2{rA[PI].x, rA[PI].y});
             rB = cmk(w.x, w.y);
         }
-        lu_backward<I - 1, LAST>(rA, rB, rowid, my, res);
+        lu_backward<I - 1, LAST, COMPACT>(rA, rB, rowid, my, res);
     }
 }
 
@@ -746,7 +760,11 @@ constexpr LuMode lu_mode(bool ABORT, bool ARCH, int LULAT, bool LUS) {
 // ENTCHK: the caller has made the finiteness check on the entries it gathered
 // the rows from (eval_hx_terms_abs) and passes the wave-uniform verdict in
 // ent_bad; the row loop below is left out.
-// FUSE (the throughput tracker's solve): the fusable steps run level by level
+// FUSE (the throughput tracker's solve): the row comes in its compact form,
+// LU_COMPACT_W positions (LuRowForm<true>, hc_lu_struct.hpp: the row's column
+// of each level, then columns 18..29; every other instantiation takes the 30
+// columns in place, and `pattern` keeps true column numbers in both); the
+// fusable steps run level by level
 // (lu_forward_fused), and so do their positions of the back substitution
 // (lu_backward_fused); scratch then has LU_SCRATCH_FUSED_CF entries, and a
 // rare condition inside a level or a solution that is not finite reports
@@ -754,7 +772,7 @@ constexpr LuMode lu_mode(bool ABORT, bool ARCH, int LULAT, bool LUS) {
 // count_mask: diagnostic builds (HC_DIAG_LUWORK), the lanes whose executed
 // work is counted; call sites pass HC_LU_COUNT(mask).
 template <bool DENSE, int LAT = 0, bool STRUCT = false, bool ENTCHK = false, bool FUSE = false>
-__device__ __forceinline__ cf lu_solve(cf (&rA)[NV], cf rB, int lane, uint32_t pattern, LUBuf &L, cf *scratch,
+__device__ __forceinline__ cf lu_solve(cf (&rA)[LuRowForm<FUSE>::W], cf rB, int lane, uint32_t pattern, LUBuf &L, cf *scratch,
                                       bool &redo, unsigned long long count_mask = ~0ull, bool ent_bad = false) {
     static_assert(!FUSE || (!DENSE && LAT == 0 && STRUCT && ENTCHK), "the fused levels belong to the throughput tracker's solve");
     (void)count_mask;
@@ -824,7 +842,7 @@ __device__ __forceinline__ cf lu_solve(cf (&rA)[NV], cf rB, int lane, uint32_t p
     HC_ISA_MARK("lu_back_init");
     pf2 res = {0.0f, 0.0f};
     if constexpr (FUSE) {
-        lu_backward<NV - 1, lu_first_unfused_step()>(rA, rB, rowid, my, res);
+        lu_backward<NV - 1, lu_first_unfused_step(), true>(rA, rB, rowid, my, res);
         lu_backward_fused<LU_LEVELS.nlevels - 1>(rA, rB, rowid, my, L, r, res);
         // the levels skip the rows that take x_J * 0, which is a zero only for
         // a finite x_J: a solve with a non-finite x goes to the dense one

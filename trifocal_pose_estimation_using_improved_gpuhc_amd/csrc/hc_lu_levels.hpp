@@ -10,9 +10,10 @@
 //  * the row's record: what the row is to the level -- its chain and member,
 //    its chain's window, its partner across a 6-row chain, its place in its
 //    triple -- is one word of LU_ROWTAB (hc_lu_struct.hpp), read from LDS;
-//  * candidate: the lane's entry in its chain's column (a select over the
-//    level's members, one compare with the record's chain number each);
-//    1 / candidate once;
+//  * candidate: the lane's entry in its chain's column, which the compact row
+//    (LuRowForm<true>, hc_lu_struct.hpp) keeps at position LV whatever the
+//    chain (until v10.12 a select over the level's members in a 30-column
+//    row, one compare with the record's chain number each); 1 / candidate once;
 //  * search: the maximum key over the lane's own chain -- inside the triple
 //    with four DPP wave shifts selected by the lane's place in it, across the two
 //    triples of a 6-row chain with one ds_bpermute (rows 15..17 cross the
@@ -24,8 +25,11 @@
 //    scratch[LU_CHAIN_WIN0 + 2k + J] for column pair J; its pivot lane writes
 //    there, every other eligible lane to its own window scratch[2r + J] as in a
 //    single step (so the store needs no exec switch), and every lane reads its
-//    own chain's window.  1/pivot and the rhs travel in pair 0.  The column
-//    pairs are those that hold a column of LU_LEVELS.cols, untested: where a
+//    own chain's window.  1/pivot and the rhs travel in pair 0.  The pairs
+//    are those of positions that hold a column of LU_LEVELS.cols (lvl_groups;
+//    the rows of a chain name the same columns in the slots above the level, so
+//    a slot pair is the same column pair to the pivot row and to the rows that
+//    take it), untested: where a
 //    chain's pivot row has no such column it holds an exact zero (equivalence
 //    3 of DESIGN.md §4).  A pair may hold a member's own pivot column: the
 //    rows below then take a_I - l * pivot there, a value nothing reads (column
@@ -51,17 +55,6 @@ __device__ __forceinline__ uint32_t *lu_rowtab_lds() {
 }
 __device__ __forceinline__ void lu_rowtab_fill(int tid) {
     if (tid < LU_REC_WORDS) lu_rowtab_lds()[tid] = LU_ROWTAB.w[tid];
-}
-// the candidate of a lane whose record names chain kk (no chain: it stays zero)
-template <int LV, int K>
-__device__ __forceinline__ void lvl_pick(const cf (&rA)[NV], pf2 &c, int kk) {
-    if constexpr (K < lu_level_count(LV)) {
-        constexpr int I = lu_level_member(LV, K);
-        const bool in = kk == K;
-        c.x = in ? rA[I].x : c.x;
-        c.y = in ? rA[I].y : c.y;
-        lvl_pick<LV, K + 1>(rA, c, kk);
-    }
 }
 
 // The members' relabels (:70-82): the pivot lane takes label I, the lane that
@@ -100,31 +93,45 @@ __device__ __forceinline__ void lvl_relabel(int &rowid, int mem, bool is_piv, un
     }
     rowid = is_piv ? mem : rowid;
 }
-// the level's column pairs J, J + 1 (J even) inside the eligible rows' region
-template <int LV, int J>
-__device__ __forceinline__ void lvl_groups(cf (&rA)[NV], const pf2 &l, cf *wrow, const cf *cw) {
-    if constexpr (J < NV) {
-        if constexpr (((LU_LEVELS.cols[LV] >> J) & 3u) != 0u) {
-            grp_store<J, 2>(wrow, rA);
+// The level's pairs of positions P, P + 1 (P even) of the compact row, inside
+// the eligible rows' region: the slot pairs that hold a slot the level can
+// change (lu_level_slots), then the pairs of columns 18.. that hold a column of
+// LU_LEVELS.cols.  A slot pair travels through entries LVL_SLOT_J0 + P of the
+// windows (entry 0 holds 1/pivot and the rhs), a pair of columns J, J + 1
+// through entries J as in a sequential step.
+constexpr int LVL_SLOT_J0 = 2;
+template <int LV, int P>
+__device__ __forceinline__ void lvl_groups(cf (&rA)[LU_COMPACT_W], const pf2 &l, cf *wrow, const cf *cw) {
+    if constexpr (P < LU_COMPACT_W) {
+        constexpr int C0 = lu_first_unfused_step() + P - LU_SLOTS;   // (P >= LU_SLOTS: the pair's first column)
+        constexpr bool RUN = P < LU_SLOTS ? ((lu_level_slots(LV) >> P) & 3u) != 0u : ((LU_LEVELS.cols[LV] >> C0) & 3u) != 0u;
+        if constexpr (RUN) {
+            constexpr int J = P < LU_SLOTS ? LVL_SLOT_J0 + P : C0;
+            grp_store<J, 2, P>(wrow, rA);
             wave_lds_sync();
             cf u[2];
             grp_load<J, 2>(cw, u);
-            grp_update<J, 2>(rA, l, u);
+            grp_update<J, 2, P>(rA, l, u);
             __builtin_amdgcn_sched_barrier(0);
         }
-        lvl_groups<LV, J + 2>(rA, l, wrow, cw);
+        lvl_groups<LV, P + 2>(rA, l, wrow, cw);
     }
+}
+constexpr int lvl_pairs(int lv) {   // the pairs lvl_groups<lv> runs
+    int n = 0;
+    for (int p = 0; p < LU_SLOTS; p += 2) n += ((lu_level_slots(lv) >> p) & 3u) != 0u;
+    for (int j = lu_first_unfused_step(); j < NV; j += 2) n += ((LU_LEVELS.cols[lv] >> j) & 3u) != 0u;
+    return n;
 }
 // returns false when the level met a rare condition (nothing is changed then)
 template <int LV>
-__device__ __forceinline__ bool lu_level(cf (&rA)[NV], cf &rB, int &rowid, uint32_t &pat, int r, int hb, PivF &my,
+__device__ __forceinline__ bool lu_level(cf (&rA)[LU_COMPACT_W], cf &rB, int &rowid, uint32_t &pat, int r, int hb, PivF &my,
                                          LUBuf &L, cf *scr, unsigned long long &elig_m HC_LU_WORK_ARG) {
     constexpr int CNT = lu_level_count(LV), I0 = lu_level_member(LV, 0);
     constexpr uint32_t ROWS = LU_LEVELS.rows[LV];
     HC_ISA_MARK_I("lu_search", I0);
-    pf2 c = {0.0f, 0.0f};
+    const pf2 c = {rA[LV].x, rA[LV].y};   // the row's slot of the level (a zero outside the level's rows)
     const uint32_t rec = lu_rowtab_lds()[LV * LU_REC_ROWS + r];
-    lvl_pick<LV, 0>(rA, c, (int)((rec >> LU_REC_CHAIN_AT) & 15u));
     const float v = __builtin_fabsf(c.x) + __builtin_fabsf(c.y);          // :55
     pf2 oo_s;
     const pf2 reg_s = recip_fast(c, v, oo_s);
@@ -171,9 +178,8 @@ __device__ __forceinline__ bool lu_level(cf (&rA)[NV], cf &rB, int &rowid, uint3
     lvl_relabel<LV>(rowid, mem, is_piv, elig_m & ~m, L);
     HC_ISA_MARK_I("lu_update", I0);
 #ifdef HC_DIAG_LUWORK
-    {   // the level's column pairs x the eligible rows below the pivots (wave-uniform)
-        int pairs = 0;
-        for (int j = 0; j < NV; j += 2) pairs += ((LU_LEVELS.cols[LV] >> j) & 3u) != 0u;
+    {   // the level's pairs x the eligible rows below the pivots (wave-uniform)
+        constexpr int pairs = lvl_pairs(LV);
         lu_work_acc.acc += 2ull * (unsigned long long)pairs *
                            (unsigned long long)__builtin_popcountll(lv_elig & lu_work_acc.mask & ~m);
         lu_work_acc.groups += (unsigned long long)pairs;
@@ -199,8 +205,8 @@ __device__ __forceinline__ bool lu_level(cf (&rA)[NV], cf &rB, int &rowid, uint3
 // where J is an ancestor of I in the forest (lu_back_chains_nested,
 // hc_lu_struct.hpp), and every lane has at most one member per level, so a lane
 // does for its own chain's column what lu_backward<I> does for column I:
-//  * select: its entry in the member's column and the member's position, from
-//    the row's record as in lu_level;
+//  * select: its entry in the member's column, slot LV of the compact row, and
+//    the member's position, from the row's record as in lu_level;
 //  * divide: cuCdivf(b, pivot) with the factors it kept, once per level; the
 //    owner's (the lane whose label is its member, which lvl_relabel gave the
 //    member's pivot lane: its b is final, every position above 17 and every
@@ -219,11 +225,11 @@ __device__ __forceinline__ bool lu_level(cf (&rA)[NV], cf &rB, int &rowid, uint3
 // Level 0 has nothing left to update: after its broadcast the lanes r < 18 read
 // the x_r they return.
 template <int LV>
-__device__ __forceinline__ void lu_back_level(const cf (&rA)[NV], cf &rB, int rowid, const PivF &my, LUBuf &L, int r) {
+__device__ __forceinline__ void lu_back_level(const cf (&rA)[LU_COMPACT_W], cf &rB, int rowid, const PivF &my, LUBuf &L,
+                                              int r) {
     HC_ISA_MARK_I("lu_back_level", LV);
-    pf2 c = {0.0f, 0.0f};
+    const pf2 c = {rA[LV].x, rA[LV].y};
     const uint32_t rec = lu_rowtab_lds()[LV * LU_REC_ROWS + r];
-    lvl_pick<LV, 0>(rA, c, (int)((rec >> LU_REC_CHAIN_AT) & 15u));
     const int mem = (int)((rec >> LU_REC_MEMBER_AT) & 31u);   // (LU_REC_NO_MEMBER outside the level: no row's label)
     const pf2 q = pcdiv_apply(pf2{rB.x, rB.y}, c, my);
     if (rowid == mem) L.row[mem] = cmk(q.x, q.y);   // mem is one of the level's members: inside row[0..17]
@@ -239,7 +245,7 @@ __device__ __forceinline__ void lu_back_level(const cf (&rA)[NV], cf &rB, int ro
 // levels LV .. 0, then x_r into the lanes r < 18 (lanes 18..29 hold theirs from
 // the sequential positions)
 template <int LV>
-__device__ __forceinline__ void lu_backward_fused(const cf (&rA)[NV], cf &rB, int rowid, const PivF &my, LUBuf &L, int r,
+__device__ __forceinline__ void lu_backward_fused(const cf (&rA)[LU_COMPACT_W], cf &rB, int rowid, const PivF &my, LUBuf &L, int r,
                                                   pf2 &res) {
     if constexpr (LV >= 0) {
         lu_back_level<LV>(rA, rB, rowid, my, L, r);

@@ -1,10 +1,11 @@
 // hc_lu_struct.hpp -- what the tracker LU (hc_lu.hpp) knows about this problem's
 // Jacobian at compile time: the column groups of a pivot step, the symbolic
 // fill-in bound and the group classes it gives, the span of each step's pivot
-// search, the levels of independent pivot steps with their chains, and the
-// layout of the solve's LDS scratch.  Host-evaluable constants and their
-// static_asserts only, no device code: the hc_lu_* test exports of
-// hc_kernels.hip and k_prep_tables' structure check read nothing else of the LU.
+// search, the levels of independent pivot steps with their chains, the layout
+// of the solve's LDS scratch, and the row forms of the solve modes (LuRowForm).
+// Host-evaluable constants and their static_asserts only, no device code: the
+// hc_lu_* test exports of hc_kernels.hip and k_prep_tables' structure check
+// read nothing else of the LU.
 #pragma once
 
 #include <initializer_list>
@@ -345,5 +346,71 @@ static_assert(LU_LEVELS.nlevels == LU_REC_LEVELS && lu_row_fields_fit(), "a fiel
 // 31 120 B of the headline kernel's workgroup + the table: at 32 144 B five
 // workgroups no longer share a CU (measured), at 31 760 B they do
 static_assert(LU_REC_WORDS * sizeof(uint32_t) <= 640, "a larger row table may cost the headline kernel its fifth workgroup per CU: measure");
+
+// The compact row of the fused solve (lu_solve<..., FUSE>).  Bit c < 18 of a
+// row's bound can only be set before step c, so a row's bound holds column c
+// exactly when the row is a candidate of step c; the candidates of a level's
+// steps are disjoint, so a row holds at most one column below
+// lu_first_unfused_step() per level: the member its record names.  In the
+// other low columns it carries an exact zero through the whole solve.  The
+// fused solve therefore keeps a row in LU_COMPACT_W positions: position L <
+// LU_SLOTS is the row's level-L column (its "slot"; a zero where it has none),
+// the positions behind them are the columns from lu_first_unfused_step() on
+// (from an even position: their column pairs stay pairs).  The rows of a chain
+// share their ancestors, so above the chain's level their slots name the same
+// columns, and a pivot row's slot pair means to every row that takes it what
+// it means to the pivot row.
+constexpr int LU_SLOTS = LU_REC_LEVELS;
+constexpr int LU_COMPACT_W = LU_SLOTS + NV - lu_first_unfused_step();
+constexpr int lu_slot_col(int row, int lv) {   // the column in slot lv of the row, -1 without one
+    const int k = lu_row_chain(lv, row);
+    return k < 0 ? -1 : lu_level_member(lv, k);
+}
+constexpr int lu_compact_col(int row, int pos) {   // the column at a position of the row's compact form, -1: none
+    return pos < LU_SLOTS ? lu_slot_col(row, pos) : lu_first_unfused_step() + pos - LU_SLOTS;
+}
+constexpr uint32_t lu_row_bound(int row) {   // everything the row can hold during the solve (lu_struct_bound's cur[row] at its end)
+    uint32_t cur[NV] = {};
+    for (int r = 0; r < NV; r++) cur[r] = LU_STRUCT_PAT[r];
+    for (int i = 0; i < NV; i++)
+        for (int r = 0; r < NV; r++)
+            if ((cur[r] >> i) & 1u) cur[r] |= LU_BOUND.s[i];
+    return cur[row];
+}
+constexpr bool lu_slots_hold_the_bound() {   // every low column of a row's bound: a fused step, the one in the slot of its level
+    for (int r = 0; r < NV; r++) {
+        const uint32_t low = lu_row_bound(r) & ((1u << lu_first_unfused_step()) - 1u);
+        int per_level[LU_SLOTS] = {};
+        for (int c = 0; c < lu_first_unfused_step(); c++) {
+            if (!((low >> c) & 1u)) continue;
+            const int lv = LU_LEVELS.level[c];
+            if (!lu_step_fusable(c) || lv >= LU_SLOTS || ++per_level[lv] > 1 || lu_slot_col(r, lv) != c) return false;
+        }
+        for (int lv = 0; lv < LU_SLOTS; lv++)   // and a slot's column is in the bound
+            if (lu_slot_col(r, lv) >= 0 && !((low >> lu_slot_col(r, lv)) & 1u)) return false;
+    }
+    return true;
+}
+static_assert(lu_slots_hold_the_bound(), "a row's bound holds a low column outside its level's slot");
+static_assert(LU_SLOTS % 2 == 0 && lu_first_unfused_step() % 2 == 0 && LU_COMPACT_W == 16,
+              "the columns behind the slots keep their pairs; 4 slots and columns 18..29");
+// the slots a level's update can change: those of the columns of its members' bounds
+constexpr uint32_t lu_level_slots(int lv) {
+    uint32_t m = 0u;
+    for (int c = 0; c < lu_first_unfused_step(); c++)
+        if ((LU_LEVELS.cols[lv] >> c) & 1u) m |= 1u << LU_LEVELS.level[c];
+    return m;
+}
+static_assert(lu_level_slots(0) == 0xEu && lu_level_slots(1) == 0xCu && lu_level_slots(2) == 0x8u && lu_level_slots(3) == 0u,
+              "a level changes the slots above its own only");
+// The row form of a solve mode: the compact one for the fused solve, else the
+// 30 columns in place.  pos(c): the register position of column c >=
+// lu_first_unfused_step() (a low column's position is its level, and depends
+// on the row); W: the row's width.
+template <bool COMPACT>
+struct LuRowForm {
+    static constexpr int W = COMPACT ? LU_COMPACT_W : NV;
+    static constexpr int pos(int c) { return COMPACT ? c - (lu_first_unfused_step() - LU_SLOTS) : c; }
+};
 
 }  // namespace hc

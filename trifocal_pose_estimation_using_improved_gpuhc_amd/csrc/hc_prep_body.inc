@@ -489,6 +489,29 @@
             }
             A->gm[wv][q][l] = make_uint4(g[0], g[1], g[2], g[3]);
         }
+        // the compact row's gather map: position p of row r is column lu_compact_col(r, p), the
+        // structural zero where the row has no column at a level (and in the pad rows)
+        for (int i = tid; i < ABS_WAVES * ABS_GMC_Q * WAVE; i += PREP_THREADS) {
+            const int l = i & 63, q = (i >> 6) % ABS_GMC_Q, wv = (i >> 6) / ABS_GMC_Q;
+            const uint32_t sb = slot_base(wv * 64 + l);
+            const int row = l & 31;
+            uint32_t g[4];
+            for (int e = 0; e < 4; e++) {
+                const int pos = 4 * q + e;
+                int c = lu_first_unfused_step() + pos - LU_SLOTS;
+                if (pos < LU_SLOTS) {   // the member the row's record names at level pos
+                    const int mem = (int)((LU_ROWTAB.w[pos * LU_REC_ROWS + row] >> LU_REC_MEMBER_AT) & 31u);
+                    c = mem == LU_REC_NO_MEMBER ? -1 : mem;
+                }
+                uint32_t off = (uint32_t)SLOT_OFF_ENTZERO;
+                if (c >= 0 && row < NV) {
+                    const uint32_t w = T->gm[c >> 1][row];
+                    off = (c & 1) ? w >> 16 : w & 0xFFFFu;
+                }
+                g[e] = sb + off;
+            }
+            A->gmc[wv][q][l] = make_uint4(g[0], g[1], g[2], g[3]);
+        }
     }
     if (r == 0) {
         // eval_rhs masks: help term q of the helpers (no accumulation), light

@@ -573,12 +573,13 @@
             }
         }
         HC_DIAG_MARK(3);
-        cf rA[NV];
+        // (LUFUSE: the row in its compact form, LuRowForm<true> of hc_lu_struct.hpp, through gmc's words)
+        cf rA[LuRowForm<LUFUSE>::W];
         HC_ISA_MARK("ev_hx");
         bool ent_ok = true;   // ABSTAB: the entries' sums of squares are finite
         if constexpr (ABSTAB) {
-            uint4 gmv[ABS_GM_Q];
-            ent_ok = eval_hx_terms_abs(AT->hx[wv], l0, l16, AT->gm[wv], gmv);
+            uint4 gmv[LUFUSE ? ABS_GMC_Q : ABS_GM_Q];
+            ent_ok = eval_hx_terms_abs(AT->hx[wv], l0, l16, LUFUSE ? AT->gmc[wv] : AT->gm[wv], gmv);
             wave_lds_sync();
             HC_ISA_MARK("ev_gather");
             gather_hx_abs(rA, l0, gmv);
@@ -622,18 +623,20 @@
             }
             // (eval_hx without its phase marker: the ISA phase count keeps this rare
             // copy under redo_evals)
+            // (the dense solve takes the 30 columns, whatever form the sparse one's row had)
+            cf rD[NV];
             if constexpr (ABSTAB) {
                 uint4 gmv[ABS_GM_Q];
                 eval_hx_terms_abs(AT->hx[wv], l0, l16_r, AT->gm[wv], gmv);
                 wave_lds_sync();
-                gather_hx_abs(rA, l0, gmv);
+                gather_hx_abs(rD, l0, gmv);
             } else {
                 eval_hx_terms(s_hx, s_hxd, reinterpret_cast<char *>(&S), r_r);
                 wave_lds_sync();
-                gather_hx(rA, &s_rowc[0][0], S, r_r);
+                gather_hx(rD, &s_rowc[0][0], S, r_r);
             }
             wave_lds_sync();
-            k = lu_solve<true>(rA, rb, lane_v, row_pat, LB, S.ent, redo, HC_LU_COUNT(__ballot(act_r)));
+            k = lu_solve<true>(rD, rb, lane_v, row_pat, LB, S.ent, redo, HC_LU_COUNT(__ballot(act_r)));
         }
         wave_lds_sync();
 #ifdef HC_DIAG_PHASES

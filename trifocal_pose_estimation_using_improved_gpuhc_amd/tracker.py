@@ -656,3 +656,34 @@ def eval_variant_batched(variant, unified: np.ndarray, x: np.ndarray, target: np
               _abi.ptr(torch.cuda.current_stream(dev)))
     torch.cuda.synchronize(dev)
     return HX.cpu().numpy(), RHS.cpu().numpy(), OK.cpu().numpy()
+
+
+def compact_rows_batched(unified: np.ndarray, x: np.ndarray, target: np.ndarray, diff: np.ndarray,
+                         start_params: np.ndarray, t: np.ndarray, kind: np.ndarray, device="cuda:0"):
+    """hc_trifocal_compact_rows_batched (include/lu/hc_lu_compact_testing.h): the
+    rows of dH/dx in the compact form the throughput tracker gathers for its fused
+    solve, at n points; arguments as eval_variant_batched's.  Returns (rows (n, 30,
+    16, 2): position p of row r is column hc_lu_compact_column(r, p), rhs (n, 30, 2))."""
+    dev = _require_gpu(device)
+    n = x.shape[0]
+    U = torch.from_numpy(np.ascontiguousarray(unified, np.int32)).to(dev)
+    X = torch.from_numpy(np.ascontiguousarray(x, np.float32)).to(dev)
+    TG = torch.from_numpy(np.ascontiguousarray(target, np.float32)).to(dev)
+    DF = torch.from_numpy(np.ascontiguousarray(diff, np.float32)).to(dev)
+    SP = torch.from_numpy(np.ascontiguousarray(start_params, np.float32)).to(dev)
+    T = torch.from_numpy(np.ascontiguousarray(t, np.float32)).to(dev)
+    K = torch.from_numpy(np.ascontiguousarray(kind, np.uint8)).to(dev)
+    if tuple(X.shape) != (n, 31, 2) or tuple(TG.shape) != (n, 34, 2) or tuple(DF.shape) != (n, 34, 2) or \
+            tuple(SP.shape) != (34, 2) or tuple(T.shape) != (n,) or tuple(K.shape) != (n,) or U.numel() != 38880:
+        raise _abi.HCError("compact_rows_batched: x (n, 31, 2), target and diff (n, 34, 2), start_params (34, 2), "
+                           "t and kind (n,), a unified index of 38880 values")
+    ROWS = torch.full((n, 30, _abi.LU_COMPACT_WIDTH, 2), float("nan"), dtype=torch.float32, device=dev)
+    RHS = torch.empty((n, 30, 2), dtype=torch.float32, device=dev)
+    OK = torch.full((n, 32), 255, dtype=torch.uint8, device=dev)
+    wsb = int(_abi.lib().hc_trifocal_workspace_size())
+    ws = torch.zeros(wsb, dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize(dev)   # the hook runs on the null stream
+    _abi.call("hc_trifocal_compact_rows_batched", n, *(_abi.ptr(v) for v in (U, X, TG, DF, SP, T, K, ROWS, RHS, OK, ws)),
+              wsb)
+    torch.cuda.synchronize(dev)
+    return ROWS.cpu().numpy(), RHS.cpu().numpy()
